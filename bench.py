@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- process-tomography MLE reconstructions/sec (2-qubit, 100 iters) on MI355X.
 
-    python bench.py                                   # N = 1: headline + the secondary workloads
+    python bench.py --gpus 1 --steps K --warmup W     # the headline alone: set up, W + K steps, one JSON line
+    python bench.py --full                            # N = 1: headline + the secondary workloads, CPU baselines, parity
     python bench.py --gpus N --steps K --warmup W     # spawns its N ranks itself (one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N ...         # same ranks, launched by torchrun
@@ -10,12 +11,15 @@ A "step" is one pass of the hot path (fbx_pgdb_process_dev, FBX_MODE_FIXED, 100 
 of projected gradient descent with backtracking, fp64) over one batch that is already resident in HBM.
 
 OUTPUT: one short JSON line per secondary workload / parity leg first, and -- LAST -- the compact headline object the driver
-parses (< 4 KB: the contract's keys, `config`, `roofline`, `cpu_baseline`); the full record goes to gpurun_out/bench_detail.json
-(--detail-out).  See DESIGN.md section 5 and tests/test_bench_line.py.
+parses (< 4 KB: the contract's keys, `config`, `roofline`, `cpu_baseline`); with --full (or --workload) the full record goes
+to bench_out/bench_detail.json (--detail-out).  See DESIGN.md section 5 and tests/test_bench_line.py.
+--dump-outputs DIR writes what the headline's last timed step computed (every item's Choi matrix, cost and work
+counters; a fixed sample of the items beyond 64 MB) as DIR/<name>.npy in float64: the inputs are seeded, so two builds
+can be compared output for output.
 
 N = 1 (BASELINE.json configs[1], the configuration the metric is quoted on): 1024 independent 2-qubit
-process tomographies (Pauli in-basis, 540 settings, 1000 shots).  The same run also times, outside
-the headline's timed region and reported as secondary lines: the conversion sweeps of configs[2]
+process tomographies (Pauli in-basis, 540 settings, 1000 shots).  A plain run times that and nothing else.  --full also
+times, outside the headline's timed region and reported as secondary lines: the conversion sweeps of configs[2]
 (10^6 two-qubit / 65 536 three-qubit Kraus sets), the 3-qubit PGDB of configs[3] (batch 256, both in-bases), the
 single-qubit PGDB (2^20 experiments to convergence), the state-estimator half of the path (iterative MLE, 2 and 3 qubits,
 maxiter 100), the caller-side shot reduction (shots -> moments), configs[4]'s whole batch on one GPU, the converge-mode
@@ -54,6 +58,8 @@ sys.path.insert(0, os.path.join(ROOT, "forest-benchmarking_amd"))
 ALGO_FLOP_PER_RECON = 0.77e9
 FP64_PEAK_TFLOPS = 78.6          # MI355X fp64 vector == fp64 MFMA (v_mfma_f64_16x16x4) dense peak
 HBM_PEAK_GBS = 8000.0
+DETAIL_OUT = os.path.join(ROOT, "bench_out", "bench_detail.json")
+DUMP_MAX_BYTES = 60 << 20                 # --dump-outputs budget: below 64 MB with the .npy headers
 
 
 def parse():
@@ -71,8 +77,11 @@ def parse():
     ap.add_argument("--cpu-sample", type=int, default=16,
                     help="items run through the oracle for cpu_baseline, its reference-faithful and multi-core variants and "
                          "the parity self-check (0 = skip every CPU leg; ~25 s of one core at the default)")
-    ap.add_argument("--workload", default="all", choices=["all", "pgdb", "sweep", "sweep3", "pgdb3", "pgdb1", "mle_state", "mle_state3", "shots"],
-                    help="all (N = 1 default) = headline pgdb + every secondary leg; pgdb = headline only; "
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: N = 1 the secondary workloads, CPU baselines, parity checks and the "
+                         "65 536-item anchor (= --workload all); N > 1 the weak 1024-per-GPU figure")
+    ap.add_argument("--workload", default=None, choices=["all", "pgdb", "sweep", "sweep3", "pgdb3", "pgdb1", "mle_state", "mle_state3", "shots"],
+                    help="default: pgdb (headline only), all with --full; all = headline pgdb + every secondary leg; "
                          "sweep / pgdb3 / pgdb1 = that workload as the primary line")
     ap.add_argument("--sweep-items", type=int, default=1_000_000)
     ap.add_argument("--anchor-items", type=int, default=65536,
@@ -80,12 +89,24 @@ def parse():
                          "GPU -- the same-workload anchor of the 1/2/4/8-GPU strong-scaling curve (0 = skip)")
     ap.add_argument("--spawn-timeout", type=float, default=1800.0,
                     help="seconds the self-spawned ranks (--gpus > 1 without a launcher) may take before they are killed")
-    ap.add_argument("--detail-out", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="where the FULL record goes (every leg with its notes); stdout carries one short line per leg and, last, "
+    ap.add_argument("--detail-out", default=None,
+                    help="where the FULL record goes (every leg with its notes; default with --full or --workload: "
+                         "bench_out/bench_detail.json, a plain run writes none); stdout carries one short line per leg and, last, "
                          "the compact headline the driver parses")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's last step computed as DIR/<name>.npy (float64, "
+                         "at most 64 MB: a fixed sample of the items beyond that)")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="testing: allow more ranks than visible GPUs (ranks share devices; host-file barrier)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    explicit = args.workload is not None
+    if args.workload is None:
+        args.workload = "all" if args.full else "pgdb"
+    if args.dump_outputs and args.workload not in ("pgdb", "all"):
+        ap.error("--dump-outputs writes the headline's outputs (workload pgdb or all)")
+    if args.detail_out is None:
+        args.detail_out = DETAIL_OUT if (args.full or explicit) else ""
+    return args
 
 
 # ================================================================================== rank spawning
@@ -735,6 +756,24 @@ class PgdbBatch:
     def choi(self, n):
         return self.d_choi.to_array(np.complex128, (n, 16, 16))
 
+    def dump(self, directory, first_item):
+        """What a caller of fbx_pgdb_process_dev receives for this batch -- the Choi matrices (real, imaginary as the last
+        axis), the final costs, the outer / Dykstra / backtracking iteration counts and the work counters -- as float64 .npy
+        files.  Beyond DUMP_MAX_BYTES in all a fixed (seeded) sample of the items; item_index.npy names the items written."""
+        B = self.B
+        per_item = 8 * (16 * 16 * 2 + 1 + 3 + 4 + 1)
+        idx = np.arange(B)
+        if B * per_item > DUMP_MAX_BYTES:
+            idx = np.sort(np.random.RandomState(0).choice(B, DUMP_MAX_BYTES // per_item, replace=False))
+        st = self.stats()
+        out = {"choi": self.choi(B)[idx].view(np.float64).reshape(len(idx), 16, 16, 2),
+               "cost": self.d_cost.to_array(np.float64, (B,))[idx],
+               "iterations": st["iterations"][idx], "dykstra_iters": st["dykstra"][idx], "backtracks": st["backtracks"][idx],
+               "work": st["work"][idx], "item_index": first_item + idx}
+        os.makedirs(directory, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
     def free(self):
         for b in (self.d_e, self.d_c, self.d_choi, self.d_it, self.d_dy, self.d_bt, self.d_cost, self.d_work):
             b.free()
@@ -795,9 +834,12 @@ def run_pgdb(args, comm, _lib, synthetic, rank_info):
         batch = PgdbBatch(_lib, synthetic, args.in_basis, hi - lo, lo)
         scaling, shards = "strong", f"contiguous blocks of a {total}-item batch, distinct seeds (items {lo}..{hi - 1} on this rank, all distinct)"
     else:
-        batch = PgdbBatch(_lib, synthetic, args.in_basis, args.batch, rank * args.batch)
+        lo = rank * args.batch
+        batch = PgdbBatch(_lib, synthetic, args.in_basis, args.batch, lo)
         scaling, shards = "weak", "distinct seeds per rank"
     elapsed, kms = timed_steps(lambda: batch.launch(_lib.MODE_FIXED, args.iters), args.steps, args.warmup, comm, _lib)
+    if args.dump_outputs and rank == 0:
+        batch.dump(args.dump_outputs, lo)                    # the last timed step's outputs (rank 0's items when N > 1)
     st = batch.stats()
     total_recons = (total if total > 0 else world * batch.B) * args.steps
     kernel_s = kms / 1e3 / args.steps
@@ -822,7 +864,7 @@ def run_pgdb(args, comm, _lib, synthetic, rank_info):
                    "mean_backtracks": sums[2] / sums[4], "mean_jacobi_sweeps": sums[3] / sums[4]},
         "roofline": pgdb_roofline(batch, st, kernel_s, args.iters),
     }
-    if world > 1 and total > 0:
+    if world > 1 and total > 0 and args.full:
         # the N = 1-comparable figure: configs[1]'s 1024 items on every rank (weak scaling)
         batch.free()
         wb = PgdbBatch(_lib, synthetic, args.in_basis, args.batch, rank * args.batch)
@@ -985,7 +1027,7 @@ def single_gpu_extras(args, comm, _lib, synthetic, batch, line):
 
 # ================================================================================== output
 # What the driver keeps of a run is the tail of stdout, and it parses the LAST line.  Round 5's single 20 KB line outgrew
-# that; since round 6 the full record goes to gpurun_out/bench_detail.json, every secondary workload is printed as its own
+# that; since round 6 the full record goes to bench_out/bench_detail.json, every secondary workload is printed as its own
 # short line FIRST, and the last stdout line is the compact headline object (< 4 KB; tests/test_bench_line.py).
 HEADLINE_MAX_BYTES = 4096
 _ROOFLINE_KEEP = ("bound", "achieved", "peak", "unit", "frac", "measured_frac", "mfma_frac", "traffic", "kernel", "kernel_ms")
@@ -1044,7 +1086,7 @@ def compact_secondary(line):
     return _sig(out)
 
 
-def compact_headline(line):
+def compact_headline(line, detail=None):
     """The LAST stdout line: the bench contract's keys + `roofline` + `cpu_baseline`, with everything the driver's record should
     keep folded into `config` as bare numbers.  Always < HEADLINE_MAX_BYTES."""
     cfg = line.get("config", {})
@@ -1078,7 +1120,8 @@ def compact_headline(line):
     if "secondary" in line:
         c["secondary"] = {s.get("tag", _short(s["metric"], 60)): {"value": s["value"], **_pick(compact_roofline(s.get("roofline")), ("frac",))}
                           for s in line["secondary"]}
-    c["detail"] = "earlier stdout lines + gpurun_out/bench_detail.json"
+    if detail:
+        c["detail"] = f"earlier stdout lines + {detail}"
     out = {k: line[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                 "scaling", "vs_baseline", "dtype", "data") if k in line}
     out["config"] = c
@@ -1097,15 +1140,19 @@ def compact_headline(line):
 
 
 def emit(line, stream=None, detail_out=None):
-    """Full record -> gpurun_out/bench_detail.json; per-workload detail lines; the compact headline LAST."""
+    """Full record -> bench_out/bench_detail.json (detail_out = "": none); per-workload detail lines; the compact headline LAST."""
     stream = stream or sys.stdout
-    detail_out = detail_out or os.path.join(ROOT, "gpurun_out", "bench_detail.json")
-    try:
-        os.makedirs(os.path.dirname(detail_out), exist_ok=True)
-        with open(detail_out, "w") as fh:
-            json.dump(line, fh)
-    except OSError:
-        pass
+    if detail_out is None:
+        detail_out = os.path.join(ROOT, "bench_out", "bench_detail.json")
+    detail = None
+    if detail_out:
+        try:
+            os.makedirs(os.path.dirname(detail_out), exist_ok=True)
+            with open(detail_out, "w") as fh:
+                json.dump(line, fh)
+            detail = os.path.relpath(detail_out, ROOT) if detail_out.startswith(ROOT + os.sep) else detail_out
+        except OSError:
+            pass
     for sec in line.get("secondary", []):
         print(json.dumps(compact_secondary(sec)), file=stream)
     for key in ("parity_vs_reference_fixtures", "parity_self_check", "pcie_inclusive", "single_experiment_latency_ms"):
@@ -1118,7 +1165,7 @@ def emit(line, stream=None, detail_out=None):
                  "workload": _short(val.get("workload", ""), 200), "roofline": compact_roofline(val.get("roofline")),
                  "pcie_inclusive": val.get("pcie_inclusive")}
             print(json.dumps(_sig(d)), file=stream)
-    head = compact_headline(line)
+    head = compact_headline(line, detail)
     text = json.dumps(head)
     assert len(text) < HEADLINE_MAX_BYTES, len(text)
     print(text, file=stream, flush=True)

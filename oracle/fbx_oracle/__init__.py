@@ -5,9 +5,9 @@ THIS IS TEST INFRASTRUCTURE, NOT PRODUCT CODE.  Only ``tests/``,
 there only as the checker / the timed CPU baseline.  The product (``fbx`` package +
 ``libfbx.so``) never imports, links or executes anything in this directory.
 
-Parity status: PINNED.  Every function here is checked (a) against the reference itself,
-imported in the build container through ``tests/golden/_ref_harness.py`` (see
-``tests/test_oracle_vs_reference.py``; skipped where /root/reference is absent) and
+Parity status: PINNED.  Every function here is checked (a) against the reference's own
+answers on the same inputs, recorded through ``tests/golden/_ref_harness.py`` into
+``tests/golden/oracle_cases.npz`` (see ``tests/test_oracle_vs_reference.py``) and
 (b) against the committed golden vectors under ``tests/golden/`` which were produced by
 running the reference (``tests/golden/make_goldens.py``) and by transcribing the
 known-answer values of the reference's own test-suite (``tests/golden/known_answers.py``).

@@ -13,15 +13,6 @@ sys.dont_write_bytecode = True
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "reference: needs /root/reference (build container only)")
-
-
-def pytest_collection_modifyitems(config, items):
-    ref_ok = os.path.isdir("/root/reference/forest/benchmarking")
-    skip_ref = pytest.mark.skip(reason="/root/reference not present (GPU box)")
-    for item in items:
-        if "reference" in item.keywords and not ref_ok:
-            item.add_marker(skip_ref)
 
 
 @pytest.fixture(scope="session")

@@ -545,8 +545,126 @@ def make_sweep_3q(batch=6):
     print("sweep 3q done", {k: v.shape for k, v in out.items()})
 
 
+def make_oracle_cases():
+    """tests/test_oracle_vs_reference.py: the reference's answers on exactly the inputs that test presents to the oracle
+    and the shim (settings as text, design matrices, estimates, operator tools, shot moments, text forms, beta draws)."""
+    import json
+    out = {}
+    # settings in the reference's order, as text (the interchange schema)
+    for qubits in ([0], [3], [0, 1], [5, 2], [3, 1], [2, 0, 1]):
+        key = "_".join(map(str, qubits))
+        out[f"state_settings_{key}"] = np.array([str(s) for s in T._state_tomo_settings(qubits)])
+        if len(qubits) < 3:
+            for basis in ("pauli", "sic"):
+                settings = process_settings(qubits, basis)
+                out[f"process_settings_{key}_{basis}"] = np.array([str(s) for s in settings])
+                step = max(1, len(settings) // 7)
+                out[f"process_roundtrip_{key}_{basis}"] = np.array(
+                    [str(OE.ExperimentSetting.from_str(str(s))) for s in settings[::step]])
+    # design matrix and counts vector of _extract_from_results
+    rs = np.random.RandomState(0)
+    for n, basis in ((1, "pauli"), (2, "sic")):
+        qubits = list(range(n))
+        settings = process_settings(qubits, basis)
+        e = rs.uniform(-1, 1, len(settings)); c = rs.randint(100, 1000, len(settings))
+        A, nvec = T._extract_from_results(ref_results(settings, e, c), qubits[::-1])
+        out[f"extract_{n}q_{basis}_e"], out[f"extract_{n}q_{basis}_c"] = e, c
+        out[f"extract_{n}q_{basis}_A"], out[f"extract_{n}q_{basis}_n"] = A, nvec
+    # PGDB on the canonical order, and trace-non-increasing on a permuted list with a repeated setting
+    _, _, e, c = synthetic.process_batch(1, "sic", 2, first_item=40)
+    settings = process_settings([0], "sic")
+    out["pgdb_e"], out["pgdb_c"] = e, c
+    for b in range(2):
+        res = ref_results(settings, e[b], c[b])
+        out[f"pgdb_tp_{b}"] = T.pgdb_process_estimate(res, [0])
+        perm = np.random.RandomState(b).permutation(len(res))
+        out[f"pgdb_tni_{b}"] = T.pgdb_process_estimate([res[i] for i in perm] + [res[1]], [0], trace_preserving=False)
+    # state estimators, 2 qubits
+    _, _, e, c = synthetic.state_batch(2, 2, first_item=7, mixed=0.05)
+    settings = list(T._state_tomo_settings([0, 1]))
+    out["state_e"], out["state_c"] = e, c
+    for b in range(2):
+        res = ref_results(settings, e[b], c[b])
+        lin = T.linear_inv_state_estimate(res, [0, 1])
+        out[f"state_linv_{b}"] = lin
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            out[f"state_mle30_{b}"] = T.iterative_mle_state_estimate(res, [0, 1], maxiter=30)
+        out[f"state_rho_{b}"] = rho = np.asarray(lin)
+        out[f"state_R_{b}"] = T._R(rho, res, [1, 0])
+        out[f"state_loglik_{b}"] = np.float64(T.state_log_likelihood(rho, res, [0, 1]))
+    # operator tools and distance measures on random operators
+    rs = np.random.RandomState(5)
+    for d in (2, 4):
+        D = d * d
+        x = rs.randn(D, D) + 1j * rs.randn(D, D)
+        h = x + x.conj().T
+        out[f"ot{d}_x"] = x
+        for name in ("choi2superop", "superop2choi", "choi2pauli_liouville", "pauli_liouville2choi",
+                     "superop2pauli_liouville", "pauli_liouville2superop", "chi2choi", "chi2pauli_liouville",
+                     "chi2superop", "proj_choi_to_trace_preserving", "proj_choi_to_trace_non_increasing",
+                     "proj_choi_to_completely_positive"):
+            out[f"ot{d}_{name}"] = getattr(OT, name)(x)
+        for name in ("choi2chi", "superop2chi", "pauli_liouville2chi", "proj_choi_to_physical", "proj_choi_to_unitary"):
+            arg = h if name != "superop2chi" else OT.choi2superop(h)
+            if name == "pauli_liouville2chi":
+                arg = OT.choi2pauli_liouville(h)
+            out[f"ot{d}_arg_{name}"] = arg
+            out[f"ot{d}_{name}"] = getattr(OT, name)(arg)
+        out[f"ot{d}_computational2pauli_basis_matrix"] = OT.computational2pauli_basis_matrix(d)
+        g = rs.randn(d, d) + 1j * rs.randn(d, d)
+        rho = g @ g.conj().T; rho /= np.trace(rho)
+        g = rs.randn(d, d) + 1j * rs.randn(d, d)
+        sig = g @ g.conj().T; sig /= np.trace(sig)
+        out[f"dm{d}_rho"], out[f"dm{d}_sigma"] = rho, sig
+        for name in ("fidelity", "trace_distance", "bures_distance", "bures_angle", "hilbert_schmidt_ip", "purity"):
+            out[f"dm{d}_{name}"] = np.asarray(getattr(DM, name)(rho, sig) if name != "purity" else DM.purity(rho))
+        out[f"dm{d}_watrous_bounds"] = np.array(DM.watrous_bounds(h))
+    # shots -> observable moments
+    rs = np.random.RandomState(9)
+    qubits = [3, 0, 5]
+    bits = (rs.uniform(size=(500, 3)) < 0.3).astype(int)
+    out["shots_bits"] = bits
+    for k, (ops, coef) in enumerate((({3: "X", 5: "Z"}, 1.0), ({0: "Y"}, -0.7), ({}, 2.0), ({3: "Z", 0: "Z", 5: "Z"}, 1.0))):
+        term = ref.PauliTerm("I", 0, coef)
+        term._ops = dict(ops)
+        for prior in (False, True):
+            out[f"shots_{k}_{int(prior)}"] = np.array(OE.shots_to_obs_moments(bits, qubits, term, prior), dtype=float)
+    out["ratio_variance"] = np.float64(OE.ratio_variance(1.0, 0.1, 2.0, 0.05))
+    # record serialisation and one-qubit state texts
+    rs_ = OE.ExperimentSetting(OE.plusX(0) * OE.SIC2(1), ref.PauliTerm.from_list([("X", 0), ("Z", 1)]))
+    rr = OE.ExperimentResult(setting=rs_, expectation=0.25, std_err=0.01, total_counts=500, raw_expectation=0.2)
+    out["record_setting"] = np.array(str(rs_))
+    out["record_json"] = np.array(json.dumps(rr, cls=OE.OperatorEncoder))
+    texts = ("X+_0", "Y-_12", "SIC3_7", " Z+_1 ")
+    out["oneq_texts"] = np.array(texts)
+    out["oneq_strs"] = np.array([str(OE._OneQState.from_str(t)) for t in texts])
+    bad = ("X+", "nonsense", "X?_1")
+    raised = []
+    for t in bad:
+        try:
+            OE._OneQState.from_str(t)
+            raised.append(False)
+        except ValueError:
+            raised.append(True)
+    out["oneq_bad"], out["oneq_bad_raises"] = np.array(bad), np.array(raised)
+    # the beta resampling's draw order
+    settings = list(T._state_tomo_settings([0, 1]))
+    rs = np.random.RandomState(3)
+    e = rs.uniform(-0.9, 0.9, size=len(settings))
+    res = [OE.ExperimentResult(setting=s, expectation=float(x), std_err=0.0, total_counts=300) for s, x in zip(settings, e)]
+    np.random.seed(77)
+    out["beta_e"] = e
+    out["beta_resampled"] = np.array([r.expectation for r in T._resample_expectations_with_beta(res)])
+    np.savez_compressed(os.path.join(HERE, "oracle_cases.npz"), **out)
+    print("oracle cases done")
+
+
 if __name__ == "__main__":
     np.random.seed(0)
+    if "--oracle-cases" in sys.argv:      # the reference's answers for tests/test_oracle_vs_reference.py
+        make_oracle_cases()
+        sys.exit(0)
     if "--sweep3q" in sys.argv:
         make_sweep_3q()
         sys.exit(0)

@@ -1,11 +1,12 @@
 """bench.py's output contract (CPU): the LAST stdout line is a compact headline object that the driver's 8 KB tail keeps
 whole -- round 5's single 20 KB line came back as `parsed: null` -- with `roofline` and `cpu_baseline` inside; every other
-line is a self-contained JSON object as well; the full record goes to gpurun_out/bench_detail.json."""
+line is a self-contained JSON object as well; the full record goes to bench_out/bench_detail.json."""
 import io
 import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,7 +73,7 @@ def test_every_line_parses_and_the_tail_holds_the_headline(tmp_path, monkeypatch
         assert len(ln) < 2048 or ln is lines[-1], (len(ln), ln[:80])
     tail = "\n".join(lines)[-8192:]
     assert tail.endswith(lines[-1]) and json.loads(tail.splitlines()[-1])["roofline"]["kernel"].startswith("pgdb_kernel")
-    detail = json.load(open(tmp_path / "gpurun_out" / "bench_detail.json"))
+    detail = json.load(open(tmp_path / "bench_out" / "bench_detail.json"))
     assert "secondary" in detail and "strong_65536" in detail                    # nothing is lost: the full record is on disk
 
 
@@ -85,3 +86,48 @@ def test_headline_shrinks_rather_than_overflowing(tmp_path, monkeypatch):
     assert len(lines[-1]) < 4096
     head = json.loads(lines[-1])
     assert "roofline" in head and "cpu_baseline" in head and "secondary" not in head["config"]
+
+
+class _HostBuffer:
+    """Stands in for a DeviceBuffer: to_array hands back the stored array."""
+
+    def __init__(self, a):
+        self.a = a
+
+    def to_array(self, dtype, shape):
+        return np.ascontiguousarray(self.a, dtype=dtype).reshape(shape)
+
+
+def _fake_batch(B):
+    rs = np.random.RandomState(1)
+    b = bench.PgdbBatch.__new__(bench.PgdbBatch)
+    b.B = B
+    b.d_choi = _HostBuffer(rs.randn(B, 16, 16) + 1j * rs.randn(B, 16, 16))
+    b.d_cost = _HostBuffer(rs.randn(B))
+    b.d_it, b.d_dy, b.d_bt = (_HostBuffer(rs.randint(0, 100, B)) for _ in range(3))
+    b.d_work = _HostBuffer(rs.randint(0, 1000, (B, 4)))
+    return b
+
+
+def test_dump_outputs_are_float64_files_of_every_item(tmp_path):
+    b = _fake_batch(8)
+    b.dump(str(tmp_path), 16)
+    names = {"choi", "cost", "iterations", "dykstra_iters", "backtracks", "work", "item_index"}
+    assert {f[:-4] for f in os.listdir(tmp_path)} == names
+    arrays = {n: np.load(tmp_path / f"{n}.npy") for n in names}
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    choi = b.d_choi.a
+    assert np.array_equal(arrays["choi"][..., 0], choi.real) and np.array_equal(arrays["choi"][..., 1], choi.imag)
+    assert np.array_equal(arrays["item_index"], np.arange(16, 24)) and arrays["work"].shape == (8, 4)
+
+
+def test_dump_outputs_sample_stays_within_the_budget_and_is_fixed(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40_000)
+    b = _fake_batch(64)
+    for d in ("a", "b"):
+        b.dump(str(tmp_path / d), 0)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    idx = np.load(tmp_path / "a" / "item_index.npy").astype(int)
+    assert 0 < len(idx) < 64 and total < 40_000 + 7 * 128
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "item_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "cost.npy"), b.d_cost.a[idx])

@@ -105,8 +105,17 @@ def _expected():
 
 
 def test_two_rank_sharding_gloo(tmp_path):
-    import torch.multiprocessing as mp
-    mp.spawn(_gloo_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    # torch is imported by the workers only: in this process its own HIP runtime and RCCL would shadow the ones
+    # libfbx.so loads for the GPU tests that run after this one
+    import multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    port = _free_port()
+    procs = [ctx.Process(target=_gloo_worker, args=(r, 2, port, str(tmp_path))) for r in range(2)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(120)
+        assert p.exitcode == 0
     a = np.load(tmp_path / "full_gloo_0.npy"); b = np.load(tmp_path / "full_gloo_1.npy")
     assert a.shape == (7, 4, 4) and np.array_equal(a, b)
     assert np.allclose(a, _expected(), atol=1e-14)

@@ -67,8 +67,8 @@ def _bench(*args):
 
 def test_bench_spawns_its_own_ranks(gpu):
     """`python bench.py --gpus 2` with no launcher: two ranks, the configs[4]-shaped strong split (scaled down),
-    the weak 1024-per-GPU leg (scaled down), one JSON line from rank 0."""
-    line, full = _bench("--gpus", "2", "--oversubscribe", "--steps", "2", "--warmup", "1", "--total-batch", "600",
+    the weak 1024-per-GPU leg (scaled down, --full), one JSON line from rank 0."""
+    line, full = _bench("--gpus", "2", "--oversubscribe", "--full", "--steps", "2", "--warmup", "1", "--total-batch", "600",
                         "--batch", "128", "--iters", "20")
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["steps"] == 2
     assert line["config"]["total_batch"] == 600 and line["config"]["batch_per_gpu"] == 300

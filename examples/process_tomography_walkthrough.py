@@ -48,6 +48,8 @@ def main(shots=2000, n_boot=40, verbose=True):
            "fidelity_pgdb": dm.process_fidelity(ptm_ideal, choi2pauli_liouville(choi_mle)),
            "fidelity_closest_unitary": dm.process_fidelity(ptm_ideal, choi2pauli_liouville(choi_unitary)),
            "diamond_norm_bounds_to_ideal": dm.watrous_bounds(choi_mle - kraus2choi(cnot))}
+    choi_ideal = kraus2choi(cnot)
+    out["diamond_norm_to_ideal"] = float(dm.diamond_norm_distance_batch(choi_mle, choi_ideal)[0])   # the reference: diamond_norm_distance
     for k, v in out.items():
         say(f"{k}: {v}")
 
@@ -55,6 +57,10 @@ def main(shots=2000, n_boot=40, verbose=True):
     mean, var = tomography.process_fidelity_variance_batch(design, expect, counts, ptm_ideal, n_resamples=n_boot, seed=1)
     out["bootstrap_fidelity"] = (float(mean[0]), float(np.sqrt(var[0])))
     say(f"process fidelity {mean[0]:.4f} +- {np.sqrt(var[0]):.4f}  ({n_boot} resamples)")
+    mean, var = tomography.process_diamond_distance_variance_batch(design, expect, counts, choi_ideal, n_resamples=n_boot, seed=1)
+    out["diamond_norm_to_ideal_std"] = float(np.sqrt(var[0]))
+    say(f"diamond-norm distance {out['diamond_norm_to_ideal']:.4f} +- {out['diamond_norm_to_ideal_std']:.4f}  (bootstrap mean {mean[0]:.4f})")
+    out["choi_estimate"], out["choi_ideal"] = choi_mle, choi_ideal
 
     # 6. what the reference's plot_pauli_transfer_matrix would draw
     ptm, labels = plotting.pauli_transfer_matrix_plot_inputs(choi_mle)

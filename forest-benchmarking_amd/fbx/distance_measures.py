@@ -335,3 +335,46 @@ def diamond_norm_distance(choi0: np.ndarray, choi1: np.ndarray) -> float:
     problem = cvx.Problem(cvx.Maximize(cvx.real(cvx.trace(delta.conj().T @ w))), constraints)
     problem.solve()
     return problem.value * 2
+
+
+def diamond_norm_distance_batch(choi0, choi1, tol: float = 1e-7, max_iters: int = 200, return_bounds: bool = False,
+                                return_inputs: bool = False):
+    """Diamond-norm distances of B pairs of channels on the device (fbx_diamond_norm; 1..3 qubits): ``choi0`` [B, D, D] (or one
+    [D, D]), ``choi1`` [B, D, D] or one shared [D, D] target.  Same quantity as ``diamond_norm_distance``: the SDP of Watrous
+    reduced to the concave maximisation of g(rho) = tr[((1 (x) rho^1/2) J (1 (x) rho^1/2))_+] over input states, solved per pair by
+    quasi-Newton ascent (the lower bound, returned) and certified by a dual-feasible point (the upper bound): every pair stops once
+    (upper - lower) <= tol * max(lower, 1e-12), or after ``max_iters`` steps.
+
+    Returns dist[B]; with ``return_bounds`` also upper[B] and iters[B] (int32, negative where tol was not reached -- both bounds
+    still hold); with ``return_inputs`` also the maximising input states rho[B, d, d].  Order: (dist, upper, iters, rho)."""
+    c0 = _lib.c128(choi0)
+    c1 = _lib.c128(choi1)
+    if c0.ndim == 2:
+        c0 = c0[None]
+    if c0.ndim != 3 or c0.shape[-1] != c0.shape[-2]:
+        raise ValueError("choi0 must be [B, D, D] or [D, D]")
+    B, D = c0.shape[0], c0.shape[-1]
+    dim = int(round(np.sqrt(D)))
+    if dim * dim != D or D < 4:
+        raise ValueError("Choi matrices must be D x D with D = d^2")
+    n = _nq(dim)
+    if c1.shape == (D, D):
+        shared = 1
+    elif c1.shape == (B, D, D):
+        shared = 0
+    else:
+        raise ValueError("choi1 must be [B, D, D] or [D, D] matching choi0")
+    dist = np.empty(B)
+    upper = np.empty(B) if return_bounds else None
+    iters = np.empty(B, dtype=np.int32) if return_bounds else None
+    rho = np.empty((B, dim, dim), dtype=np.complex128) if return_inputs else None
+    if B:
+        _lib.check(_lib.lib().fbx_diamond_norm(
+            n, B, _lib.dptr(c0.view(np.float64)), _lib.dptr(c1.view(np.float64)), shared, float(tol), int(max_iters),
+            _lib.dptr(dist), _lib.dptr(upper), None if rho is None else _lib.dptr(rho.view(np.float64)), _lib.iptr(iters)))
+    out = (dist,)
+    if return_bounds:
+        out += (upper, iters)
+    if return_inputs:
+        out += (rho,)
+    return out[0] if len(out) == 1 else out

@@ -440,6 +440,49 @@ def process_fidelity_variance_batch(design: Design, expectations, total_counts, 
     return fid.mean(axis=0), fid.var(axis=0)
 
 
+def process_diamond_distance_variance_batch(design: Design, expectations, total_counts, target_choi,
+                                            n_resamples: int = 40, seed: int = 0, prior_counts=1,
+                                            trace_preserving=True, mode="converge", max_iters=0,
+                                            tol=1e-7, diamond_max_iters=200, return_samples=False):
+    """Bootstrap error bars of the diamond-norm distance of B process tomographies to ``target_choi`` ([D, D] or [B, D, D]):
+    the diamond analogue of ``process_fidelity_variance_batch``.  Every experiment is resampled ``n_resamples`` times (Beta
+    posterior, fbx_beta_resample), all ``n_resamples * B`` resampled experiments are reconstructed by PGDB in one launch and
+    their diamond distances to the target solved on the device (fbx_diamond_norm, ``tol`` / ``diamond_max_iters`` as in
+    ``distance_measures.diamond_norm_distance_batch``); nothing leaves HBM in between.
+    Returns (mean[B], var[B]) (and the [n_resamples, B] distances with ``return_samples``)."""
+    if mode not in ("converge", "fixed"):
+        raise ValueError("mode must be 'converge' or 'fixed'")
+    e, c = _batch_arrays(design, expectations, total_counts)
+    B, m, n, D = e.shape[0], design.m, design.n_qubits, design.dim ** 2
+    R = int(n_resamples)
+    tgt = np.asarray(target_choi, dtype=np.complex128)
+    if tgt.shape not in ((D, D), (B, D, D)):
+        raise ValueError("target_choi must be [D, D] or [B, D, D]")
+    if R < 1 or B == 0:
+        raise ValueError("need n_resamples >= 1 and a non-empty batch")
+    lib, DB = _lib.lib(), _lib.DeviceBuffer
+    d_e, d_c = DB.from_array(e), DB.from_array(c)
+    d_er, d_cr = DB(R * B * m * 8), DB(R * B * m * 8)
+    _lib.check(lib.fbx_beta_resample_dev(B * m, R, d_e.ptr, d_c.ptr, float(prior_counts),
+                                         int(seed) & (2 ** 64 - 1), d_er.ptr, d_cr.ptr))
+    d_choi = DB(R * B * D * D * 16)
+    _lib.check(lib.fbx_pgdb_process_dev(design.handle, R * B, d_er.ptr, d_cr.ptr, int(bool(trace_preserving)),
+                                        _lib.MODE_FIXED if mode == "fixed" else _lib.MODE_CONVERGE, int(max_iters),
+                                        d_choi.ptr, None, None, None, None, None))
+    shared = tgt.ndim == 2
+    d_tgt = DB.from_array(np.ascontiguousarray(tgt if shared else np.broadcast_to(tgt, (R, B, D, D))))
+    d_dist = DB(R * B * 8)
+    _lib.check(lib.fbx_diamond_norm_dev(n, R * B, d_choi.ptr, d_tgt.ptr, int(shared), float(tol), int(diamond_max_iters),
+                                        d_dist.ptr, None, None, None))
+    _lib.synchronize()
+    dist = d_dist.to_array(np.float64, (R, B))
+    for buf in (d_e, d_c, d_er, d_cr, d_choi, d_tgt, d_dist):
+        buf.free()
+    if return_samples:
+        return dist.mean(axis=0), dist.var(axis=0), dist
+    return dist.mean(axis=0), dist.var(axis=0)
+
+
 def estimate_by_qubit_groups(results, qubit_groups, kind="process", estimator="pgdb", **kwargs):
     """Tomography of several qubit groups measured in one (merged) experiment: split the results
     with ``get_results_by_qubit_groups`` (observable_estimation.py:1145-1173, the process notebook's

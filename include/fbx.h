@@ -27,7 +27,7 @@
  *    itertools.product('IXYZ', repeat=n) with qubits[0] the left-most tensor factor.
  *  - sizes: the estimators, projections, state measures and channel application take 1..3 qubits
  *    (fbx_kraus_sweep is one fused kernel for 1..2 and a composition of the pairwise conversions for 3);
- *    fbx_convert and fbx_process_fidelity 1..5 qubits; fbx_eigh / fbx_matmul any N <= 1024;
+ *    fbx_convert and fbx_process_fidelity 1..5 qubits; fbx_diamond_norm 1..3 qubits; fbx_eigh / fbx_matmul any N <= 1024;
  *    fbx_convert_general and fbx_partial_trace any dimension (each entry point states its own range).
  *  - label codes: one-qubit input states 0:X+ 1:X- 2:Y+ 3:Y- 4:Z+ 5:Z- 6:SIC0 7:SIC1
  *    8:SIC2 9:SIC3; one-qubit Paulis 0:I 1:X 2:Y 3:Z.
@@ -360,6 +360,19 @@ int fbx_process_fidelity(int n_qubits, int64_t B, const double* ptm0, const doub
                          double* fe_out, double* fp_out);
 int fbx_process_fidelity_dev(int n_qubits, int64_t B, const double* d_ptm0, const double* d_ptm1,
                              double* d_fe_out, double* d_fp_out);
+
+/* Diamond-norm distance of B pairs of channels (distance_measures.py:378-437), Choi matrices [B][D][D], D = 4^n_qubits,
+ * n_qubits 1..3 (others FBX_ERR_UNSUPPORTED).  choi1 is [B][D][D], or one shared [D][D] when choi1_shared != 0.  Every pair is
+ * solved to a certified relative gap: dist_out[b] = 2 g(rho) for the returned input state rho (a lower bound, g(rho) =
+ * tr[((1 (x) rho^1/2) J (1 (x) rho^1/2))_+], J the Hermitian part of choi0 - choi1), upper_out[b] an upper bound from a
+ * dual-feasible certificate; the search stops once upper - dist <= tol * max(dist, 1e-12) (tol <= 0: 1e-7) or after
+ * max_iters quasi-Newton steps.  rho_out [B][d][d] (the maximising input state), iters_out[B] (steps taken; negative when
+ * tol was not reached -- the bounds still hold).  upper_out, rho_out, iters_out may be NULL.  A non-finite input gives a NaN
+ * result for that pair only. */
+int fbx_diamond_norm(int n_qubits, int64_t B, const double* choi0, const double* choi1, int choi1_shared, double tol,
+                     int max_iters, double* dist_out, double* upper_out, double* rho_out, int32_t* iters_out);
+int fbx_diamond_norm_dev(int n_qubits, int64_t B, const double* d_choi0, const double* d_choi1, int choi1_shared, double tol,
+                         int max_iters, double* d_dist_out, double* d_upper_out, double* d_rho_out, int32_t* d_iters_out);
 
 /* State measures (distance_measures.py:14-114, :198): purity tr(rho^2), fidelity
  * (tr sqrt(sqrt(rho) sigma sqrt(rho)))^2, trace_distance = 0.5 * induced 1-norm,

@@ -134,6 +134,8 @@ PROTOTYPES = {
     "fbx_beta_resample_dev": [_i64, _i64, _vp, _vp, C.c_double, C.c_uint64, _vp, _vp],
     "fbx_diamond_norm": [C.c_int, _i64, _dp, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _ip],
     "fbx_diamond_norm_dev": [C.c_int, _i64, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp, _vp],
+    "fbx_chernoff_bound": [C.c_int, _i64, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_double, _dp, _dp, _dp, _ip],
+    "fbx_chernoff_bound_dev": [C.c_int, _i64, _vp, _vp, C.c_int, C.c_double, C.c_int, C.c_double, _vp, _vp, _vp, _vp],
 }
 
 

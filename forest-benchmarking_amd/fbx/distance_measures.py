@@ -3,7 +3,7 @@
 Mirror of forest/benchmarking/distance_measures.py.  Scalars are returned as python floats
 like the reference (``np.real_if_close(...).item()``).  ``*_batch`` variants take stacked
 matrices ``[B, d, d]``.  ``quantum_chernoff_bound`` and ``watrous_bounds`` take their spectra from
-the device eigensolver; ``diamond_norm_distance`` is the reference's cvxpy semidefinite program
+the device eigensolver (``quantum_chernoff_bound_batch`` is the batched device search, with certified bounds); ``diamond_norm_distance`` is the reference's cvxpy semidefinite program
 (distance_measures.py:378-437) and, like there, needs cvxpy to be installed.
 """
 from typing import Tuple
@@ -137,6 +137,44 @@ def quantum_chernoff_bound(rho: np.ndarray, sigma: np.ndarray, tol: float = 1000
 
     res = minimize_scalar(f, bounds=(0, 1), method="bounded")
     return np.real_if_close(res.fun, tol), np.real_if_close(res.x, tol)
+
+
+def quantum_chernoff_bound_batch(rho, sigma, tol: float = 1e-10, max_iters: int = 100, zero_tol: float = 1e-12,
+                                 return_bounds: bool = False):
+    """Quantum Chernoff bounds of B pairs of states on the device (fbx_chernoff_bound; 1..5 qubits): ``rho`` [B, d, d] (or one
+    [d, d]), ``sigma`` [B, d, d] or one shared [d, d].  The quantity of ``quantum_chernoff_bound`` (distance_measures.py:153-195),
+    min over s in [0, 1] of tr(rho^s sigma^(1-s)), with eigenvalues <= ``zero_tol`` * lambda_max of their matrix counted as zero
+    (``zero_tol = 0``: every positive eigenvalue kept, as the host function does).  Each pair is searched until
+    qcb - lower <= tol * max(qcb, 1e-12), or for ``max_iters`` evaluations; ``lower`` is a certified lower bound.
+
+    Returns (qcb[B], s[B]); with ``return_bounds`` also lower[B] and iters[B] (int32, negative where tol was not reached -- both
+    bounds still hold)."""
+    r = _lib.c128(rho)
+    s = _lib.c128(sigma)
+    if r.ndim == 2:
+        r = r[None]
+    if r.ndim != 3 or r.shape[-1] != r.shape[-2]:
+        raise ValueError("rho must be [B, d, d] or [d, d]")
+    B, d = r.shape[0], r.shape[-1]
+    if d < 2:
+        raise ValueError("states must be d x d with d = 2^n, n >= 1")
+    n = _nq(d)
+    if s.shape == (d, d):
+        shared = 1
+    elif s.shape == (B, d, d):
+        shared = 0
+    else:
+        raise ValueError("sigma must be [B, d, d] or [d, d] matching rho")
+    qcb, s_opt = np.empty(B), np.empty(B)
+    lower = np.empty(B) if return_bounds else None
+    iters = np.empty(B, dtype=np.int32) if return_bounds else None
+    if B:
+        _lib.check(_lib.lib().fbx_chernoff_bound(
+            n, B, _lib.dptr(r.view(np.float64)), _lib.dptr(s.view(np.float64)), shared, float(tol), int(max_iters),
+            float(zero_tol), _lib.dptr(qcb), _lib.dptr(lower), _lib.dptr(s_opt), _lib.iptr(iters)))
+    if return_bounds:
+        return qcb, s_opt, lower, iters
+    return qcb, s_opt
 
 
 def hilbert_schmidt_ip(A: np.ndarray, B: np.ndarray, tol: float = 1000):

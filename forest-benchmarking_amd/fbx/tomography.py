@@ -483,6 +483,59 @@ def process_diamond_distance_variance_batch(design: Design, expectations, total_
     return dist.mean(axis=0), dist.var(axis=0)
 
 
+def state_chernoff_variance_batch(design: Design, expectations, total_counts, target_state, n_resamples: int = 40,
+                                  seed: int = 0, estimator="mle", project_to_physical=True, tol=1e-10,
+                                  return_samples=False):
+    """Bootstrap error bars of the quantum Chernoff bound of B state tomographies against ``target_state`` ([d, d] or
+    [B, d, d]): the state analogue of ``process_diamond_distance_variance_batch``.  Every experiment is resampled
+    ``n_resamples`` times (Beta posterior, fbx_beta_resample), all ``n_resamples * B`` resampled experiments are estimated in one
+    launch (``estimator`` "mle": iterative MLE with the reference's defaults, "linv": linear inversion), optionally projected to
+    physical states (1..3 qubits), and their Chernoff bounds to the target found on the device (fbx_chernoff_bound with the
+    estimates as rho and the target as sigma, ``tol`` as in ``distance_measures.quantum_chernoff_bound_batch``); nothing leaves
+    HBM in between.  Returns (mean[B], var[B]) (and the [n_resamples, B] values with ``return_samples``)."""
+    if estimator not in ("mle", "linv"):
+        raise ValueError("estimator must be 'mle' or 'linv'")
+    e, c = _batch_arrays(design, expectations, total_counts)
+    B, m, n, d = e.shape[0], design.m, design.n_qubits, design.dim
+    R = int(n_resamples)
+    tgt = np.asarray(target_state, dtype=np.complex128)
+    if tgt.shape not in ((d, d), (B, d, d)):
+        raise ValueError("target_state must be [d, d] or [B, d, d]")
+    if R < 1 or B == 0:
+        raise ValueError("need n_resamples >= 1 and a non-empty batch")
+    if project_to_physical and n > 3:
+        raise ValueError("project_to_physical runs on the device for 1..3 qubits only")
+    lib, DB = _lib.lib(), _lib.DeviceBuffer
+    d_e, d_c = DB.from_array(e), DB.from_array(c)
+    d_er, d_cr = DB(R * B * m * 8), DB(R * B * m * 8)
+    _lib.check(lib.fbx_beta_resample_dev(B * m, R, d_e.ptr, d_c.ptr, 1.0, int(seed) & (2 ** 64 - 1), d_er.ptr, d_cr.ptr))
+    d_rho = DB(R * B * d * d * 16)
+    if estimator == "mle":
+        _lib.check(lib.fbx_mle_state_dev(design.handle, R * B, d_er.ptr, d_cr.ptr, .1, 0.0, 0.0, 1e-9, 10_000, d_rho.ptr,
+                                         None, None))
+    else:
+        _lib.check(lib.fbx_linv_state_dev(design.handle, R * B, d_er.ptr, d_rho.ptr))
+    bufs = [d_e, d_c, d_er, d_cr, d_rho]
+    if project_to_physical:
+        d_phys = DB(R * B * d * d * 16)
+        _lib.check(lib.fbx_proj_state_physical_dev(n, R * B, d_rho.ptr, d_phys.ptr))
+        bufs.append(d_phys)
+        d_rho = d_phys
+    shared = tgt.ndim == 2
+    d_tgt = DB.from_array(np.ascontiguousarray(tgt if shared else np.broadcast_to(tgt, (R, B, d, d))))
+    d_q = DB(R * B * 8)
+    bufs += [d_tgt, d_q]
+    _lib.check(lib.fbx_chernoff_bound_dev(n, R * B, d_rho.ptr, d_tgt.ptr, int(shared), float(tol), 100, 1e-12, d_q.ptr,
+                                          None, None, None))
+    _lib.synchronize()
+    q = d_q.to_array(np.float64, (R, B))
+    for buf in bufs:
+        buf.free()
+    if return_samples:
+        return q.mean(axis=0), q.var(axis=0), q
+    return q.mean(axis=0), q.var(axis=0)
+
+
 def estimate_by_qubit_groups(results, qubit_groups, kind="process", estimator="pgdb", **kwargs):
     """Tomography of several qubit groups measured in one (merged) experiment: split the results
     with ``get_results_by_qubit_groups`` (observable_estimation.py:1145-1173, the process notebook's

@@ -27,7 +27,8 @@
  *    itertools.product('IXYZ', repeat=n) with qubits[0] the left-most tensor factor.
  *  - sizes: the estimators, projections, state measures and channel application take 1..3 qubits
  *    (fbx_kraus_sweep is one fused kernel for 1..2 and a composition of the pairwise conversions for 3);
- *    fbx_convert and fbx_process_fidelity 1..5 qubits; fbx_diamond_norm 1..3 qubits; fbx_eigh / fbx_matmul any N <= 1024;
+ *    fbx_convert and fbx_process_fidelity 1..5 qubits; fbx_diamond_norm 1..3 qubits; fbx_chernoff_bound 1..5 qubits;
+ *    fbx_eigh / fbx_matmul any N <= 1024;
  *    fbx_convert_general and fbx_partial_trace any dimension (each entry point states its own range).
  *  - label codes: one-qubit input states 0:X+ 1:X- 2:Y+ 3:Y- 4:Z+ 5:Z- 6:SIC0 7:SIC1
  *    8:SIC2 9:SIC3; one-qubit Paulis 0:I 1:X 2:Y 3:Z.
@@ -373,6 +374,27 @@ int fbx_diamond_norm(int n_qubits, int64_t B, const double* choi0, const double*
                      int max_iters, double* dist_out, double* upper_out, double* rho_out, int32_t* iters_out);
 int fbx_diamond_norm_dev(int n_qubits, int64_t B, const double* d_choi0, const double* d_choi1, int choi1_shared, double tol,
                          int max_iters, double* d_dist_out, double* d_upper_out, double* d_rho_out, int32_t* d_iters_out);
+
+/* Quantum Chernoff bound of B pairs of states (distance_measures.py:153-195): qcb = min over s in [0, 1] of
+ * Q(s) = tr(rho^s sigma^(1-s)), rho [B][d][d] and sigma [B][d][d] or one shared [d][d] (sigma_shared != 0), d = 2^n_qubits,
+ * n_qubits 1..5 (others FBX_ERR_UNSUPPORTED).  The LOWER triangles are read (numpy's eigh).  An eigenvalue <= zero_tol * lambda_max
+ * of its own matrix (negative ones included; zero_tol in [0, 1), the Python default 1e-12) counts as exactly zero and its terms are
+ * left out at every s, the endpoints included (support projectors); zero_tol = 0 keeps every eigenvalue > 0, as
+ * quantum_chernoff_bound does.  Q is convex; per pair a safeguarded Newton search on Q' gives qcb_out[b] (the smallest evaluated
+ * Q, an upper bound up to rounding) and s_out[b] (where it was reached), and the tangents at the two ends of the final bracket give
+ * lower_out[b] <= the exact minimum.  The search stops once qcb - lower <= tol * max(qcb, 1e-12) (tol <= 0: 1e-10) or after
+ * max_iters evaluations besides the two endpoints.  iters_out[b] = those evaluations, negative when tol was not reached (both
+ * bounds still hold).  lower_out, s_out, iters_out may be NULL.  A non-finite item gives NaN (iters -1) in that item only.
+ * Rounding: lower is shifted down by a bound on the rounding of Q and Q' (fbx_chernoff.hip), so it is a lower bound of the exact
+ * minimum over the COMPUTED eigendecompositions; qcb may fall below that minimum by at most (8 L + 16 + d^2) 2^-52 relative,
+ * L = the largest |ln a_i| + |ln b_j| over the kept terms (below 2e-13 for unit-trace states at zero_tol = 1e-12).  The
+ * eigensolver's own backward error (~1e-15 relative to lambda_max) is outside both statements.  A shared sigma gives the same bits
+ * as the same sigma passed per item; results do not depend on the batch. */
+int fbx_chernoff_bound(int n_qubits, int64_t B, const double* rho, const double* sigma, int sigma_shared, double tol,
+                       int max_iters, double zero_tol, double* qcb_out, double* lower_out, double* s_out, int32_t* iters_out);
+int fbx_chernoff_bound_dev(int n_qubits, int64_t B, const double* d_rho, const double* d_sigma, int sigma_shared, double tol,
+                           int max_iters, double zero_tol, double* d_qcb_out, double* d_lower_out, double* d_s_out,
+                           int32_t* d_iters_out);
 
 /* State measures (distance_measures.py:14-114, :198): purity tr(rho^2), fidelity
  * (tr sqrt(sqrt(rho) sigma sqrt(rho)))^2, trace_distance = 0.5 * induced 1-norm,

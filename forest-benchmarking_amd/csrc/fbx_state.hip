@@ -1336,6 +1336,245 @@ static int launch_mle_big(const fbx_design* des, int64_t B, const double* e, con
     return FBX_OK;
 }
 
+// ---- 4 and 5 qubits after the reconstruction: physical projection and state measures.  One workgroup of (d/2)^2 threads per
+// item (one wavefront at 16 x 16, four at 32 x 32), thread t = (I, J) owns the 2 x 2 block of rows {2I, 2I+1} x columns
+// {2J, 2J+1} -- the thread grid of the Jacobi solver, the one fbx_eigh runs at these sizes, so no thread idles through the
+// eigensolves and the 16 x 16 solve needs no workgroup barrier.  Whole matrices stay in LDS buffers of PostBigLds<NQ>::MAT
+// entries, each of which holds a matrix row-major or in the solver's block layout; the buffers are reused as the comments say.
+template <int NQ>
+struct PostBigLds {
+    static constexpr int d = 1 << NQ, D = d * d, NB = d / 2, NT = NB * NB;
+    static constexpr int MAT = sys_elems<d>() > D ? sys_elems<d>() : D;
+    static constexpr int RED = 2 * (NT / 64) + 2;                      // block_sum2 scratch, then {shift, cut, physical}
+    static constexpr size_t bytes(int mats) { return sizeof(cplx) * MAT * (size_t)mats + sizeof(double) * (2 * d + RED + 2); }
+};
+template <int NT>
+__device__ __forceinline__ void post_sync() { if constexpr (NT > 64) __syncthreads(); else FBX_WAVE_SYNC(); }
+
+// block t of the Hermitian matrix in the lower triangle of row-major `src` (what scipy / numpy eigh read)
+template <int d>
+__device__ __forceinline__ Blk lower_blk(const cplx* src, int t) {
+    constexpr int NB = d / 2;
+    const int I = t / NB, J = t % NB;
+    Blk h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int r = 2 * I + (e >> 1), c = 2 * J + (e & 1);
+        const cplx v = r >= c ? src[r * d + c] : src[c * d + r];
+        h.re[e] = v.re;
+        h.im[e] = r > c ? v.im : r < c ? -v.im : 0.0;
+    }
+    return h;
+}
+// block t of A * Bm (row-major d x d)
+template <int d>
+__device__ __forceinline__ Blk matmul_blk(const cplx* A, const cplx* Bm, int t) {
+    constexpr int NB = d / 2;
+    const int I = t / NB, J = t % NB;
+    Blk o = blk_zero();
+#pragma unroll 8
+    for (int k = 0; k < d; ++k) {
+        const cplx a[2] = {A[(2 * I) * d + k], A[(2 * I + 1) * d + k]};
+        const cplx b[2] = {Bm[k * d + 2 * J], Bm[k * d + 2 * J + 1]};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            o.re[e] += a[e >> 1].re * b[e & 1].re - a[e >> 1].im * b[e & 1].im;
+            o.im[e] += a[e >> 1].re * b[e & 1].im + a[e >> 1].im * b[e & 1].re;
+        }
+    }
+    return o;
+}
+
+// purity / fidelity / trace distance / Hilbert-Schmidt inner product as state_measures_kernel has them; an output whose pointer
+// is NULL is skipped, and without the fidelity there is no eigensolve.  A non-finite pair gives NaN in every output asked for.
+template <int NQ>
+__global__ void __launch_bounds__(PostBigLds<NQ>::NT)
+state_measures_big_kernel(long long B, const double* __restrict__ rho_in, const double* __restrict__ sig_in,
+                          double* __restrict__ purity, double* __restrict__ fidelity, double* __restrict__ tdist,
+                          double* __restrict__ hsip) {
+    using P = PostBigLds<NQ>;
+    constexpr int d = P::d, D = P::D, NT = P::NT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    cplx* X = (cplx*)smem;                   // |rho - sigma|, then the solver's matrix, then sqrt_rho
+    cplx* Y = X + P::MAT;                    // rho, then the solver's eigenvectors, then sqrt_rho sigma
+    cplx* Z = Y + P::MAT;                    // sigma, then sqrt_rho sigma sqrt_rho
+    double* lam = (double*)(Z + P::MAT);
+    double* red = lam + 2 * d;
+    const int t = threadIdx.x;
+    const long long item = blockIdx.x;
+    const double* ra = rho_in + item * D * 2;
+    const double* sb = sig_in + item * D * 2;
+    double mag = 0.0, hs = 0.0;
+    double* ad = (double*)X;
+#pragma unroll
+    for (int k = 0; k < D / NT; ++k) {
+        const int idx = t + k * NT;
+        cplx a, b;
+        a.re = ra[2 * idx]; a.im = ra[2 * idx + 1]; b.re = sb[2 * idx]; b.im = sb[2 * idx + 1];
+        Y[idx] = a; Z[idx] = b;
+        mag += fabs(a.re) + fabs(a.im) + fabs(b.re) + fabs(b.im);
+        hs += a.re * b.re + a.im * b.im;                                // Re tr(A^H B)
+        const double dr = a.re - b.re, di = a.im - b.im;
+        ad[idx] = sqrt(dr * dr + di * di);
+    }
+    block_sum2<NT>(mag, hs, red);                                       // (its barriers publish Y, Z and ad as well)
+    post_sync<NT>();
+    if (!(mag <= DBL_MAX)) {
+        if (t == 0) {
+            if (purity) purity[item] = NAN;
+            if (fidelity) fidelity[item] = NAN;
+            if (tdist) tdist[item] = NAN;
+            if (hsip) hsip[item] = NAN;
+        }
+        return;
+    }
+    if (t == 0 && hsip) hsip[item] = hs;
+    if (purity) {                                                       // Re tr(rho rho)
+        double p = 0.0;
+#pragma unroll
+        for (int k = 0; k < D / NT; ++k) {
+            const int idx = t + k * NT;
+            const cplx a = Y[idx], at = Y[(idx % d) * d + idx / d];
+            p += a.re * at.re - a.im * at.im;
+        }
+        p = block_sum<NT>(p, red);
+        if (t == 0) purity[item] = p;
+    }
+    if (tdist) {                                                        // 0.5 * max_c sum_r |rho - sigma|[r][c]
+        double cs = 0.0;
+        if (t < d) for (int r = 0; r < d; ++r) cs += ad[r * d + t];
+        if (t < 64) cs = wave_max(cs);                                  // d <= 32: the columns sit in the first wavefront
+        if (t == 0) tdist[item] = 0.5 * cs;
+    }
+    if (!fidelity) return;
+    // (tr sqrtm_psd(sqrt_rho sigma sqrt_rho))^2, both roots through the clipped spectrum
+    Blk h = lower_blk<d>(Y, t);
+    post_sync<NT>();                                                    // ad and rho are read: X and Y are free
+    sys_store<d>(X, t, h);
+    post_sync<NT>();
+    jacobi_eigh_simple<d, NT>(X, Y, t, true, red);
+    post_sync<NT>();
+    if (t < d) { const double l = X[sys_index<d>(t, t)].re; lam[t] = sqrt(l > 0.0 ? l : 0.0); }
+    post_sync<NT>();
+    h = reconstruct_blk<d>(Y, lam, t);
+    blk_store<d, d>(X, t, h);                                           // sqrt_rho
+    post_sync<NT>();
+    h = matmul_blk<d>(X, Z, t);
+    blk_store<d, d>(Y, t, h);                                           // sqrt_rho sigma
+    post_sync<NT>();
+    h = matmul_blk<d>(Y, X, t);
+    blk_store<d, d>(Z, t, h);                                           // ... sqrt_rho
+    post_sync<NT>();
+    h = lower_blk<d>(Z, t);
+    sys_store<d>(X, t, h);
+    post_sync<NT>();
+    jacobi_eigh_simple<d, NT>(X, Y, t, true, red);
+    post_sync<NT>();
+    double s = 0.0;
+    if (t < d) { const double l = X[sys_index<d>(t, t)].re; s = sqrt(l > 0.0 ? l : 0.0); }
+    s = block_sum<NT>(s, red);
+    if (t == 0) fidelity[item] = s * s;
+}
+
+// project_state_matrix_to_physical, project_state_matrix.py:6-52, as proj_state_kernel: a state that is physical after the
+// division by its trace is written as divided, not rebuilt.  A non-finite item gives NaN in every entry.
+template <int NQ>
+__global__ void __launch_bounds__(PostBigLds<NQ>::NT)
+proj_state_big_kernel(long long B, const double* __restrict__ rho_in, double* __restrict__ out) {
+    using P = PostBigLds<NQ>;
+    constexpr int d = P::d, D = P::D, NB = P::NB, NT = P::NT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    cplx* X = (cplx*)smem;                   // the solver's matrix
+    cplx* Y = X + P::MAT;                    // rho / tr(rho), then the solver's eigenvectors
+    double* lam = (double*)(Y + P::MAT);
+    double* sorted = lam + d;
+    double* red = sorted + d;
+    const int t = threadIdx.x, I = t / NB, J = t % NB;
+    const long long item = blockIdx.x;
+    const double* ra = rho_in + item * D * 2;
+    double* oa = out + item * D * 2;
+    Blk q;
+    double mag = 0.0, tr_re = 0.0, tr_im = 0.0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int r = 2 * I + (e >> 1), c = 2 * J + (e & 1);
+        q.re[e] = ra[2 * (r * d + c)]; q.im[e] = ra[2 * (r * d + c) + 1];
+        mag += fabs(q.re[e]) + fabs(q.im[e]);
+        if (r == c) { tr_re += q.re[e]; tr_im += q.im[e]; }
+    }
+    block_sum2<NT>(tr_re, tr_im, red);
+    mag = block_sum<NT>(mag, red);
+    if (!(mag <= DBL_MAX)) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int r = 2 * I + (e >> 1), c = 2 * J + (e & 1);
+            oa[2 * (r * d + c)] = NAN; oa[2 * (r * d + c) + 1] = NAN;
+        }
+        return;
+    }
+    const double den = tr_re * tr_re + tr_im * tr_im;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const double vr = q.re[e], vi = q.im[e];
+        q.re[e] = (vr * tr_re + vi * tr_im) / den; q.im[e] = (vi * tr_re - vr * tr_im) / den;
+    }
+    post_sync<NT>();
+    blk_store<d, d>(Y, t, q);
+    post_sync<NT>();
+    const Blk h = lower_blk<d>(Y, t);
+    post_sync<NT>();
+    sys_store<d>(X, t, h);
+    post_sync<NT>();
+    jacobi_eigh_simple<d, NT>(X, Y, t, true, red);
+    post_sync<NT>();
+    double ev = 0.0;
+    if (t < d) { ev = X[sys_index<d>(t, t)].re; lam[t] = ev; }
+    post_sync<NT>();
+    int rank = 0;                                                       // place in descending order (stable)
+    if (t < d) {
+        for (int j = 0; j < d; ++j) rank += (lam[j] > ev) || (lam[j] == ev && j < t);
+        sorted[rank] = ev;
+    }
+    post_sync<NT>();
+    if (t == 0) {                                                       // project_state_matrix.py:37-48
+        int i = d; double acc = 0.0;
+        while (i > 0 && sorted[i - 1] + acc / (double)i < 0.0) { acc += sorted[i - 1]; --i; }
+        red[0] = acc; red[1] = (double)i; red[2] = sorted[d - 1] >= 0.0 ? 1.0 : 0.0;
+    }
+    post_sync<NT>();
+    const double acc = red[0];
+    const int cut = (int)red[1];
+    const bool physical = red[2] != 0.0;
+    post_sync<NT>();
+    if (t < d) lam[t] = rank < cut ? ev + acc / (double)cut : 0.0;
+    post_sync<NT>();
+    if (!physical) q = reconstruct_blk<d>(Y, lam, t);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int r = 2 * I + (e >> 1), c = 2 * J + (e & 1);
+        oa[2 * (r * d + c)] = q.re[e]; oa[2 * (r * d + c) + 1] = q.im[e];
+    }
+}
+
+template <int NQ>
+static int launch_measures_big(int64_t B, const double* rho, const double* sigma, double* purity, double* fidelity, double* tdist,
+                               double* hsip) {
+    const size_t lds = PostBigLds<NQ>::bytes(3);
+    FBX_HIP(hipFuncSetAttribute((const void*)state_measures_big_kernel<NQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(state_measures_big_kernel<NQ>, dim3((unsigned)B), dim3(PostBigLds<NQ>::NT), lds, stream(), (long long)B, rho,
+                       sigma, purity, fidelity, tdist, hsip);
+    FBX_HIP(hipGetLastError());
+    return FBX_OK;
+}
+template <int NQ>
+static int launch_proj_big(int64_t B, const double* rho, double* out) {
+    const size_t lds = PostBigLds<NQ>::bytes(2);
+    FBX_HIP(hipFuncSetAttribute((const void*)proj_state_big_kernel<NQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(proj_state_big_kernel<NQ>, dim3((unsigned)B), dim3(PostBigLds<NQ>::NT), lds, stream(), (long long)B, rho, out);
+    FBX_HIP(hipGetLastError());
+    return FBX_OK;
+}
+
 namespace {
 struct HostIO {
     std::vector<DevBuf*> bufs;
@@ -1758,17 +1997,19 @@ int fbx_choi2kraus(int n_qubits, int64_t B, const double* choi, double tol, doub
 }
 
 int fbx_proj_state_physical_dev(int n_qubits, int64_t B, const double* d_rho, double* d_out) {
-    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 3, "fbx_proj_state_physical: n_qubits must be 1..3");
+    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 5, "fbx_proj_state_physical: n_qubits must be 1..5");
     FBX_REQUIRE(B >= 0 && (B == 0 || (d_rho && d_out)), "fbx_proj_state_physical: bad batch / NULL buffer");
     FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
+    if (n_qubits == 4) return launch_proj_big<4>(B, d_rho, d_out);
+    if (n_qubits == 5) return launch_proj_big<5>(B, d_rho, d_out);
     FBX_DISPATCH_NQ(n_qubits, proj_state_kernel, state_lds(n_qubits, 1), B, (long long)B, d_rho, d_out);
     FBX_HIP(hipGetLastError());
     return FBX_OK;
 }
 
 int fbx_proj_state_physical(int n_qubits, int64_t B, const double* rho, double* out) {
-    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 3, "fbx_proj_state_physical: n_qubits must be 1..3");
+    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 5, "fbx_proj_state_physical: n_qubits must be 1..5");
     FBX_REQUIRE(B >= 0 && (B == 0 || (rho && out)), "fbx_proj_state_physical: bad batch / NULL buffer");
     FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
@@ -1782,10 +2023,12 @@ int fbx_proj_state_physical(int n_qubits, int64_t B, const double* rho, double* 
 
 int fbx_state_measures_dev(int n_qubits, int64_t B, const double* d_rho, const double* d_sigma, double* d_purity_out,
                            double* d_fidelity_out, double* d_trace_dist_out, double* d_hs_ip_out) {
-    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 3, "fbx_state_measures: n_qubits must be 1..3");
+    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 5, "fbx_state_measures: n_qubits must be 1..5");
     FBX_REQUIRE(B >= 0 && (B == 0 || (d_rho && d_sigma)), "fbx_state_measures: bad batch / NULL buffer");
     FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
+    if (n_qubits == 4) return launch_measures_big<4>(B, d_rho, d_sigma, d_purity_out, d_fidelity_out, d_trace_dist_out, d_hs_ip_out);
+    if (n_qubits == 5) return launch_measures_big<5>(B, d_rho, d_sigma, d_purity_out, d_fidelity_out, d_trace_dist_out, d_hs_ip_out);
     FBX_DISPATCH_NQ(n_qubits, state_measures_kernel, state_lds(n_qubits, 1), B, (long long)B, d_rho, d_sigma, d_purity_out,
                     d_fidelity_out, d_trace_dist_out, d_hs_ip_out);
     FBX_HIP(hipGetLastError());
@@ -1794,7 +2037,7 @@ int fbx_state_measures_dev(int n_qubits, int64_t B, const double* d_rho, const d
 
 int fbx_state_measures(int n_qubits, int64_t B, const double* rho, const double* sigma, double* purity_out,
                        double* fidelity_out, double* trace_dist_out, double* hs_ip_out) {
-    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 3, "fbx_state_measures: n_qubits must be 1..3");
+    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 5, "fbx_state_measures: n_qubits must be 1..5");
     FBX_REQUIRE(B >= 0 && (B == 0 || (rho && sigma)), "fbx_state_measures: bad batch / NULL buffer");
     FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;

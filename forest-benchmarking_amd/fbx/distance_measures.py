@@ -41,7 +41,7 @@ def state_measures_batch(rho, sigma=None, which=("purity", "fidelity", "trace_di
         rho = pad(rho)
         sig = rho if same else pad(sig)
         d = p
-    if d > 8:
+    if d > 32:
         return _state_measures_large(rho, sig, which)
     outs = {k: np.empty(B) for k in which}
     _lib.check(_lib.lib().fbx_state_measures(
@@ -52,10 +52,10 @@ def state_measures_batch(rho, sigma=None, which=("purity", "fidelity", "trace_di
 
 
 def _state_measures_large(rho, sig, which):
-    """Dimensions above 8 (4 and 5 qubits, up to 1024): the reference's formulas step by step on the generic device
-    primitives -- ``fbx_matmul`` for the products, ``fbx_eigh`` (HBM-resident above 64) for the matrix square roots
+    """Dimensions above 32 (up to 1024): the reference's formulas step by step on the generic device primitives --
+    ``fbx_matmul`` for the products, ``fbx_eigh`` (HBM-resident above 64) for the matrix square roots
     (distance_measures.py:14-36, 64-84, 100-114, 198-216).  The kernels of ``fbx_state_measures`` keep whole states
-    in LDS and stop at three qubits."""
+    in LDS and stop at five qubits."""
     from .operator_tools.calculational import sqrtm_psd_batch
     if rho.shape[-1] > 1024:
         raise _lib.FbxError(_lib.FBX_ERR_UNSUPPORTED, "state measures: dimensions above 1024 are outside this build")

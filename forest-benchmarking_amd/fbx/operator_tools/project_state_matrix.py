@@ -11,7 +11,7 @@ def project_state_matrix_to_physical_batch(rho) -> np.ndarray:
     if x.shape[-2] != d:
         raise ValueError("state matrices must be square")
     n = int(round(np.log2(d)))
-    if 2 ** n != d or d > 8:
+    if 2 ** n != d or d > 32:
         return _project_general(x)
     out = np.empty_like(x)
     _lib.check(_lib.lib().fbx_proj_state_physical(n, x.shape[0], _lib.dptr(x.view(np.float64)),
@@ -20,7 +20,7 @@ def project_state_matrix_to_physical_batch(rho) -> np.ndarray:
 
 
 def _project_general(x) -> np.ndarray:
-    """Any dimension up to 1024 (a qutrit, 4 and 5 qubits): the same algorithm on the generic device primitives --
+    """Any other dimension up to 1024 (a qutrit, 6 qubits): the same algorithm on the generic device primitives --
     ``fbx_eigh`` of rho / tr(rho), the redistribution of the negative eigenvalues over the d numbers of the spectrum
     (project_state_matrix.py:37-48; control flow, done here), ``fbx_matmul`` for V diag(lambda') V^H.  Already
     physical inputs come back rescaled but otherwise untouched, as in the reference (:32-33)."""

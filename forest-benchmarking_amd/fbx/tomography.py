@@ -490,7 +490,7 @@ def state_chernoff_variance_batch(design: Design, expectations, total_counts, ta
     [B, d, d]): the state analogue of ``process_diamond_distance_variance_batch``.  Every experiment is resampled
     ``n_resamples`` times (Beta posterior, fbx_beta_resample), all ``n_resamples * B`` resampled experiments are estimated in one
     launch (``estimator`` "mle": iterative MLE with the reference's defaults, "linv": linear inversion), optionally projected to
-    physical states (1..3 qubits), and their Chernoff bounds to the target found on the device (fbx_chernoff_bound with the
+    physical states, and their Chernoff bounds to the target found on the device (fbx_chernoff_bound with the
     estimates as rho and the target as sigma, ``tol`` as in ``distance_measures.quantum_chernoff_bound_batch``); nothing leaves
     HBM in between.  Returns (mean[B], var[B]) (and the [n_resamples, B] values with ``return_samples``)."""
     if estimator not in ("mle", "linv"):
@@ -503,8 +503,6 @@ def state_chernoff_variance_batch(design: Design, expectations, total_counts, ta
         raise ValueError("target_state must be [d, d] or [B, d, d]")
     if R < 1 or B == 0:
         raise ValueError("need n_resamples >= 1 and a non-empty batch")
-    if project_to_physical and n > 3:
-        raise ValueError("project_to_physical runs on the device for 1..3 qubits only")
     lib, DB = _lib.lib(), _lib.DeviceBuffer
     d_e, d_c = DB.from_array(e), DB.from_array(c)
     d_er, d_cr = DB(R * B * m * 8), DB(R * B * m * 8)
@@ -534,6 +532,78 @@ def state_chernoff_variance_batch(design: Design, expectations, total_counts, ta
     if return_samples:
         return q.mean(axis=0), q.var(axis=0), q
     return q.mean(axis=0), q.var(axis=0)
+
+
+_STATE_MEASURES = ("purity", "fidelity", "infidelity", "trace_distance", "hs_ip")
+
+
+def state_measure_variance_batch(design: Design, expectations, total_counts, target_state=None, measure="fidelity",
+                                 n_resamples: int = 40, seed: int = 0, estimator="mle", project_to_physical=True,
+                                 return_samples=False):
+    """Bootstrap error bars of a state measure of B state tomographies of 1..5 qubits: ``estimate_variance`` with the
+    resamples and the experiments as one batch that never leaves HBM.  Every experiment is resampled ``n_resamples`` times (Beta
+    posterior, fbx_beta_resample), all ``n_resamples * B`` resampled experiments are estimated in one launch (``estimator``
+    "mle": iterative MLE with the reference's defaults, "linv": linear inversion), optionally projected to physical states
+    (fbx_proj_state_physical) and measured (fbx_state_measures).  ``measure`` is "purity" (no target), "fidelity",
+    "infidelity", "trace_distance" or "hs_ip" against ``target_state`` ([d, d] or [B, d, d]), the target as rho and the
+    estimates as sigma like ``estimate_variance`` passes them.  Returns (mean[B], var[B]) (and the [n_resamples, B] values with
+    ``return_samples``)."""
+    if measure not in _STATE_MEASURES:
+        raise ValueError(f"measure must be one of {_STATE_MEASURES}")
+    if estimator not in ("mle", "linv"):
+        raise ValueError("estimator must be 'mle' or 'linv'")
+    d = design.dim
+    R = int(n_resamples)
+    if R < 1:
+        raise ValueError("need n_resamples >= 1")
+    tgt = None
+    if measure != "purity":
+        if target_state is None:
+            raise ValueError(f"measure '{measure}' needs a target state")
+        tgt = np.asarray(target_state, dtype=np.complex128)
+        if tgt.ndim not in (2, 3) or tgt.shape[-2:] != (d, d):
+            raise ValueError("target_state must be [d, d] or [B, d, d]")
+    e, c = _batch_arrays(design, expectations, total_counts)
+    B, m, n = e.shape[0], design.m, design.n_qubits
+    if B == 0:
+        raise ValueError("need a non-empty batch")
+    if tgt is not None and tgt.ndim == 3 and tgt.shape[0] != B:
+        raise ValueError("target_state must be [d, d] or [B, d, d]")
+    lib, DB = _lib.lib(), _lib.DeviceBuffer
+    d_e, d_c = DB.from_array(e), DB.from_array(c)
+    d_er, d_cr = DB(R * B * m * 8), DB(R * B * m * 8)
+    _lib.check(lib.fbx_beta_resample_dev(B * m, R, d_e.ptr, d_c.ptr, 1.0, int(seed) & (2 ** 64 - 1), d_er.ptr, d_cr.ptr))
+    d_est = DB(R * B * d * d * 16)
+    if estimator == "mle":
+        _lib.check(lib.fbx_mle_state_dev(design.handle, R * B, d_er.ptr, d_cr.ptr, .1, 0.0, 0.0, 1e-9, 10_000, d_est.ptr,
+                                         None, None))
+    else:
+        _lib.check(lib.fbx_linv_state_dev(design.handle, R * B, d_er.ptr, d_est.ptr))
+    bufs = [d_e, d_c, d_er, d_cr, d_est]
+    if project_to_physical:
+        d_phys = DB(R * B * d * d * 16)
+        _lib.check(lib.fbx_proj_state_physical_dev(n, R * B, d_est.ptr, d_phys.ptr))
+        bufs.append(d_phys)
+        d_est = d_phys
+    d_v = DB(R * B * 8)
+    bufs.append(d_v)
+    key = "fidelity" if measure == "infidelity" else measure
+    if tgt is None:
+        d_rho = d_est
+    else:
+        d_rho = DB.from_array(np.ascontiguousarray(np.broadcast_to(tgt, (R, B, d, d))))
+        bufs.append(d_rho)
+    outs = [d_v.ptr if k == key else None for k in ("purity", "fidelity", "trace_distance", "hs_ip")]
+    _lib.check(lib.fbx_state_measures_dev(n, R * B, d_rho.ptr, d_est.ptr, *outs))
+    _lib.synchronize()
+    v = d_v.to_array(np.float64, (R, B))
+    for buf in bufs:
+        buf.free()
+    if measure == "infidelity":
+        v = 1 - v
+    if return_samples:
+        return v.mean(axis=0), v.var(axis=0), v
+    return v.mean(axis=0), v.var(axis=0)
 
 
 def estimate_by_qubit_groups(results, qubit_groups, kind="process", estimator="pgdb", **kwargs):

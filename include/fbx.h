@@ -27,6 +27,7 @@
  *    itertools.product('IXYZ', repeat=n) with qubits[0] the left-most tensor factor.
  *  - sizes: the estimators, projections, state measures and channel application take 1..3 qubits
  *    (fbx_kraus_sweep is one fused kernel for 1..2 and a composition of the pairwise conversions for 3);
+ *    the state estimators on a state design, fbx_proj_state_physical and fbx_state_measures 1..5 qubits;
  *    fbx_convert and fbx_process_fidelity 1..5 qubits; fbx_diamond_norm 1..3 qubits; fbx_chernoff_bound 1..5 qubits;
  *    fbx_eigh / fbx_matmul any N <= 1024;
  *    fbx_convert_general and fbx_partial_trace any dimension (each entry point states its own range).
@@ -331,7 +332,10 @@ int fbx_proj_choi(int proj_kind, int n_qubits, int64_t B, const double* choi, do
 int fbx_proj_choi_dev(int proj_kind, int n_qubits, int64_t B, const double* d_choi, double* d_out,
                       int32_t* d_iters_out);
 
-/* project_state_matrix_to_physical (operator_tools/project_state_matrix.py:6-52). */
+/* project_state_matrix_to_physical (operator_tools/project_state_matrix.py:6-52): rho[B][d][d] -> out[B][d][d], d = 2^n_qubits,
+ * n_qubits 1..5 (others FBX_ERR_BAD_ARG).  The lower triangle of rho / tr(rho) is diagonalised; when no eigenvalue is negative
+ * the output is rho / tr(rho) as it stands, else the rebuilt matrix.  A non-finite item gives non-finite entries for that item
+ * only (NaN in every entry at 4 and 5 qubits).  The _dev form enqueues on the calling thread's stream and does not synchronise. */
 int fbx_proj_state_physical(int n_qubits, int64_t B, const double* rho, double* out);
 int fbx_proj_state_physical_dev(int n_qubits, int64_t B, const double* d_rho, double* d_out);
 
@@ -398,7 +402,10 @@ int fbx_chernoff_bound_dev(int n_qubits, int64_t B, const double* d_rho, const d
 
 /* State measures (distance_measures.py:14-114, :198): purity tr(rho^2), fidelity
  * (tr sqrt(sqrt(rho) sigma sqrt(rho)))^2, trace_distance = 0.5 * induced 1-norm,
- * hilbert_schmidt_ip Re tr(rho^H sigma); rho, sigma are [B][d][d]; out arrays [B], NULL to skip. */
+ * hilbert_schmidt_ip Re tr(rho^H sigma); rho, sigma are [B][d][d], d = 2^n_qubits, n_qubits 1..5 (others FBX_ERR_BAD_ARG);
+ * out arrays [B], NULL to skip (without the fidelity no eigendecomposition runs).  Both square roots of the fidelity go through
+ * the spectrum clipped at zero; rho enters it through its lower triangle.  At 4 and 5 qubits a non-finite pair gives NaN in every
+ * output asked for.  The _dev form enqueues on the calling thread's stream and does not synchronise. */
 int fbx_state_measures(int n_qubits, int64_t B, const double* rho, const double* sigma,
                        double* purity_out, double* fidelity_out, double* trace_dist_out,
                        double* hs_ip_out);

@@ -4,7 +4,7 @@ does two eigendecompositions per item.  Also the certified share and the p50 / p
 
     python scripts/chernoff_time.py [--tol 1e-10] [--host-pairs 200]
 
-2^16 random pairs at 1-3 qubits, 4096 at 4-5 qubits (fidelity: the fbx_matmul / fbx_eigh composition above 3 qubits); half
+2^16 random pairs at 1-3 qubits, 4096 at 4-5 qubits; half
 full-rank, a quarter low-rank, a quarter nearly commuting (tests/chernoff_cases.py).  One JSON line per size."""
 import argparse
 import json

@@ -136,6 +136,10 @@ PROTOTYPES = {
     "fbx_diamond_norm_dev": [C.c_int, _i64, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp, _vp],
     "fbx_chernoff_bound": [C.c_int, _i64, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_double, _dp, _dp, _dp, _ip],
     "fbx_chernoff_bound_dev": [C.c_int, _i64, _vp, _vp, C.c_int, C.c_double, C.c_int, C.c_double, _vp, _vp, _vp, _vp],
+    "fbx_qv_heavy_outputs": [C.c_int, _i64, C.c_int, _u8p, _dp, _dp, _dp, C.POINTER(C.c_uint64), _dp, _ip],
+    "fbx_qv_heavy_outputs_dev": [C.c_int, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "fbx_qv_count_heavy": [C.c_int, _i64, _i64, _u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
+    "fbx_qv_count_heavy_dev": [C.c_int, _i64, _i64, _vp, _vp, _vp],
 }
 
 

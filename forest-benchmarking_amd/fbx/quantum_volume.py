@@ -1,0 +1,285 @@
+"""Quantum volume (forest/benchmarking/quantum_volume.py) without the acquisition: model circuits, their ideal heavy outputs, the
+heavy-hitter counts of measured bitstrings and the statistics that turn the counts into a quantum volume.
+
+What runs where:
+  * ``collect_heavy_outputs[_batch]`` / ``ideal_heavy_output_probability_batch`` -- ``fbx_qv_heavy_outputs``: a state-vector
+    simulation of B circuits of one width in one launch, the state in LDS, widths 2..13 (wider: ``FbxError(FBX_ERR_UNSUPPORTED)``;
+    there is no host fallback);
+  * ``count_heavy_hitters_sampled[_batch]`` -- ``fbx_qv_count_heavy``: a streaming reduction of the ``qc.run`` bit arrays;
+  * ``generate_abstract_qv_circuit`` -- host numpy with the reference's draw order (a run seeded with ``np.random.seed`` reproduces
+    the reference's circuit); ``generate_abstract_qv_circuits_batch`` -- gates from the device generator;
+  * ``calculate_prob_est_and_err``, ``get_prob_sample_heavy_by_depth``, ``extract_quantum_volume_from_results`` -- host arithmetic.
+
+``measure_quantum_volume``, ``sample_rand_circuits_for_heavy_out`` and the program generator need a pyquil ``QuantumComputer`` and
+a compiler and are not mirrored.
+
+Conventions (quantum_volume.py:113-115): output index i has qubit 0 as its most significant bit; a gate on ``(q0, q1)`` has q0 as
+the more significant bit of its 4 x 4 matrix index.  ``pairing="reference"`` is the reference's rule: gate g of a layer acts on
+``(perm[g], perm[g + 1])`` -- consecutive gates of a layer overlap on one qubit, so their order matters and is kept.
+``pairing="disjoint"`` is the layout of the paper (arXiv:1811.12926), ``(perm[2 g], perm[2 g + 1])``; a deviation from the
+reference, offered because it is what the protocol describes.  For odd widths the last position is idle in both.
+"""
+from typing import Dict, Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from .operator_tools.random_operators import _stream_seed, haar_rand_unitary
+
+__all__ = ["generate_abstract_qv_circuit", "generate_abstract_qv_circuits_batch", "collect_heavy_outputs",
+           "collect_heavy_outputs_batch", "ideal_heavy_output_probability_batch", "count_heavy_hitters_sampled",
+           "count_heavy_hitters_sampled_batch", "calculate_prob_est_and_err", "get_prob_sample_heavy_by_depth",
+           "extract_quantum_volume_from_results", "layer_pairs", "pack_heavy_mask", "unpack_heavy_mask", "heavy_outputs_flat"]
+
+MIN_WIDTH, MAX_WIDTH = 2, 13
+
+
+# ------------------------------------------------------------------------------------------------ circuits
+def generate_abstract_qv_circuit(depth: int) -> Tuple[List[np.ndarray], np.ndarray]:
+    """quantum_volume.py:126-151: depth permutations of range(depth), then depth x depth // 2 Haar 4 x 4 gates, drawn from numpy's
+    global stream in the reference's order (all permutations first, then the gates layer by layer)."""
+    permutations = [np.random.permutation(range(depth)) for _ in range(depth)]
+    gates = np.asarray([[haar_rand_unitary(4) for _ in range(depth // 2)] for _ in range(depth)])
+    return permutations, gates
+
+
+def generate_abstract_qv_circuits_batch(depth: int, batch: int, seed: Optional[int] = None, first_item: int = 0):
+    """``batch`` model circuits of one depth: ``permutations [B, depth, depth]`` (int64, from ``np.random.default_rng`` keyed by
+    the stream seed and the circuit's global id ``first_item + b``) and ``gates [B, depth, depth // 2, 4, 4]`` from
+    ``fbx_random_operators`` (Haar unitaries; gate j of circuit b is device item ``(first_item + b) * depth * (depth // 2) + j``).
+    A circuit depends on (seed, its id) only, not on the batch.  Parity with the reference is distributional."""
+    depth, batch, first_item = int(depth), int(batch), int(first_item)
+    if depth < 2 or batch < 0 or first_item < 0:
+        raise ValueError("generate_abstract_qv_circuits_batch: need depth >= 2, batch >= 0 and first_item >= 0")
+    from . import _lib
+    key = _stream_seed(seed)
+    per = depth * (depth // 2)
+    perms = np.empty((batch, depth, depth), dtype=np.int64)
+    for b in range(batch):
+        rng = np.random.default_rng([key & 0xFFFFFFFF, key >> 32, first_item + b])
+        for layer in range(depth):
+            perms[b, layer] = rng.permutation(depth)
+    gates = np.empty((batch, depth, depth // 2, 4, 4), dtype=np.complex128)
+    if batch:
+        _lib.check(_lib.lib().fbx_random_operators(_lib.RAND_UNITARY, 4, 0, batch * per, key, first_item * per,
+                                                   _lib.dptr(gates.view(np.float64))))
+    return perms, gates
+
+
+def layer_pairs(permutations, pairing: str = "reference") -> np.ndarray:
+    """``[..., depth, width]`` permutations -> ``[..., depth, width // 2, 2]`` qubit pairs (uint8) of every gate, in the order of
+    application.  ``reference``: ``(perm[g], perm[g + 1])`` (quantum_volume.py:55, :113); ``disjoint``: ``(perm[2 g], perm[2 g + 1])``."""
+    perms = np.asarray(permutations)
+    if perms.ndim < 2 or not np.issubdtype(perms.dtype, np.integer):
+        raise ValueError("permutations must be an integer array [..., depth, width]")
+    width = perms.shape[-1]
+    g = np.arange(width // 2)
+    if pairing == "reference":
+        first, second = g, g + 1
+    elif pairing == "disjoint":
+        first, second = 2 * g, 2 * g + 1
+    else:
+        raise ValueError(f"pairing must be 'reference' or 'disjoint', not {pairing!r}")
+    if perms.size and (perms.min() < 0 or perms.max() >= width or np.any(np.sort(perms, axis=-1) != np.arange(width))):
+        raise ValueError("every row of permutations must be a permutation of range(width)")
+    return np.stack([perms[..., first], perms[..., second]], axis=-1).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ masks
+def _mask_words(n_qubits: int) -> int:
+    return max(1, (1 << n_qubits) // 64)
+
+
+def pack_heavy_mask(heavy) -> np.ndarray:
+    """boolean table ``[B, 2^n]`` -> ``[B, W]`` uint64, W = max(1, 2^n / 64): output i is bit i % 64 of word i // 64"""
+    heavy = np.asarray(heavy, dtype=bool)
+    if heavy.ndim != 2 or heavy.shape[1] < 4 or heavy.shape[1] & (heavy.shape[1] - 1):
+        raise ValueError("heavy must be a boolean table [B, 2^n] with n >= 2")
+    B, N = heavy.shape
+    padded = np.zeros((B, max(N, 64)), dtype=np.uint8)
+    padded[:, :N] = heavy
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view("<u8").astype(np.uint64).reshape(B, max(N, 64) // 64)
+
+
+def unpack_heavy_mask(mask, n_qubits: int) -> np.ndarray:
+    """the inverse of ``pack_heavy_mask``: ``[B, W]`` uint64 -> boolean ``[B, 2^n]``"""
+    mask = np.ascontiguousarray(mask, dtype=np.uint64)
+    if mask.ndim != 2 or mask.shape[1] != _mask_words(n_qubits):
+        raise ValueError(f"mask must be [B, {_mask_words(n_qubits)}] for {n_qubits} qubits")
+    bits = np.unpackbits(mask.astype("<u8").view(np.uint8).reshape(mask.shape[0], 8 * mask.shape[1]), axis=1, bitorder="little")
+    return bits[:, :1 << n_qubits].astype(bool)
+
+
+# ------------------------------------------------------------------------------------------------ heavy outputs
+def heavy_outputs_flat(n_qubits: int, pairs, gates, probabilities=True, median=True, mask=True, heavy_prob=True, heavy_count=True):
+    """``fbx_qv_heavy_outputs`` on flat gate lists: ``pairs [B, L, 2]`` (q0, q1) and ``gates [B, L, 4, 4]``, applied in order.
+    Returns a dict with the outputs asked for: ``probabilities [B, 2^n]``, ``median [B]``, ``mask [B, W]`` (uint64), ``heavy_prob [B]``,
+    ``heavy_count [B]`` (int32)."""
+    n = int(n_qubits)
+    pairs = np.asarray(pairs)
+    gates = np.asarray(gates)
+    if pairs.ndim != 3 or pairs.shape[2] != 2:
+        raise ValueError("pairs must be [B, L, 2]")
+    B, L = pairs.shape[:2]
+    if gates.shape != (B, L, 4, 4):
+        raise ValueError(f"gates must be [B, L, 4, 4] = {(B, L, 4, 4)}, not {gates.shape}")
+    if not (probabilities or median or mask or heavy_prob or heavy_count):
+        raise ValueError("no output asked for")
+    if pairs.size and (pairs.min() < 0 or pairs.max() > 255):
+        raise ValueError("qubit indices must be 0..255")
+    pairs = np.ascontiguousarray(pairs, dtype=np.uint8)
+    if n >= 1 and pairs.size:
+        if pairs.max() >= n:
+            raise ValueError(f"a qubit index is out of range for {n} qubits")
+        if np.any(pairs[..., 0] == pairs[..., 1]):
+            raise ValueError("a gate needs two different qubits")
+    from . import _lib
+    import ctypes as C
+    gates = _lib.c128(gates)
+    N, W = 1 << max(n, 0), _mask_words(max(n, 0))
+    ok = MIN_WIDTH <= n <= MAX_WIDTH                     # (outside, the library refuses before it touches a buffer)
+    out = {}
+    if probabilities:
+        out["probabilities"] = np.empty((B, N if ok else 0))
+    if median:
+        out["median"] = np.empty(B)
+    if mask:
+        out["mask"] = np.zeros((B, W if ok else 0), dtype=np.uint64)
+    if heavy_prob:
+        out["heavy_prob"] = np.empty(B)
+    if heavy_count:
+        out["heavy_count"] = np.empty(B, dtype=np.int32)
+    _lib.check(_lib.lib().fbx_qv_heavy_outputs(
+        n, B, L, pairs.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(gates.view(np.float64)),
+        _lib.dptr(out.get("probabilities")), _lib.dptr(out.get("median")),
+        out["mask"].ctypes.data_as(C.POINTER(C.c_uint64)) if mask else None,
+        _lib.dptr(out.get("heavy_prob")), _lib.iptr(out.get("heavy_count"))))
+    return out
+
+
+def _flatten_circuits(permutations, gates, pairing):
+    perms = np.asarray(permutations)
+    gates = np.asarray(gates)
+    if perms.ndim != 3:
+        raise ValueError("permutations must be [B, depth, width]")
+    B, depth, width = perms.shape
+    if gates.shape != (B, depth, width // 2, 4, 4):
+        raise ValueError(f"gates must be [B, depth, width // 2, 4, 4] = {(B, depth, width // 2, 4, 4)}, not {gates.shape}")
+    pairs = layer_pairs(perms, pairing)
+    return width, pairs.reshape(B, depth * (width // 2), 2), gates.reshape(B, depth * (width // 2), 4, 4)
+
+
+def collect_heavy_outputs_batch(permutations, gates, pairing: str = "reference", return_probabilities: bool = False,
+                                return_stats: bool = False):
+    """The heavy outputs of B model circuits of one width in one launch: ``permutations [B, depth, width]``,
+    ``gates [B, depth, width // 2, 4, 4]`` -> the boolean heavy table ``[B, 2^width]``; with ``return_probabilities`` also the ideal
+    output distribution ``[B, 2^width]``; with ``return_stats`` also a dict of ``median``, ``heavy_prob`` and ``heavy_count`` ([B] each)."""
+    width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
+    r = heavy_outputs_flat(width, pairs, flat, probabilities=return_probabilities, median=return_stats, mask=True,
+                           heavy_prob=return_stats, heavy_count=return_stats)
+    res = [unpack_heavy_mask(r["mask"], width)]
+    if return_probabilities:
+        res.append(r["probabilities"])
+    if return_stats:
+        res.append({k: r[k] for k in ("median", "heavy_prob", "heavy_count")})
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def ideal_heavy_output_probability_batch(permutations, gates, pairing: str = "reference") -> np.ndarray:
+    """``[B]``: the probability that an ideal device outputs a heavy bitstring of each circuit (the number a measured heavy
+    fraction is compared with; (1 + ln 2) / 2 on average for wide random circuits)."""
+    width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
+    return heavy_outputs_flat(width, pairs, flat, probabilities=False, median=False, mask=False, heavy_prob=True,
+                              heavy_count=False)["heavy_prob"]
+
+
+def collect_heavy_outputs(wfn_sim, permutations, gates) -> List[int]:
+    """quantum_volume.py:94-123 with the reference's signature; ``wfn_sim`` is accepted and ignored (may be ``None``): the
+    simulation runs on the device.  Returns the sorted list of heavy outputs as ints."""
+    perms = np.asarray([np.asarray(p) for p in permutations])
+    heavy = collect_heavy_outputs_batch(perms[None], np.asarray(gates)[None])
+    return [int(i) for i in np.flatnonzero(heavy[0])]
+
+
+# ------------------------------------------------------------------------------------------------ counts
+def count_heavy_hitters_sampled_batch(bitarrays, heavy) -> np.ndarray:
+    """``bitarrays [B, shots, n]`` (0/1, first column = qubit 0, as ``qc.run`` returns them) and ``heavy`` -- the boolean table
+    ``[B, 2^n]`` or the packed masks ``[B, W]`` (uint64) -- -> the number of heavy shots of every circuit, ``[B]`` int64."""
+    bits = np.asarray(bitarrays)
+    if bits.ndim != 3:
+        raise ValueError("bitarrays must be [B, shots, n_qubits]")
+    B, shots, n = bits.shape
+    heavy = np.asarray(heavy)
+    if heavy.dtype == np.uint64:
+        mask = np.ascontiguousarray(heavy)
+        if mask.shape != (B, _mask_words(n)):
+            raise ValueError(f"masks must be [B, W] = {(B, _mask_words(n))}, not {mask.shape}")
+    else:
+        if heavy.shape != (B, 1 << n):
+            raise ValueError(f"heavy must be a boolean table [B, 2^n] = {(B, 1 << n)}, not {heavy.shape}")
+        mask = pack_heavy_mask(heavy)
+    if bits.size and (bits.min() < 0 or bits.max() > 1):
+        raise ValueError("bitarrays must hold 0 / 1")
+    bits = np.ascontiguousarray(bits, dtype=np.uint8)
+    from . import _lib
+    import ctypes as C
+    counts = np.zeros(B, dtype=np.int64)
+    _lib.check(_lib.lib().fbx_qv_count_heavy(n, B, shots, bits.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                             mask.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                             counts.ctypes.data_as(C.POINTER(C.c_int64))))
+    return counts
+
+
+def count_heavy_hitters_sampled(qc_results: Iterator[np.ndarray], heavy_hitters: Iterator[List[int]]) -> Iterator[int]:
+    """quantum_volume.py:322-341 with the reference's signature: per circuit the measured bit array and the list of heavy outputs;
+    yields the number of heavy shots of each.  Circuits of one (width, shot count) go to the device as one batch."""
+    results = [np.asarray(r) for r in qc_results]
+    lists = [list(h) for h in heavy_hitters]
+    m = min(len(results), len(lists))                        # zip semantics
+    results, lists = results[:m], lists[:m]
+    counts = [0] * m
+    by_shape: Dict[Tuple[int, int], List[int]] = {}
+    for i, r in enumerate(results):
+        if r.ndim != 2:
+            raise ValueError("every result must be a [shots, n_qubits] bit array")
+        by_shape.setdefault(r.shape, []).append(i)
+    for (shots, n), idx in by_shape.items():
+        table = np.zeros((len(idx), 1 << n), dtype=bool)
+        for row, i in enumerate(idx):
+            table[row, np.asarray(lists[i], dtype=np.int64)] = True
+        got = count_heavy_hitters_sampled_batch(np.stack([results[i] for i in idx]), table)
+        for row, i in enumerate(idx):
+            counts[i] = int(got[row])
+    yield from counts
+
+
+# ------------------------------------------------------------------------------------------------ statistics (host)
+def calculate_prob_est_and_err(num_heavy: int, num_circuits: int, num_shots: int) -> Tuple[float, float]:
+    """quantum_volume.py:211-231: the heavy-output frequency over all circuits of a depth and its 2-sigma one-sided lower bound
+    (Eq. (C3) of arXiv:1811.12926: worst-case binomial in the number of circuits, Gaussian approximation)."""
+    total = num_circuits * num_shots
+    prob = num_heavy / total
+    lower = prob - 2 * np.sqrt(num_heavy * (num_shots - num_heavy / num_circuits)) / total
+    return prob, lower
+
+
+def get_prob_sample_heavy_by_depth(depths: Iterator[int], num_hh_sampled: Iterator[int],
+                                   num_shots: Iterator[int]) -> Dict[int, Tuple[float, float]]:
+    """quantum_volume.py:344-376: per-circuit (depth, heavy count, shots) -> {depth: (estimate, lower bound)}"""
+    grouped: Dict[int, Tuple[List[int], int]] = {}
+    for depth, heavy, shots in zip(depths, num_hh_sampled, num_shots):
+        if depth in grouped:
+            assert shots == grouped[depth][1], 'The number of shots should be the same for each circuit of a given depth.'
+            grouped[depth][0].append(heavy)
+        else:
+            grouped[depth] = ([heavy], shots)
+    return {depth: calculate_prob_est_and_err(sum(heavy), len(heavy), shots) for depth, (heavy, shots) in grouped.items()}
+
+
+def extract_quantum_volume_from_results(results: Dict[int, Tuple[float, float]]) -> int:
+    """quantum_volume.py:379-397: 2^(largest depth reached before the first depth whose lower bound is <= 2/3), Eq. 7"""
+    achieved = 1
+    for depth in sorted(results):
+        if results[depth][1] <= 2 / 3:
+            break
+        achieved = depth
+    return 2 ** achieved

@@ -123,3 +123,27 @@ def kraus_batch(n_qubits, n_kraus, batch, seed=0):
     w, v = np.linalg.eigh(s)
     s_inv_half = np.einsum('bij,bj,bkj->bik', v, 1 / np.sqrt(w), v.conj())
     return np.einsum('bkij,bjl->bkil', g, s_inv_half)
+
+
+def qv_shots(probabilities, shots, depolarizing=0.0, seed=3000):
+    """Measured bitstrings of quantum-volume circuits: ``probabilities [B, 2^n]`` (the ideal output distributions,
+    ``quantum_volume.collect_heavy_outputs_batch(..., return_probabilities=True)``) -> ``[B, shots, n]`` uint8 bit arrays as
+    ``qc.run`` returns them (first column = qubit 0 = the most significant bit of the output index), sampled from
+    ``(1 - depolarizing) p + depolarizing / 2^n``; circuit b draws from ``np.random.default_rng([seed, b])``."""
+    p = np.asarray(probabilities, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] < 2 or p.shape[1] & (p.shape[1] - 1):
+        raise ValueError("probabilities must be [B, 2^n]")
+    if not 0.0 <= depolarizing <= 1.0 or int(shots) < 0:
+        raise ValueError("need 0 <= depolarizing <= 1 and shots >= 0")
+    B, N = p.shape
+    n = N.bit_length() - 1
+    out = np.empty((B, int(shots), n), dtype=np.uint8)
+    shifts = np.arange(n - 1, -1, -1)
+    for b in range(B):
+        total = p[b].sum()
+        if not np.isfinite(total) or total <= 0.0 or p[b].min() < 0.0:
+            raise ValueError(f"probabilities[{b}] is not a distribution (sum {total}): a poisoned or empty item cannot be sampled")
+        q = (1.0 - depolarizing) * p[b] / total + depolarizing / N
+        idx = np.random.default_rng([int(seed), b]).choice(N, size=int(shots), p=q / q.sum())
+        out[b] = (idx[:, None] >> shifts) & 1
+    return out

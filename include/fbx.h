@@ -471,6 +471,35 @@ int fbx_beta_resample(int64_t n, int64_t R, const double* expect, const double* 
 int fbx_beta_resample_dev(int64_t n, int64_t R, const double* d_expect, const double* d_counts,
                           double prior_counts, uint64_t seed, double* d_out, double* d_counts_out);
 
+/* ---------------------------------------------------------------- quantum volume (quantum_volume.py)
+ * collect_heavy_outputs (quantum_volume.py:94-123) for B model circuits of one width: the ideal output distribution of each
+ * circuit from a state-vector simulation in LDS, its median and its heavy outputs.  A circuit is a flat list of L two-qubit gates:
+ * pairs [B][L][2] qubit indices (q0, q1), q0 != q1, both < n_qubits; gates [B][L][4][4] complex128, applied in order l = 0 .. L-1.
+ * The state starts as |0...0>; amplitude index i has qubit 0 as its MOST significant bit (:115), and of the 4 x 4 matrix index q0
+ * is the more significant bit: for every assignment of the other qubits the amplitudes at (bit of q0, bit of q1) = 00, 01, 10, 11
+ * are replaced by U times that 4-vector.  probs_out [B][2^n] = |amp|^2; median_out [B] = half the sum of the two middle order
+ * statistics (statistics.median, :118; exact order statistics, no tolerance); output i is heavy iff probs[i] > median, strictly
+ * (:121) -- ties are not heavy; heavy_mask_out [B][W], W = max(1, 2^n / 64), bit i % 64 of word i / 64; heavy_prob_out [B] = sum of
+ * the heavy probabilities; heavy_count_out [B] = number of heavy outputs.  Every output may be NULL, not all of them.
+ * n_qubits 2..13 (the state lives in the LDS of one CU; others FBX_ERR_UNSUPPORTED).  L = 0: probs (1, 0, ...), median 0, heavy {0}.
+ * The host-pointer form checks every pair (FBX_ERR_BAD_ARG); the _dev form cannot, and turns a circuit with a bad pair into a
+ * poisoned item.  A poisoned item (bad pair, non-finite gate entry) gets NaN probabilities, median and heavy probability and an
+ * empty heavy set; its neighbours are untouched.  Results do not depend on the batch.  The _dev form enqueues on the calling
+ * thread's stream and does not synchronise. */
+int fbx_qv_heavy_outputs(int n_qubits, int64_t B, int L, const uint8_t* pairs, const double* gates, double* probs_out,
+                         double* median_out, uint64_t* heavy_mask_out, double* heavy_prob_out, int32_t* heavy_count_out);
+int fbx_qv_heavy_outputs_dev(int n_qubits, int64_t B, int L, const uint8_t* d_pairs, const double* d_gates, double* d_probs_out,
+                             double* d_median_out, uint64_t* d_heavy_mask_out, double* d_heavy_prob_out,
+                             int32_t* d_heavy_count_out);
+
+/* count_heavy_hitters_sampled (quantum_volume.py:322-341) for B circuits: bits [B][n_shots][n_qubits] 0/1 bytes as qc.run returns
+ * them; every shot row becomes an integer by bit_array_to_int (utils.py:32-42: first column most significant) and is looked up in
+ * the circuit's heavy_mask [B][W] (fbx_qv_heavy_outputs); counts_out [B].  Only bit 0 of every byte is read.  n_qubits 2..13. */
+int fbx_qv_count_heavy(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* bits, const uint64_t* heavy_mask,
+                       int64_t* counts_out);
+int fbx_qv_count_heavy_dev(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* d_bits, const uint64_t* d_heavy_mask,
+                           int64_t* d_counts_out);
+
 /* ---------------------------------------------------------------- random operators
  * operator_tools/random_operators.py:21-157 for batches, generated on the device.  Item b (global id
  * first_item + b) owns a counter-based Philox4x32-10 stream keyed by `seed`, so an item's matrices

@@ -16,6 +16,12 @@ MODE_LS_REFERENCE = 0x100       # flag: the line search of tomography.py:575-585
 REP_KRAUS, REP_CHOI, REP_SUPEROP, REP_PAULI_LIOUVILLE, REP_CHI = range(5)
 PROJ_CP, PROJ_TP, PROJ_TNI, PROJ_PHYSICAL_TP, PROJ_PHYSICAL_TNI = range(5)
 RAND_GINIBRE, RAND_UNITARY, RAND_STATE_VECTOR, RAND_GINIBRE_STATE, RAND_BURES_STATE = range(5)
+FIT_BASE_DECAY, FIT_TIME_DECAY, FIT_DECAYING_COSINE, FIT_SHIFTED_COSINE = range(4)
+FIT_MAX_POINTS = 256
+FIT_CONVERGED_FTOL, FIT_CONVERGED_XTOL, FIT_MAX_ITERS, FIT_BAD_START = 1, 2, 3, 4
+FIT_SINGULAR_COVAR = 16
+FIT_GRAD_FLOOR = 4096 * 2.0 ** -52
+FIT_PREPARE_RB, FIT_PREPARE_UNITARITY = 0, 1
 
 
 class FbxError(RuntimeError):
@@ -140,6 +146,15 @@ PROTOTYPES = {
     "fbx_qv_heavy_outputs_dev": [C.c_int, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fbx_qv_count_heavy": [C.c_int, _i64, _i64, _u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
     "fbx_qv_count_heavy_dev": [C.c_int, _i64, _i64, _vp, _vp, _vp],
+    "fbx_curve_fit": [C.c_int, _i64, C.c_int, _dp, _i64, _dp, _dp, _dp, C.c_uint, C.c_double, C.c_double, C.c_int,
+                      _dp, _dp, _dp, _dp, _ip, _ip, _dp],
+    "fbx_curve_fit_dev": [C.c_int, _i64, C.c_int, _vp, _i64, _vp, _vp, _vp, C.c_uint, C.c_double, C.c_double, C.c_int,
+                          _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "fbx_rb_survival": [C.c_int, _i64, _dp, _dp, _i64, _dp, _dp],
+    "fbx_rb_survival_dev": [C.c_int, _i64, _vp, _vp, _i64, _vp, _vp],
+    "fbx_rb_purity": [C.c_int, _i64, _dp, _dp, C.c_int, _dp, _dp],
+    "fbx_rb_purity_dev": [C.c_int, _i64, _vp, _vp, C.c_int, _vp, _vp],
+    "fbx_fit_prepare_dev": [C.c_int, _i64, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp],
 }
 
 

@@ -147,3 +147,49 @@ def qv_shots(probabilities, shots, depolarizing=0.0, seed=3000):
         idx = np.random.default_rng([int(seed), b]).choice(N, size=int(shots), p=q / q.sum())
         out[b] = (idx[:, None] >> shifts) & 1
     return out
+
+
+def rb_data(n_qubits, depths, decay=0.97, shots=500, batch=1, seed=4000):
+    """Synthetic randomized-benchmarking statistics in the shapes ``randomized_benchmarking.fit_rb_results_batch`` takes:
+    ``(z_expectations, z_std_errs)``, both [batch, len(depths), 2^n - 1].  A sequence of depth m leaves the depolarised state
+    decay^m |0..0><0..0| + (1 - decay^m) I / 2^n; its ``shots`` outcomes are drawn from ``np.random.default_rng([seed, b])``
+    (multinomial), observable z (a non-zero bit mask, in increasing order) has the expectation of (-1)^popcount(outcome & z)
+    and the standard error sqrt((1 - e^2) / shots) -- all from ONE set of shots, hence covariant.  ``decay`` may be [batch]."""
+    depths = np.asarray(depths, dtype=np.float64)
+    dim = 1 << int(n_qubits)
+    decay = np.broadcast_to(np.asarray(decay, dtype=np.float64), (int(batch),))
+    outcomes = np.arange(dim)
+    masks = np.arange(1, dim)
+    parity = np.array([[bin(int(x & z)).count("1") & 1 for x in outcomes] for z in masks])
+    signs = 1.0 - 2.0 * parity                                                  # [dim - 1, dim]
+    e = np.empty((int(batch), len(depths), dim - 1))
+    for b in range(int(batch)):
+        rng = np.random.default_rng([int(seed), b])
+        f = decay[b] ** depths
+        probs = np.outer(1.0 - f, np.full(dim, 1.0 / dim))
+        probs[:, 0] += f
+        counts = np.stack([rng.multinomial(int(shots), p / p.sum()) for p in probs])
+        e[b] = counts @ signs.T / float(shots)
+    return e, np.sqrt(np.clip(1.0 - e * e, 0.0, None) / float(shots))
+
+
+def spectroscopy_data(kind, xs, shots=500, batch=1, seed=5000, **params):
+    """Synthetic single-qubit spectroscopy statistics for ``qubit_spectroscopy.fit_*_results_batch``: ``(expectations, std_errs)``,
+    both [batch, len(xs)].  ``kind``: 't1' (amplitude, decay_time, offset), 't2' (amplitude, decay_time, offset, baseline,
+    frequency), 'rabi' or 'cz_ramsey' (amplitude, offset, baseline, frequency) -- the model of analysis/fitting.py for the
+    probability p1 of measuring 1, with the parameters given by name (scalars or [batch]).  Every point is k ~ Binomial(shots, p1)
+    from ``np.random.default_rng([seed, b])``; the Pauli expectation is 1 - 2 k / shots (the fit front ends negate it) and the
+    standard error sqrt((1 - e^2) / shots), zero where k is 0 or ``shots``."""
+    from .analysis import fitting
+    models = {"t1": fitting.decay_time_param_decay, "t2": fitting.decaying_cosine, "rabi": fitting.shifted_cosine,
+              "cz_ramsey": fitting.shifted_cosine}
+    if kind not in models:
+        raise ValueError(f"kind must be one of {sorted(models)}")
+    xs = np.asarray(xs, dtype=np.float64)
+    cols = {k: np.broadcast_to(np.asarray(v, dtype=np.float64), (int(batch),)) for k, v in params.items()}
+    e = np.empty((int(batch), len(xs)))
+    for b in range(int(batch)):
+        rng = np.random.default_rng([int(seed), b])
+        p1 = np.clip(models[kind](xs, **{k: v[b] for k, v in cols.items()}), 0.0, 1.0)
+        e[b] = 1.0 - 2.0 * rng.binomial(int(shots), p1) / float(shots)
+    return e, np.sqrt(np.clip(1.0 - e * e, 0.0, None) / float(shots))

@@ -500,6 +500,85 @@ int fbx_qv_count_heavy(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* 
 int fbx_qv_count_heavy_dev(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* d_bits, const uint64_t* d_heavy_mask,
                            int64_t* d_counts_out);
 
+/* ---------------------------------------------------------------- curve fits (analysis/fitting.py, randomized_benchmarking.py,
+ * qubit_spectroscopy.py)
+ * fbx_curve_fit: B independent weighted non-linear least-squares fits, one per GPU lane, of the four models of
+ * analysis/fitting.py:16-149 (what lmfit's Model.fit does for fit_base_param_decay, fit_decay_time_param_decay,
+ * fit_decaying_cosine and fit_shifted_cosine, one data set at a time).  Parameter order is the reference's:
+ *   FBX_FIT_BASE_DECAY       baseline + amplitude * decay**x                            (amplitude, decay, baseline)
+ *   FBX_FIT_TIME_DECAY       amplitude * exp(-(x - offset) / decay_time)                (amplitude, decay_time, offset)
+ *   FBX_FIT_DECAYING_COSINE  amplitude * exp(-x / decay_time) * cos(2 pi frequency x + offset) + baseline
+ *                                                                       (amplitude, decay_time, offset, baseline, frequency)
+ *   FBX_FIT_SHIFTED_COSINE   amplitude * cos(frequency x + offset) + baseline            (amplitude, offset, baseline, frequency)
+ * x is [K] for the whole batch (x_stride = 0) or [B][K] (x_stride = K); y is [B][K]; weights is [B][K] or NULL; the residual is
+ * (model - y) * weight, as in lmfit.  guess is [B][P].  Bit j of `vary` set: parameter j is fitted; cleared: it keeps its guess,
+ * bit for bit.  K is 2..FBX_FIT_MAX_POINTS (more: FBX_ERR_UNSUPPORTED).
+ * Method: Levenberg-Marquardt with analytic Jacobians in fp64 on the normal equations, columns scaled by the largest column norm
+ * seen so far (MINPACK's diag); the damped P x P system is solved in registers.  A trial point at which the cost or a derivative
+ * is not finite is a rejected step.  MINPACK's tests (relative actual and predicted reduction of the cost <= ftol; scaled step <=
+ * xtol * scaled parameters) propose a stop; the item is declared converged once, in addition,
+ *   grad_norm <= sqrt((n_free + 1) * max(ftol, xtol) * chisqr) + FBX_FIT_GRAD_FLOOR * ||weights * y||_2
+ * holds at the new point (the first term follows from the ftol test when the step is a Gauss-Newton step; the second is the
+ * rounding floor of a residual) -- every item with a CONVERGED status satisfies this bound.  max_iters counts trial points.
+ * Outputs, each may be NULL: params[B][P]; covar[B][P][P] = inv(J^T J) * redchi at the returned point (lmfit's
+ * scale_covar=True; rows and columns of fixed parameters zero; NaN when FBX_FIT_SINGULAR_COVAR is reported); chisqr[B];
+ * redchi[B] = chisqr / max(1, K - n_free); iters[B]; grad_norm[B] = max over free j of |J_j^T r| / ||J_j|| at the returned point;
+ * status[B] = one of FBX_FIT_CONVERGED_FTOL / _XTOL / FBX_FIT_MAX_ITERS / FBX_FIT_BAD_START, with FBX_FIT_SINGULAR_COVAR
+ * OR-ed in when the unit-diagonal scaling of J^T J has a Cholesky pivot <= FBX_FIT_SINGULAR_PIVOT (some combination of the free
+ * parameters does not move the model -- all three parameters of FBX_FIT_TIME_DECAY free is such a case; FBX_FIT_SINGULAR_COVAR is
+ * only looked for when covar is asked for).  A non-finite x, y, weight or guess makes that item FBX_FIT_BAD_START with NaN results
+ * and touches no other item.  Results do not depend on B or on an item's position in the batch. */
+#define FBX_FIT_BASE_DECAY       0
+#define FBX_FIT_TIME_DECAY       1
+#define FBX_FIT_DECAYING_COSINE  2
+#define FBX_FIT_SHIFTED_COSINE   3
+#define FBX_FIT_MAX_POINTS       256
+#define FBX_FIT_CONVERGED_FTOL   1
+#define FBX_FIT_CONVERGED_XTOL   2
+#define FBX_FIT_MAX_ITERS        3
+#define FBX_FIT_BAD_START        4
+#define FBX_FIT_SINGULAR_COVAR   16      /* flag, OR-ed onto one of the four above */
+#define FBX_FIT_GRAD_FLOOR       9.094947017729282e-13   /* 4096 * 2^-52 */
+#define FBX_FIT_SINGULAR_PIVOT   1e-11
+int fbx_curve_fit(int model, int64_t B, int K, const double* x, int64_t x_stride, const double* y, const double* weights,
+                  const double* guess, unsigned vary, double ftol, double xtol, int max_iters, double* params_out,
+                  double* covar_out, double* chisqr_out, double* redchi_out, int32_t* iters_out, int32_t* status_out,
+                  double* grad_norm_out);
+int fbx_curve_fit_dev(int model, int64_t B, int K, const double* d_x, int64_t x_stride, const double* d_y, const double* d_weights,
+                      const double* d_guess, unsigned vary, double ftol, double xtol, int max_iters, double* d_params_out,
+                      double* d_covar_out, double* d_chisqr_out, double* d_redchi_out, int32_t* d_iters_out, int32_t* d_status_out,
+                      double* d_grad_norm_out);
+
+/* z_obs_stats_to_survival_statistics with covariances_of_all_iz_obs (randomized_benchmarking.py:308-383) for S sequences:
+ * expectations / std_errs [S][dim - 1] of the non-trivial I/Z observables, dim a power of two in 2..32.  survival[S] =
+ * (sum + 1) / dim; variance[S] = sum of squared standard errors / dim^2, plus, for dim > 2 and num_shots > 0, the summed pairwise
+ * covariance (2 sum_i e_i - sum_{i != j} e_i e_j) / num_shots / dim^2.  num_shots = 0 is the reference's
+ * obs_are_independent=True; for dim = 2 the term does not exist. */
+int fbx_rb_survival(int dim, int64_t S, const double* expectations, const double* std_errs, int64_t num_shots,
+                    double* survival_out, double* variance_out);
+int fbx_rb_survival_dev(int dim, int64_t S, const double* d_expectations, const double* d_std_errs, int64_t num_shots,
+                        double* d_survival_out, double* d_variance_out);
+
+/* estimate_purity and estimate_purity_err (randomized_benchmarking.py:490-533) for S sequences: expectations / std_errs
+ * [S][dim^2 - 1] of the non-identity Paulis (the identity term, expectation 1 and variance 0, is appended inside), dim a power
+ * of two in 2..8.  purity[S] = sum e^2 / dim, shifted to (dim / (dim - 1)) (purity - 1 / dim) when renorm != 0; purity_err[S]
+ * propagates v_i = (2 |e_i|)^2 var_i, replaced by var_i^2 where numpy.isclose(0, v_i, atol=1e-6) holds, as the reference does. */
+int fbx_rb_purity(int dim, int64_t S, const double* expectations, const double* std_errs, int renorm, double* purity_out,
+                  double* purity_err_out);
+int fbx_rb_purity_dev(int dim, int64_t S, const double* d_expectations, const double* d_std_errs, int renorm,
+                      double* d_purity_out, double* d_purity_err_out);
+
+/* What fit_rb_results (:423-436) and fit_unitarity_results (:577-589) do between their statistics and the fit, for B items of
+ * K values on the device: weights[B][K] = 1 / error with every error that is not above zero (zero, or the NaN of a negative variance)
+ * replaced by the item's smallest one that is (error = sqrt(d_errors) when errors_are_variances != 0); an item without one gets unit weights and has_weights[b] = 0
+ * (the reference passes weights=None, the same fit).  guess[B][3] = (y[0] - y[K-1], 0.95, y[K-1]) for FBX_FIT_PREPARE_RB and
+ * (y[0], 0.95, 0) for FBX_FIT_PREPARE_UNITARITY.  d_errors may be NULL when neither weights nor has_weights is asked for.  With
+ * it fbx_rb_survival_dev -> fbx_fit_prepare_dev -> fbx_curve_fit_dev never leaves the device. */
+#define FBX_FIT_PREPARE_RB         0
+#define FBX_FIT_PREPARE_UNITARITY  1
+int fbx_fit_prepare_dev(int kind, int64_t B, int K, const double* d_values, const double* d_errors, int errors_are_variances,
+                        double* d_weights_out, double* d_guess_out, int32_t* d_has_weights_out);
+
 /* ---------------------------------------------------------------- random operators
  * operator_tools/random_operators.py:21-157 for batches, generated on the device.  Item b (global id
  * first_item + b) owns a counter-based Philox4x32-10 stream keyed by `seed`, so an item's matrices

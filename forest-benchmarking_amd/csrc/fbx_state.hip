@@ -13,6 +13,8 @@
 #include "fbx_eigh64.hpp"
 #include <hip/hip_cooperative_groups.h>
 #include <cfloat>
+#include <cmath>
+#include <limits>
 #include <type_traits>
 #include <cstdlib>
 #include <algorithm>
@@ -759,6 +761,7 @@ eigh_kernel(long long B, const double* __restrict__ a, double* __restrict__ w_ou
     const long long item = blockIdx.x;
     const double* src = a + item * (long long)N * N * 2;
     Blk h = blk_zero();
+    int nonfinite = 0;                  // over the entries read: the diagonal's real parts and the strictly lower triangle
     if (lane < NB * NB) {
         const int I = lane / NB, J = lane % NB;
 #pragma unroll
@@ -767,11 +770,22 @@ eigh_kernel(long long B, const double* __restrict__ a, double* __restrict__ w_ou
             if (r > c) { h.re[e] = src[2 * (r * N + c)]; h.im[e] = src[2 * (r * N + c) + 1]; }
             else if (r < c) { h.re[e] = src[2 * (c * N + r)]; h.im[e] = -src[2 * (c * N + r) + 1]; }
             else { h.re[e] = src[2 * (r * N + c)]; h.im[e] = 0.0; }
+            nonfinite |= !(isfinite(h.re[e]) && isfinite(h.im[e]));
         }
     }
+    // A non-finite item gives NaN for itself only (include/fbx.h): the solver's stopping test is false on a NaN and would
+    // hand back the sorted diagonal with the identity.  The item is solved as the zero matrix and NaN is written in its place.
+    nonfinite = __syncthreads_or(nonfinite);
+    if (nonfinite) h = blk_zero();
     sys_store<N>(Ms, lane, h);
     __syncthreads();
     jacobi_eigh_block<N, NT>(Ms, Vs, lane, true, red);
+    if (nonfinite) {
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+        if (lane < N) w_out[item * N + lane] = nan;
+        if (v_out) for (int idx = lane; idx < 2 * N * N; idx += NT) v_out[item * N * N * 2 + idx] = nan;
+        return;
+    }
     if (lane < N) lam[lane] = Ms[sys_index<N>(lane, lane)].re;
     __syncthreads();
     if (lane < N) {                     // rank of eigenvalue `lane` in ascending order (stable)
@@ -824,16 +838,23 @@ eigh_big_kernel(int N, long long B, const double* __restrict__ a, double* __rest
     cplx* M0 = work + (size_t)item * 4 * NN;
     cplx* M1 = M0 + NN; cplx* V0 = M1 + NN; cplx* V1 = V0 + NN;
     const double* src = a + item * (long long)NN * 2;
+    int nonfinite = 0;
     for (size_t idx = t; idx < NN; idx += NT) {            // numpy eigh: the lower triangle defines the matrix
         const int r = (int)(idx / N), c = (int)(idx % N);
         cplx h, v;
         if (r > c) { h.re = src[2 * idx]; h.im = src[2 * idx + 1]; }
         else if (r < c) { h.re = src[2 * ((size_t)c * N + r)]; h.im = -src[2 * ((size_t)c * N + r) + 1]; }
         else { h.re = src[2 * idx]; h.im = 0.0; }
+        nonfinite |= !(isfinite(h.re) && isfinite(h.im));
         v.re = r == c ? 1.0 : 0.0; v.im = 0.0;
         M0[idx] = h; V0[idx] = v;
     }
-    __syncthreads();
+    if (__syncthreads_or(nonfinite)) {                     // a non-finite item gives NaN for itself only (include/fbx.h)
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+        for (int k = t; k < N; k += NT) w_out[item * N + k] = nan;
+        if (v_out) for (size_t idx = t; idx < 2 * NN; idx += NT) v_out[(size_t)item * NN * 2 + idx] = nan;
+        return;
+    }
     cplx *Mc = M0, *Mn = M1, *Vc = V0, *Vn = V1;
     for (int sweep = 0; sweep < FBX_JACOBI_MAX_SWEEPS; ++sweep) {
         double o2 = 0.0, n2 = 0.0;
@@ -909,16 +930,30 @@ eigh_coop_kernel(int N, const double* __restrict__ a, double* __restrict__ w_out
     const int t = threadIdx.x, NB = N / 2, G = gridDim.x, g = blockIdx.x;
     const size_t NN = (size_t)N * N;
     cplx* M0 = work; cplx* M1 = M0 + NN; cplx* V0 = M1 + NN; cplx* V1 = V0 + NN;
+    int nonfinite = 0;
     for (size_t idx = (size_t)g * NT + t; idx < NN; idx += (size_t)G * NT) {
         const int r = (int)(idx / N), c = (int)(idx % N);
         cplx h, v;
         if (r > c) { h.re = a[2 * idx]; h.im = a[2 * idx + 1]; }
         else if (r < c) { h.re = a[2 * ((size_t)c * N + r)]; h.im = -a[2 * ((size_t)c * N + r) + 1]; }
         else { h.re = a[2 * idx]; h.im = 0.0; }
+        nonfinite |= !(isfinite(h.re) && isfinite(h.im));
         v.re = r == c ? 1.0 : 0.0; v.im = 0.0;
         M0[idx] = h; V0[idx] = v;
     }
+    // a non-finite matrix gives NaN (include/fbx.h): every workgroup publishes what it saw in the slots of `partial` that
+    // are next written by the ranks at the end (G <= N), and all of them leave together
+    nonfinite = __syncthreads_or(nonfinite);
+    if (t == 0) partial[2 * G + g] = nonfinite ? 1.0 : 0.0;
     grid.sync();
+    nonfinite = 0;
+    for (int k = 0; k < G; ++k) nonfinite |= partial[2 * G + k] != 0.0;
+    if (nonfinite) {
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+        for (size_t idx = (size_t)g * NT + t; idx < (size_t)N; idx += (size_t)G * NT) w_out[idx] = nan;
+        if (v_out) for (size_t idx = (size_t)g * NT + t; idx < 2 * NN; idx += (size_t)G * NT) v_out[idx] = nan;
+        return;
+    }
     cplx *Mc = M0, *Mn = M1, *Vc = V0, *Vn = V1;
     for (int sweep = 0; sweep < FBX_JACOBI_MAX_SWEEPS; ++sweep) {
         double o2 = 0.0, n2 = 0.0;
@@ -1881,7 +1916,16 @@ int fbx_eigh(int N, int64_t B, const double* a, double* w_out, double* v_out) {
         FBX_TRY(io.back(wp.data(), dw, wp.size())); FBX_TRY(io.back(vp.data(), dv, vp.size()));
         FBX_TRY(io.sync());
     }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
     for (int64_t b = 0; b < B; ++b) {
+        // a non-finite item came back all NaN (no column can be told from padding): NaN for that item, as for direct sizes
+        bool nonfinite = false;
+        for (int k = 0; k < Np && !nonfinite; ++k) nonfinite = std::isnan(wp[b * Np + k]);
+        if (nonfinite) {
+            for (int k = 0; k < N; ++k) w_out[b * N + k] = nan;
+            if (v_out) for (size_t k = 0; k < (size_t)N * N * 2; ++k) v_out[(size_t)b * N * N * 2 + k] = nan;
+            continue;
+        }
         int kept = 0;
         for (int k = 0; k < Np; ++k) {
             bool padding = false;

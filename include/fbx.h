@@ -632,7 +632,13 @@ int fbx_partial_trace_dev(int dim_a, int dim_b, int keep, int64_t B, const doubl
  * primitive under choi2kraus (superoperator_transformations.py:325-336), the PSD validators
  * (validate_operator.py:118-150), proj_choi_to_unitary (project_superoperators.py:147-175),
  * sqrtm_psd (calculational.py:77-91) and the spectral distance measures (distance_measures.py:153-195,440-460).
- * w_out[B][N]; v_out[B][N][N] holds the eigenvectors as columns (phases arbitrary), may be NULL. */
+ * w_out[B][N]; v_out[B][N][N] holds the eigenvectors as columns (phases arbitrary), may be NULL.
+ * Supported magnitudes: entries (and gaps that matter) between about 1e-150 and 1e+150 -- beyond that squares under- or
+ * overflow in the rotations and the stopping test (off-norm^2 <= 1e-26 norm^2), and smaller entries count as zero.
+ * Non-finite input: an item with a NaN or Inf on its diagonal (real part) or in its strictly lower triangle returns all-NaN
+ * w and all-NaN v; every other item of the batch is bit-identical to what it is beside a finite item, and the call returns
+ * FBX_OK.  This holds for both forms, at every N (padded sizes included) and from either large-N kernel.  The strictly
+ * upper triangle and the diagonal's imaginary parts are never read: NaN or Inf there changes nothing. */
 int fbx_eigh(int N, int64_t B, const double* a, double* w_out, double* v_out);
 int fbx_eigh_dev(int N, int64_t B, const double* d_a, double* d_w_out, double* d_v_out);
 

@@ -155,6 +155,12 @@ PROTOTYPES = {
     "fbx_rb_purity": [C.c_int, _i64, _dp, _dp, C.c_int, _dp, _dp],
     "fbx_rb_purity_dev": [C.c_int, _i64, _vp, _vp, C.c_int, _vp, _vp],
     "fbx_fit_prepare_dev": [C.c_int, _i64, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp],
+    "fbx_rpe_phase": [_i64, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _ip, _dp],
+    "fbx_rpe_phase_dev": [_i64, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
+    "fbx_rpe_from_shots": [C.c_int, _i64, C.c_int, _i64, _u8p, _u8p, C.c_int, C.c_int, C.c_int, _dp, _ip, _dp, _dp],
+    "fbx_rpe_from_shots_dev": [C.c_int, _i64, C.c_int, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
+    "fbx_circular_stats": [_i64, _i64, _dp, _dp, _dp, _ip],
+    "fbx_circular_stats_dev": [_i64, _i64, _vp, _vp, _vp, _vp],
 }
 
 

@@ -579,6 +579,55 @@ int fbx_rb_purity_dev(int dim, int64_t S, const double* d_expectations, const do
 int fbx_fit_prepare_dev(int kind, int64_t B, int K, const double* d_values, const double* d_errors, int errors_are_variances,
                         double* d_weights_out, double* d_guess_out, int32_t* d_has_weights_out);
 
+/* ---------------------------------------------------------------- robust phase estimation (robust_phase_estimation.py)
+ * fbx_rpe_phase: estimate_phase_from_moments (robust_phase_estimation.py:361-404) for B estimates of K depths, one estimate per GPU
+ * lane.  x, y, x_err, y_err are [B][K]: the expectations of X and Y after 2^j applications of the rotation, j = 0 .. K-1, and the
+ * standard errors of those means (their variances when errors_are_variances != 0, as in fbx_fit_prepare_dev: what
+ * fbx_shots_to_moments_dev writes goes in directly).  K is 1..62 (more: FBX_ERR_UNSUPPORTED; 2^j must stay an exact integer).
+ * xz, yz, xz_err, yz_err ([B][K], all four or none) are the expectations of the same observables times a Z on a partner qubit: with
+ * them the recursion runs on the post-selected combination of robust_phase_estimate (:496-504), x + xz for post_select = 0 and
+ * x - xz for post_select = 1, with the two errors added in quadrature.
+ * The recursion is the reference's, operation for operation in fp64 without fused multiply-adds (:377-404): at iteration j, k = 2^j,
+ * r = sqrt(x^2 + y^2), r_std = sqrt(x_err^2 + y_err^2); r < r_std (strictly) ends the item; otherwise theta_j = atan2(y, x) / k is
+ * moved into the window of width 2 pi / k around the running estimate with Python's float % (the result carries the divisor's
+ * sign); the result is the estimate % 2 pi.  Where the reference's own assert (:399) would fire -- the offset rounded up to the
+ * window's width -- the item keeps the computed value.
+ * Outputs, each may be NULL, not all: phase[B] in [0, 2 pi); depth_reached[B] = the number of iterations used (K when the item was
+ * never cut short; the reference's warning (:385) reports 2^depth_reached / 2); bloch[B][K][2] = (r, theta_est * k) per iteration,
+ * the reference's bloch_data, NaN beyond the cut.  A non-finite moment among the iterations an item uses makes that item's phase and
+ * all of its bloch rows NaN (depth_reached = the iteration at which it was met) and touches no other item.  Results do not depend
+ * on B or on an item's position in the batch.  The _dev forms enqueue on the calling thread's stream and do not synchronise. */
+int fbx_rpe_phase(int64_t B, int K, const double* x, const double* y, const double* x_err, const double* y_err,
+                  int errors_are_variances, const double* xz, const double* yz, const double* xz_err, const double* yz_err,
+                  int post_select, double* phase_out, int32_t* depth_reached_out, double* bloch_out);
+int fbx_rpe_phase_dev(int64_t B, int K, const double* d_x, const double* d_y, const double* d_x_err, const double* d_y_err,
+                      int errors_are_variances, const double* d_xz, const double* d_yz, const double* d_xz_err,
+                      const double* d_yz_err, int post_select, double* d_phase_out, int32_t* d_depth_reached_out,
+                      double* d_bloch_out);
+
+/* The same estimate straight from measured bits, one wavefront per estimate: x_bits and y_bits are [B][K][n_shots][n_qubits] 0/1
+ * bytes (the records of fbx_shots_to_moments; only bit 0 of a byte is read), col the column measured in X / Y, zcol a column
+ * measured in Z or -1 for none (with it post_select chooses x + xz or x - xz as above).  n_qubits 1..8, n_shots >= 1 and the same
+ * at every depth (depth-dependent shot counts: fbx_shots_to_moments_dev -> fbx_rpe_phase_dev).  Per record the shots with
+ * b[col] = 1 and the shots with b[col] ^ b[zcol] = 1 are counted (exact integers); mean = (n_plus - n_minus) / n_shots and the
+ * variance of the mean (1 - mean^2) / n_shots as fbx_shots_to_moments documents them (coefficient 1, no Beta prior), then the
+ * recursion of fbx_rpe_phase.  Outputs as there, plus moments_out[B][K][4] = (x, y, x_err, y_err) as the recursion consumed them
+ * (after post-selection, errors as standard errors).  Without moments_out the records of an item beyond its cut are not read. */
+int fbx_rpe_from_shots(int n_qubits, int64_t B, int K, int64_t n_shots, const uint8_t* x_bits, const uint8_t* y_bits, int col,
+                       int zcol, int post_select, double* phase_out, int32_t* depth_reached_out, double* bloch_out,
+                       double* moments_out);
+int fbx_rpe_from_shots_dev(int n_qubits, int64_t B, int K, int64_t n_shots, const uint8_t* d_x_bits, const uint8_t* d_y_bits,
+                           int col, int zcol, int post_select, double* d_phase_out, int32_t* d_depth_reached_out,
+                           double* d_bloch_out, double* d_moments_out);
+
+/* Circular statistics of angles[R][B] over R (the layout fbx_beta_resample_dev -> fbx_rpe_phase_dev leaves bootstrap phases in):
+ * mean[B] = atan2(mean sin, mean cos) mod 2 pi, std[B] = sqrt(-2 ln Rbar) with Rbar the length of the mean vector,
+ * nan_count[B] = the number of NaN entries, which are skipped (an item with nothing left gets NaN).  One item per thread, entries in
+ * order, compensated sums: repeated calls agree bit for bit.  Each output may be NULL, not all. */
+int fbx_circular_stats(int64_t R, int64_t B, const double* angles, double* mean_out, double* std_out, int32_t* nan_count_out);
+int fbx_circular_stats_dev(int64_t R, int64_t B, const double* d_angles, double* d_mean_out, double* d_std_out,
+                           int32_t* d_nan_count_out);
+
 /* ---------------------------------------------------------------- random operators
  * operator_tools/random_operators.py:21-157 for batches, generated on the device.  Item b (global id
  * first_item + b) owns a counter-based Philox4x32-10 stream keyed by `seed`, so an item's matrices

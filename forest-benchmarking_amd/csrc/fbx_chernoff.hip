@@ -301,8 +301,6 @@ int launch_small(int64_t B, const double* rho, const double* sigma, int shared, 
     return FBX_OK;
 }
 
-#define FBX_TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
-
 template <int NQ>
 int launch_big(int64_t B, const double* rho, const double* sigma, int shared, double tol, int max_iters, double zero_tol,
                double* qcb, double* lower, double* s, int32_t* iters) {
@@ -334,34 +332,6 @@ int launch_big(int64_t B, const double* rho, const double* sigma, int shared, do
     }
     return FBX_OK;
 }
-
-struct HostIO {     // host <-> device staging for the host-pointer entry point
-    std::vector<DevBuf*> bufs;
-    ~HostIO() { for (auto* b : bufs) delete b; }
-    template <class T> int in(const T* host, size_t count, T** dev) {
-        auto* b = new DevBuf(); bufs.push_back(b);
-        FBX_TRY(b->alloc(sizeof(T) * count));
-        hipError_t e = hipMemcpyAsync(b->p, host, sizeof(T) * count, hipMemcpyHostToDevice, stream());
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(H2D)", __FILE__, __LINE__);
-        *dev = b->as<T>();
-        return FBX_OK;
-    }
-    template <class T> int out(const T* host, size_t count, T** dev) {   // nullptr when the caller does not want it
-        *dev = nullptr;
-        if (!host) return FBX_OK;
-        auto* b = new DevBuf(); bufs.push_back(b);
-        FBX_TRY(b->alloc(sizeof(T) * count));
-        *dev = b->as<T>();
-        return FBX_OK;
-    }
-    template <class T> int back(T* host, const T* dev, size_t count) {
-        if (!host) return FBX_OK;
-        hipError_t e = hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, stream());
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(D2H)", __FILE__, __LINE__);
-        return FBX_OK;
-    }
-    int sync() { FBX_HIP(hipStreamSynchronize(stream())); return FBX_OK; }
-};
 
 int chernoff_check(const char* who, int n_qubits, int64_t B, const void* rho, const void* sigma, const void* qcb, int max_iters,
                    double zero_tol) {
@@ -404,12 +374,10 @@ int fbx_chernoff_bound(int n_qubits, int64_t B, const double* rho, const double*
     const size_t nm = ((size_t)2 << (2 * n_qubits));      // doubles per d x d complex matrix
     HostIO io; double *dr, *ds, *dq, *dl, *dsv; int32_t* dit;
     FBX_TRY(io.in(rho, nm * B, &dr)); FBX_TRY(io.in(sigma, nm * (sigma_shared ? 1 : B), &ds));
-    FBX_TRY(io.out(qcb_out, (size_t)B, &dq)); FBX_TRY(io.out(lower_out, (size_t)B, &dl));
-    FBX_TRY(io.out(s_out, (size_t)B, &dsv)); FBX_TRY(io.out(iters_out, (size_t)B, &dit));
+    FBX_TRY(io.out_opt(qcb_out, (size_t)B, &dq)); FBX_TRY(io.out_opt(lower_out, (size_t)B, &dl));
+    FBX_TRY(io.out_opt(s_out, (size_t)B, &dsv)); FBX_TRY(io.out_opt(iters_out, (size_t)B, &dit));
     FBX_TRY(fbx_chernoff_bound_dev(n_qubits, B, dr, ds, sigma_shared, tol, max_iters, zero_tol, dq, dl, dsv, dit));
-    FBX_TRY(io.back(qcb_out, dq, (size_t)B)); FBX_TRY(io.back(lower_out, dl, (size_t)B));
-    FBX_TRY(io.back(s_out, dsv, (size_t)B)); FBX_TRY(io.back(iters_out, dit, (size_t)B));
-    return io.sync();
+    return io.finish();
 }
 
 }  // extern "C"

@@ -81,14 +81,70 @@ void pool_give(void* p);
         if (!(cond)) { fbx::set_error(msg); return FBX_ERR_BAD_ARG; }          \
     } while (0)
 
-// Device staging buffer of a host-pointer entry point.  The block comes from the calling thread's
-// pool (no hipMalloc / hipFree per call once the pool is warm) and goes back when the entry point
-// returns -- every such entry point synchronises its stream before it does.
+#define FBX_TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
+
+// Device block from the calling thread's pool (no hipMalloc / hipFree per call once the pool is warm); it goes back when the
+// DevBuf goes out of scope, whatever is still queued on it.  Whoever holds one waits for that work first: HostIO below does
+// so on every path, fbx_pgdb_process_ex drains its streams by hand, and the asynchronous `_dev` launchers that keep one as
+// scratch rely on stream order instead (the pool serves one thread, whose next use of the block queues behind theirs).
 struct DevBuf {
     void* p = nullptr;
     ~DevBuf() { if (p) pool_give(p); }
     int alloc(size_t bytes) { return pool_take(bytes ? bytes : 16, &p); }
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
+};
+
+// Staging of a host-pointer entry point, all of it on the calling thread's stream(): in() uploads, out() / out_opt() reserve
+// a device block for a result and remember where it goes, the entry point calls its `_dev` form, and `return io.finish();`
+// downloads every registered result in the order it was registered and waits for the stream.  Leaving any other way -- a
+// failed allocation, a `_dev` form that rejects its arguments -- waits for the stream too before the blocks go back to the
+// pool: no copy or kernel is still running on a block, or into the caller's memory, once the entry point has returned.
+struct HostIO {
+    HostIO() = default;
+    HostIO(const HostIO&) = delete;
+    HostIO& operator=(const HostIO&) = delete;
+    ~HostIO() {
+        if (pending) (void)hipStreamSynchronize(stream());
+        for (void* p : blocks) pool_give(p);
+    }
+    // `count` elements uploaded from `host`; the block is there, and not written, for host == NULL or count == 0
+    template <class T> int in(const T* host, size_t count, T** dev) {
+        void* p = nullptr;
+        FBX_TRY(take(sizeof(T) * count, &p));
+        if (host && count) FBX_HIP(hipMemcpyAsync(p, host, sizeof(T) * count, hipMemcpyHostToDevice, stream()));
+        *dev = reinterpret_cast<T*>(p);
+        return FBX_OK;
+    }
+    // a result the `_dev` form writes whether or not the caller wants it: always a block, downloaded when `host` is not NULL
+    template <class T> int out(T* host, size_t count, T** dev) {
+        void* p = nullptr;
+        FBX_TRY(take(sizeof(T) * count, &p));
+        if (host && count) results.push_back({host, p, sizeof(T) * count});
+        *dev = reinterpret_cast<T*>(p);
+        return FBX_OK;
+    }
+    // a result the `_dev` form skips for a NULL pointer: no block and *dev = NULL when `host` is NULL
+    template <class T> int out_opt(T* host, size_t count, T** dev) {
+        *dev = nullptr;
+        return host ? out(host, count, dev) : FBX_OK;
+    }
+    int finish() {
+        for (const Result& r : results) FBX_HIP(hipMemcpyAsync(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost, stream()));
+        results.clear();
+        FBX_HIP(hipStreamSynchronize(stream()));
+        pending = false;
+        return FBX_OK;
+    }
+private:
+    struct Result { void* host; const void* dev; size_t bytes; };
+    std::vector<void*> blocks;
+    std::vector<Result> results;
+    bool pending = false;       // a block is out and the stream has not been waited for since
+    int take(size_t bytes, void** p) {
+        FBX_TRY(pool_take(bytes ? bytes : 16, p));
+        blocks.push_back(*p); pending = true;
+        return FBX_OK;
+    }
 };
 
 // ------------------------------------------------------------------ device-side design

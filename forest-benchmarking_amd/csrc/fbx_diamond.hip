@@ -428,39 +428,6 @@ int launch_diamond(int64_t B, const double* c0, const double* c1, int shared, do
 
 static_assert(Dia<3>::lds_bytes <= 160 * 1024, "3-qubit diamond kernel: LDS");
 
-struct HostIO {     // host <-> device staging for the host-pointer entry point
-    std::vector<DevBuf*> bufs;
-    ~HostIO() { for (auto* b : bufs) delete b; }
-    template <class T> int in(const T* host, size_t count, T** dev) {
-        auto* b = new DevBuf(); bufs.push_back(b);
-        int rc = b->alloc(sizeof(T) * count);
-        if (rc) return rc;
-        if (host && count) {
-            hipError_t e = hipMemcpyAsync(b->p, host, sizeof(T) * count, hipMemcpyHostToDevice, stream());
-            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(H2D)", __FILE__, __LINE__);
-        }
-        *dev = b->as<T>();
-        return FBX_OK;
-    }
-    template <class T> int out(const T* host, size_t count, T** dev) {   // nullptr when the caller does not want it
-        *dev = nullptr;
-        if (!host) return FBX_OK;
-        auto* b = new DevBuf(); bufs.push_back(b);
-        int rc = b->alloc(sizeof(T) * count);
-        if (rc) return rc;
-        *dev = b->as<T>();
-        return FBX_OK;
-    }
-    template <class T> int back(T* host, const T* dev, size_t count) {
-        if (!host || !count) return FBX_OK;
-        hipError_t e = hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, stream());
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(D2H)", __FILE__, __LINE__);
-        return FBX_OK;
-    }
-    int sync() { FBX_HIP(hipStreamSynchronize(stream())); return FBX_OK; }
-};
-#define FBX_TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
-
 int diamond_check(const char* who, int n_qubits, int64_t B, const void* c0, const void* c1, const void* dist, int max_iters) {
     if (n_qubits > 3) { set_error(std::string(who) + ": n_qubits must be 1..3 (larger pairs are not implemented)"); return FBX_ERR_UNSUPPORTED; }
     FBX_REQUIRE(n_qubits >= 1, "fbx_diamond_norm: n_qubits must be 1..3");
@@ -498,12 +465,10 @@ int fbx_diamond_norm(int n_qubits, int64_t B, const double* choi0, const double*
     const size_t d = (size_t)1 << n_qubits, D = d * d, nm = D * D * 2;
     HostIO io; double *dc0, *dc1, *ddist, *dup, *drho; int32_t* dit;
     FBX_TRY(io.in(choi0, nm * B, &dc0)); FBX_TRY(io.in(choi1, nm * (choi1_shared ? 1 : B), &dc1));
-    FBX_TRY(io.out(dist_out, (size_t)B, &ddist)); FBX_TRY(io.out(upper_out, (size_t)B, &dup));
-    FBX_TRY(io.out(rho_out, d * d * 2 * B, &drho)); FBX_TRY(io.out(iters_out, (size_t)B, &dit));
+    FBX_TRY(io.out_opt(dist_out, (size_t)B, &ddist)); FBX_TRY(io.out_opt(upper_out, (size_t)B, &dup));
+    FBX_TRY(io.out_opt(rho_out, d * d * 2 * B, &drho)); FBX_TRY(io.out_opt(iters_out, (size_t)B, &dit));
     FBX_TRY(fbx_diamond_norm_dev(n_qubits, B, dc0, dc1, choi1_shared, tol, max_iters, ddist, dup, drho, dit));
-    FBX_TRY(io.back(dist_out, ddist, (size_t)B)); FBX_TRY(io.back(upper_out, dup, (size_t)B));
-    FBX_TRY(io.back(rho_out, drho, d * d * 2 * B)); FBX_TRY(io.back(iters_out, dit, (size_t)B));
-    return io.sync();
+    return io.finish();
 }
 
 }  // extern "C"

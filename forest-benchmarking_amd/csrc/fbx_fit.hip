@@ -434,7 +434,8 @@ fit_prepare_kernel(int kind, long long B, int K, const double* __restrict__ valu
     if (has_weights_out) has_weights_out[b] = any ? 1 : 0;
 }
 
-static int fit_check(int model, int64_t B, int K, int64_t x_stride, unsigned vary, double ftol, double xtol, int max_iters) {
+static int fit_check(int model, int64_t B, int K, const void* x, int64_t x_stride, const void* y, const void* guess, unsigned vary,
+                     double ftol, double xtol, int max_iters) {
     const int P = fit_param_count(model);
     FBX_REQUIRE(P != 0, "fbx_curve_fit: unknown model id (FBX_FIT_BASE_DECAY .. FBX_FIT_SHIFTED_COSINE)");
     FBX_REQUIRE(B >= 0, "fbx_curve_fit: need B >= 0");
@@ -446,15 +447,23 @@ static int fit_check(int model, int64_t B, int K, int64_t x_stride, unsigned var
     FBX_REQUIRE(x_stride == 0 || x_stride == K, "fbx_curve_fit: x_stride must be 0 (one x for the batch) or K (one row per item)");
     FBX_REQUIRE((vary >> P) == 0u, "fbx_curve_fit: vary has bits beyond the model's parameters");
     FBX_REQUIRE(ftol >= 0.0 && xtol >= 0.0 && max_iters >= 0, "fbx_curve_fit: need ftol >= 0, xtol >= 0, max_iters >= 0");
+    FBX_REQUIRE(B == 0 || (x && y && guess), "fbx_curve_fit: NULL x / y / guess");
     return FBX_OK;
 }
 
-static int rb_check(const char* who, int dim, int max_dim, int64_t S) {
+static int rb_check(const char* who, int dim, int max_dim, int64_t S, const void* expectations, const void* std_errs) {
     if (dim < 2 || dim > max_dim || (dim & (dim - 1))) {
         set_error(std::string(who) + ": dim must be a power of two in 2.." + std::to_string(max_dim) + " (got " + std::to_string(dim) + ")");
         return (dim > max_dim && !(dim & (dim - 1))) ? FBX_ERR_UNSUPPORTED : FBX_ERR_BAD_ARG;
     }
     FBX_REQUIRE(S >= 0, std::string(who) + ": need S >= 0");
+    FBX_REQUIRE(S == 0 || (expectations && std_errs), std::string(who) + ": NULL expectations / std_errs");
+    return FBX_OK;
+}
+
+static int rb_survival_check(int dim, int64_t S, const void* expectations, const void* std_errs, int64_t num_shots) {
+    FBX_TRY(rb_check("fbx_rb_survival", dim, 32, S, expectations, std_errs));
+    FBX_REQUIRE(num_shots >= 0, "fbx_rb_survival: need num_shots >= 0 (0: the observables are independent)");
     return FBX_OK;
 }
 
@@ -470,15 +479,13 @@ int fbx_curve_fit_dev(int model, int64_t B, int K, const double* d_x, int64_t x_
                       const double* d_guess, unsigned vary, double ftol, double xtol, int max_iters, double* d_params_out,
                       double* d_covar_out, double* d_chisqr_out, double* d_redchi_out, int32_t* d_iters_out, int32_t* d_status_out,
                       double* d_grad_norm_out) {
-    int rc = fit_check(model, B, K, x_stride, vary, ftol, xtol, max_iters);
-    if (rc) return rc;
-    FBX_REQUIRE(B == 0 || (d_x && d_y && d_guess), "fbx_curve_fit: NULL x / y / guess");
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(fit_check(model, B, K, d_x, x_stride, d_y, d_guess, vary, ftol, xtol, max_iters));
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const size_t plane = sizeof(double) * (size_t)B * (size_t)K;
     const int planes = 1 + (d_weights ? 1 : 0) + (x_stride ? 1 : 0);
     void* ws = nullptr;
-    if ((rc = workspace(WS_FIT, plane * planes, &ws))) return rc;
+    FBX_TRY(workspace(WS_FIT, plane * planes, &ws));
     double* yT = reinterpret_cast<double*>(ws);
     double* wT = d_weights ? yT + (size_t)B * K : nullptr;
     double* xT = x_stride ? yT + (size_t)B * K * (d_weights ? 2 : 1) : nullptr;
@@ -506,50 +513,25 @@ int fbx_curve_fit(int model, int64_t B, int K, const double* x, int64_t x_stride
                   const double* guess, unsigned vary, double ftol, double xtol, int max_iters, double* params_out,
                   double* covar_out, double* chisqr_out, double* redchi_out, int32_t* iters_out, int32_t* status_out,
                   double* grad_norm_out) {
-    int rc = fit_check(model, B, K, x_stride, vary, ftol, xtol, max_iters);
-    if (rc) return rc;
-    FBX_REQUIRE(B == 0 || (x && y && guess), "fbx_curve_fit: NULL x / y / guess");
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(fit_check(model, B, K, x, x_stride, y, guess, vary, ftol, xtol, max_iters));
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const size_t P = (size_t)fit_param_count(model), n = (size_t)B, nk = n * (size_t)K, nx = x_stride ? nk : (size_t)K;
-    DevBuf dx, dy, dw, dg, dpar, dcov, dchi, dred, dit, dst, dgn;
-    if ((rc = dx.alloc(8 * nx)) || (rc = dy.alloc(8 * nk)) || (rc = dg.alloc(8 * n * P))) return rc;
-    if (weights && (rc = dw.alloc(8 * nk))) return rc;
-    if (params_out && (rc = dpar.alloc(8 * n * P))) return rc;
-    if (covar_out && (rc = dcov.alloc(8 * n * P * P))) return rc;
-    if (chisqr_out && (rc = dchi.alloc(8 * n))) return rc;
-    if (redchi_out && (rc = dred.alloc(8 * n))) return rc;
-    if (iters_out && (rc = dit.alloc(4 * n))) return rc;
-    if (status_out && (rc = dst.alloc(4 * n))) return rc;
-    if (grad_norm_out && (rc = dgn.alloc(8 * n))) return rc;
-    FBX_HIP(hipMemcpyAsync(dx.p, x, 8 * nx, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(dy.p, y, 8 * nk, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(dg.p, guess, 8 * n * P, hipMemcpyHostToDevice, stream()));
-    if (weights) FBX_HIP(hipMemcpyAsync(dw.p, weights, 8 * nk, hipMemcpyHostToDevice, stream()));
-    rc = fbx_curve_fit_dev(model, B, K, dx.as<double>(), x_stride, dy.as<double>(), weights ? dw.as<double>() : nullptr,
-                           dg.as<double>(), vary, ftol, xtol, max_iters, params_out ? dpar.as<double>() : nullptr,
-                           covar_out ? dcov.as<double>() : nullptr, chisqr_out ? dchi.as<double>() : nullptr,
-                           redchi_out ? dred.as<double>() : nullptr, iters_out ? dit.as<int32_t>() : nullptr,
-                           status_out ? dst.as<int32_t>() : nullptr, grad_norm_out ? dgn.as<double>() : nullptr);
-    if (rc) return rc;
-    if (params_out) FBX_HIP(hipMemcpyAsync(params_out, dpar.p, 8 * n * P, hipMemcpyDeviceToHost, stream()));
-    if (covar_out) FBX_HIP(hipMemcpyAsync(covar_out, dcov.p, 8 * n * P * P, hipMemcpyDeviceToHost, stream()));
-    if (chisqr_out) FBX_HIP(hipMemcpyAsync(chisqr_out, dchi.p, 8 * n, hipMemcpyDeviceToHost, stream()));
-    if (redchi_out) FBX_HIP(hipMemcpyAsync(redchi_out, dred.p, 8 * n, hipMemcpyDeviceToHost, stream()));
-    if (iters_out) FBX_HIP(hipMemcpyAsync(iters_out, dit.p, 4 * n, hipMemcpyDeviceToHost, stream()));
-    if (status_out) FBX_HIP(hipMemcpyAsync(status_out, dst.p, 4 * n, hipMemcpyDeviceToHost, stream()));
-    if (grad_norm_out) FBX_HIP(hipMemcpyAsync(grad_norm_out, dgn.p, 8 * n, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    HostIO io; double *dx, *dy, *dg, *dw = nullptr, *dpar, *dcov, *dchi, *dred, *dgn; int32_t *dit, *dst;
+    FBX_TRY(io.in(x, nx, &dx)); FBX_TRY(io.in(y, nk, &dy)); FBX_TRY(io.in(guess, n * P, &dg));
+    if (weights) FBX_TRY(io.in(weights, nk, &dw));
+    FBX_TRY(io.out_opt(params_out, n * P, &dpar)); FBX_TRY(io.out_opt(covar_out, n * P * P, &dcov));
+    FBX_TRY(io.out_opt(chisqr_out, n, &dchi)); FBX_TRY(io.out_opt(redchi_out, n, &dred));
+    FBX_TRY(io.out_opt(iters_out, n, &dit)); FBX_TRY(io.out_opt(status_out, n, &dst));
+    FBX_TRY(io.out_opt(grad_norm_out, n, &dgn));
+    FBX_TRY(fbx_curve_fit_dev(model, B, K, dx, x_stride, dy, dw, dg, vary, ftol, xtol, max_iters, dpar, dcov, dchi, dred, dit, dst, dgn));
+    return io.finish();
 }
 
 int fbx_rb_survival_dev(int dim, int64_t S, const double* d_expectations, const double* d_std_errs, int64_t num_shots,
                         double* d_survival_out, double* d_variance_out) {
-    int rc = rb_check("fbx_rb_survival", dim, 32, S);
-    if (rc) return rc;
-    FBX_REQUIRE(S == 0 || (d_expectations && d_std_errs), "fbx_rb_survival: NULL expectations / std_errs");
-    FBX_REQUIRE(num_shots >= 0, "fbx_rb_survival: need num_shots >= 0 (0: the observables are independent)");
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(rb_survival_check(dim, S, d_expectations, d_std_errs, num_shots));
+    FBX_TRY(ensure_device());
     if (S == 0) return FBX_OK;
     hipLaunchKernelGGL(rb_survival_kernel, dim3(grid_for(S)), dim3(256), 0, stream(), dim, (long long)S, d_expectations, d_std_errs,
                        (double)num_shots, d_survival_out, d_variance_out);
@@ -559,30 +541,21 @@ int fbx_rb_survival_dev(int dim, int64_t S, const double* d_expectations, const 
 
 int fbx_rb_survival(int dim, int64_t S, const double* expectations, const double* std_errs, int64_t num_shots,
                     double* survival_out, double* variance_out) {
-    int rc = rb_check("fbx_rb_survival", dim, 32, S);
-    if (rc) return rc;
-    FBX_REQUIRE(S == 0 || (expectations && std_errs), "fbx_rb_survival: NULL expectations / std_errs");
-    FBX_REQUIRE(num_shots >= 0, "fbx_rb_survival: need num_shots >= 0 (0: the observables are independent)");
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(rb_survival_check(dim, S, expectations, std_errs, num_shots));
+    FBX_TRY(ensure_device());
     if (S == 0) return FBX_OK;
-    const size_t n = (size_t)S, row = 8 * n * (size_t)(dim - 1);
-    DevBuf de, ds, dp, dv;
-    if ((rc = de.alloc(row)) || (rc = ds.alloc(row)) || (rc = dp.alloc(8 * n)) || (rc = dv.alloc(8 * n))) return rc;
-    FBX_HIP(hipMemcpyAsync(de.p, expectations, row, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(ds.p, std_errs, row, hipMemcpyHostToDevice, stream()));
-    if ((rc = fbx_rb_survival_dev(dim, S, de.as<double>(), ds.as<double>(), num_shots, dp.as<double>(), dv.as<double>()))) return rc;
-    if (survival_out) FBX_HIP(hipMemcpyAsync(survival_out, dp.p, 8 * n, hipMemcpyDeviceToHost, stream()));
-    if (variance_out) FBX_HIP(hipMemcpyAsync(variance_out, dv.p, 8 * n, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    const size_t n = (size_t)S, row = n * (size_t)(dim - 1);
+    HostIO io; double *de, *ds, *dp, *dv;
+    FBX_TRY(io.in(expectations, row, &de)); FBX_TRY(io.in(std_errs, row, &ds));
+    FBX_TRY(io.out(survival_out, n, &dp)); FBX_TRY(io.out(variance_out, n, &dv));
+    FBX_TRY(fbx_rb_survival_dev(dim, S, de, ds, num_shots, dp, dv));
+    return io.finish();
 }
 
 int fbx_rb_purity_dev(int dim, int64_t S, const double* d_expectations, const double* d_std_errs, int renorm, double* d_purity_out,
                       double* d_purity_err_out) {
-    int rc = rb_check("fbx_rb_purity", dim, 8, S);
-    if (rc) return rc;
-    FBX_REQUIRE(S == 0 || (d_expectations && d_std_errs), "fbx_rb_purity: NULL expectations / std_errs");
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(rb_check("fbx_rb_purity", dim, 8, S, d_expectations, d_std_errs));
+    FBX_TRY(ensure_device());
     if (S == 0) return FBX_OK;
     hipLaunchKernelGGL(rb_purity_kernel, dim3(grid_for(S)), dim3(256), 0, stream(), dim, (long long)S, d_expectations, d_std_errs,
                        renorm, d_purity_out, d_purity_err_out);
@@ -592,21 +565,15 @@ int fbx_rb_purity_dev(int dim, int64_t S, const double* d_expectations, const do
 
 int fbx_rb_purity(int dim, int64_t S, const double* expectations, const double* std_errs, int renorm, double* purity_out,
                   double* purity_err_out) {
-    int rc = rb_check("fbx_rb_purity", dim, 8, S);
-    if (rc) return rc;
-    FBX_REQUIRE(S == 0 || (expectations && std_errs), "fbx_rb_purity: NULL expectations / std_errs");
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(rb_check("fbx_rb_purity", dim, 8, S, expectations, std_errs));
+    FBX_TRY(ensure_device());
     if (S == 0) return FBX_OK;
-    const size_t n = (size_t)S, row = 8 * n * (size_t)(dim * dim - 1);
-    DevBuf de, ds, dp, dv;
-    if ((rc = de.alloc(row)) || (rc = ds.alloc(row)) || (rc = dp.alloc(8 * n)) || (rc = dv.alloc(8 * n))) return rc;
-    FBX_HIP(hipMemcpyAsync(de.p, expectations, row, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(ds.p, std_errs, row, hipMemcpyHostToDevice, stream()));
-    if ((rc = fbx_rb_purity_dev(dim, S, de.as<double>(), ds.as<double>(), renorm, dp.as<double>(), dv.as<double>()))) return rc;
-    if (purity_out) FBX_HIP(hipMemcpyAsync(purity_out, dp.p, 8 * n, hipMemcpyDeviceToHost, stream()));
-    if (purity_err_out) FBX_HIP(hipMemcpyAsync(purity_err_out, dv.p, 8 * n, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    const size_t n = (size_t)S, row = n * (size_t)(dim * dim - 1);
+    HostIO io; double *de, *ds, *dp, *dv;
+    FBX_TRY(io.in(expectations, row, &de)); FBX_TRY(io.in(std_errs, row, &ds));
+    FBX_TRY(io.out(purity_out, n, &dp)); FBX_TRY(io.out(purity_err_out, n, &dv));
+    FBX_TRY(fbx_rb_purity_dev(dim, S, de, ds, renorm, dp, dv));
+    return io.finish();
 }
 
 int fbx_fit_prepare_dev(int kind, int64_t B, int K, const double* d_values, const double* d_errors, int errors_are_variances,
@@ -615,8 +582,7 @@ int fbx_fit_prepare_dev(int kind, int64_t B, int K, const double* d_values, cons
     FBX_REQUIRE(B >= 0 && K >= 1, "fbx_fit_prepare: need B >= 0 and K >= 1");
     FBX_REQUIRE(B == 0 || d_values, "fbx_fit_prepare: NULL values");
     FBX_REQUIRE(d_errors || (!d_weights_out && !d_has_weights_out), "fbx_fit_prepare: weights asked for without errors");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     hipLaunchKernelGGL(fit_prepare_kernel, dim3(grid_for(B)), dim3(256), 0, stream(), kind, (long long)B, K, d_values, d_errors,
                        errors_are_variances, d_weights_out, d_guess_out, (int*)d_has_weights_out);

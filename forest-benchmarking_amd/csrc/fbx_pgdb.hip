@@ -610,25 +610,17 @@ int fbx_pgdb_cost_grad_dev(const fbx_design* design, int64_t B, const double* d_
 
 int fbx_pgdb_cost_grad(const fbx_design* design, int64_t B, const double* nvec, const double* choi_in, double eps,
                        double* cost_out, double* grad_out) {
-    int rc = ensure_device();
-    if (rc) return rc;
-    { const int r = check_design(design, "fbx_pgdb_cost_grad"); if (r) return r; }
+    FBX_TRY(ensure_device());
+    FBX_TRY(check_design(design, "fbx_pgdb_cost_grad"));
     FBX_REQUIRE(B >= 0, "fbx_pgdb_cost_grad: negative batch");
     FBX_REQUIRE(B == 0 || (nvec && choi_in && (cost_out || grad_out)), "fbx_pgdb_cost_grad: NULL buffer");
     if (B == 0) return FBX_OK;
     const size_t m = design->dev.m, DD = (size_t)design->dev.D * design->dev.D;
-    DevBuf dn, dchoi, dcost, dgrad;
-    if ((rc = dn.alloc(sizeof(double) * 2 * B * m)) || (rc = dchoi.alloc(sizeof(double) * 2 * B * DD)) ||
-        (rc = dcost.alloc(sizeof(double) * B)) || (grad_out && (rc = dgrad.alloc(sizeof(double) * 2 * B * DD))))
-        return rc;
-    FBX_HIP(hipMemcpyAsync(dn.p, nvec, sizeof(double) * 2 * B * m, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(dchoi.p, choi_in, sizeof(double) * 2 * B * DD, hipMemcpyHostToDevice, stream()));
-    rc = fbx_pgdb_cost_grad_dev(design, B, dn.as<double>(), dchoi.as<double>(), eps, dcost.as<double>(), grad_out ? dgrad.as<double>() : nullptr);
-    if (rc) { (void)hipStreamSynchronize(stream()); return rc; }
-    if (cost_out) FBX_HIP(hipMemcpyAsync(cost_out, dcost.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream()));
-    if (grad_out) FBX_HIP(hipMemcpyAsync(grad_out, dgrad.p, sizeof(double) * 2 * B * DD, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    HostIO io; double *dn, *dchoi, *dcost, *dgrad;
+    FBX_TRY(io.in(nvec, 2 * B * m, &dn)); FBX_TRY(io.in(choi_in, 2 * B * DD, &dchoi));
+    FBX_TRY(io.out(cost_out, (size_t)B, &dcost)); FBX_TRY(io.out_opt(grad_out, 2 * B * DD, &dgrad));
+    FBX_TRY(fbx_pgdb_cost_grad_dev(design, B, dn, dchoi, eps, dcost, dgrad));
+    return io.finish();
 }
 
 int fbx_pgdb_process(const fbx_design* design, int64_t B, const double* expect,

@@ -334,6 +334,20 @@ static int qv_check_width(int n_qubits, const char* who) {
     return FBX_OK;
 }
 
+static int qv_heavy_outputs_check(int n_qubits, int64_t B, int L, const void* pairs, const void* gates, const void* probs,
+                                  const void* median, const void* mask, const void* heavy_prob, const void* heavy_count) {
+    FBX_REQUIRE(B >= 0 && L >= 0, "fbx_qv_heavy_outputs: need B >= 0 and L >= 0");
+    FBX_REQUIRE(B == 0 || L == 0 || (pairs && gates), "fbx_qv_heavy_outputs: NULL pairs / gates");
+    FBX_REQUIRE(probs || median || mask || heavy_prob || heavy_count, "fbx_qv_heavy_outputs: no output asked for");
+    return qv_check_width(n_qubits, "fbx_qv_heavy_outputs");
+}
+
+static int qv_count_heavy_check(int n_qubits, int64_t B, int64_t n_shots, const void* bits, const void* mask, const void* counts) {
+    FBX_REQUIRE(B >= 0 && n_shots >= 0, "fbx_qv_count_heavy: need B >= 0 and n_shots >= 0");
+    FBX_REQUIRE(B == 0 || (mask && counts && (bits || n_shots == 0)), "fbx_qv_count_heavy: NULL buffer");
+    return qv_check_width(n_qubits, "fbx_qv_count_heavy");
+}
+
 }  // namespace fbx
 
 using namespace fbx;
@@ -342,13 +356,9 @@ extern "C" {
 
 int fbx_qv_heavy_outputs_dev(int n_qubits, int64_t B, int L, const uint8_t* d_pairs, const double* d_gates, double* d_probs_out,
                              double* d_median_out, uint64_t* d_heavy_mask_out, double* d_heavy_prob_out, int32_t* d_heavy_count_out) {
-    FBX_REQUIRE(B >= 0 && L >= 0, "fbx_qv_heavy_outputs: need B >= 0 and L >= 0");
-    FBX_REQUIRE(B == 0 || L == 0 || (d_pairs && d_gates), "fbx_qv_heavy_outputs: NULL pairs / gates");
-    FBX_REQUIRE(d_probs_out || d_median_out || d_heavy_mask_out || d_heavy_prob_out || d_heavy_count_out,
-                "fbx_qv_heavy_outputs: no output asked for");
-    int rc = qv_check_width(n_qubits, "fbx_qv_heavy_outputs");
-    if (rc) return rc;
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(qv_heavy_outputs_check(n_qubits, B, L, d_pairs, d_gates, d_probs_out, d_median_out, d_heavy_mask_out, d_heavy_prob_out,
+                                   d_heavy_count_out));
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const size_t state = sizeof(cplx) << n_qubits;
     if (n_qubits <= 8) {
@@ -373,50 +383,27 @@ int fbx_qv_heavy_outputs_dev(int n_qubits, int64_t B, int L, const uint8_t* d_pa
 
 int fbx_qv_heavy_outputs(int n_qubits, int64_t B, int L, const uint8_t* pairs, const double* gates, double* probs_out,
                          double* median_out, uint64_t* heavy_mask_out, double* heavy_prob_out, int32_t* heavy_count_out) {
-    FBX_REQUIRE(B >= 0 && L >= 0, "fbx_qv_heavy_outputs: need B >= 0 and L >= 0");
-    FBX_REQUIRE(B == 0 || L == 0 || (pairs && gates), "fbx_qv_heavy_outputs: NULL pairs / gates");
-    FBX_REQUIRE(probs_out || median_out || heavy_mask_out || heavy_prob_out || heavy_count_out,
-                "fbx_qv_heavy_outputs: no output asked for");
-    int rc = qv_check_width(n_qubits, "fbx_qv_heavy_outputs");
-    if (rc) return rc;
+    FBX_TRY(qv_heavy_outputs_check(n_qubits, B, L, pairs, gates, probs_out, median_out, heavy_mask_out, heavy_prob_out, heavy_count_out));
     const size_t n_gates = (size_t)B * (size_t)L;
     for (size_t g = 0; g < n_gates; ++g)
         FBX_REQUIRE(pairs[2 * g] < n_qubits && pairs[2 * g + 1] < n_qubits && pairs[2 * g] != pairs[2 * g + 1],
                     "fbx_qv_heavy_outputs: a gate needs two different qubits below n_qubits");
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
-    const size_t N = (size_t)1 << n_qubits, W = N >= 64 ? N / 64 : 1;
-    DevBuf dp, dg, dprob, dmed, dmask, dhp, dhc;
-    if ((rc = dp.alloc(2 * n_gates)) || (rc = dg.alloc(sizeof(double) * 32 * n_gates))) return rc;
-    if (probs_out && (rc = dprob.alloc(sizeof(double) * B * N))) return rc;
-    if (median_out && (rc = dmed.alloc(sizeof(double) * B))) return rc;
-    if (heavy_mask_out && (rc = dmask.alloc(sizeof(uint64_t) * B * W))) return rc;
-    if (heavy_prob_out && (rc = dhp.alloc(sizeof(double) * B))) return rc;
-    if (heavy_count_out && (rc = dhc.alloc(sizeof(int32_t) * B))) return rc;
-    if (n_gates) {
-        FBX_HIP(hipMemcpyAsync(dp.p, pairs, 2 * n_gates, hipMemcpyHostToDevice, stream()));
-        FBX_HIP(hipMemcpyAsync(dg.p, gates, sizeof(double) * 32 * n_gates, hipMemcpyHostToDevice, stream()));
-    }
-    rc = fbx_qv_heavy_outputs_dev(n_qubits, B, L, dp.as<uint8_t>(), dg.as<double>(), probs_out ? dprob.as<double>() : nullptr,
-                                  median_out ? dmed.as<double>() : nullptr, heavy_mask_out ? dmask.as<uint64_t>() : nullptr,
-                                  heavy_prob_out ? dhp.as<double>() : nullptr, heavy_count_out ? dhc.as<int32_t>() : nullptr);
-    if (rc) return rc;
-    if (probs_out) FBX_HIP(hipMemcpyAsync(probs_out, dprob.p, sizeof(double) * B * N, hipMemcpyDeviceToHost, stream()));
-    if (median_out) FBX_HIP(hipMemcpyAsync(median_out, dmed.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream()));
-    if (heavy_mask_out) FBX_HIP(hipMemcpyAsync(heavy_mask_out, dmask.p, sizeof(uint64_t) * B * W, hipMemcpyDeviceToHost, stream()));
-    if (heavy_prob_out) FBX_HIP(hipMemcpyAsync(heavy_prob_out, dhp.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream()));
-    if (heavy_count_out) FBX_HIP(hipMemcpyAsync(heavy_count_out, dhc.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    const size_t n = (size_t)B, N = (size_t)1 << n_qubits, W = N >= 64 ? N / 64 : 1;
+    HostIO io; uint8_t* dp; double *dg, *dprob, *dmed, *dhp; uint64_t* dmask; int32_t* dhc;
+    FBX_TRY(io.in(pairs, 2 * n_gates, &dp)); FBX_TRY(io.in(gates, 32 * n_gates, &dg));
+    FBX_TRY(io.out_opt(probs_out, n * N, &dprob)); FBX_TRY(io.out_opt(median_out, n, &dmed));
+    FBX_TRY(io.out_opt(heavy_mask_out, n * W, &dmask)); FBX_TRY(io.out_opt(heavy_prob_out, n, &dhp));
+    FBX_TRY(io.out_opt(heavy_count_out, n, &dhc));
+    FBX_TRY(fbx_qv_heavy_outputs_dev(n_qubits, B, L, dp, dg, dprob, dmed, dmask, dhp, dhc));
+    return io.finish();
 }
 
 int fbx_qv_count_heavy_dev(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* d_bits, const uint64_t* d_heavy_mask,
                            int64_t* d_counts_out) {
-    FBX_REQUIRE(B >= 0 && n_shots >= 0, "fbx_qv_count_heavy: need B >= 0 and n_shots >= 0");
-    FBX_REQUIRE(B == 0 || (d_heavy_mask && d_counts_out && (d_bits || n_shots == 0)), "fbx_qv_count_heavy: NULL buffer");
-    int rc = qv_check_width(n_qubits, "fbx_qv_count_heavy");
-    if (rc) return rc;
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(qv_count_heavy_check(n_qubits, B, n_shots, d_bits, d_heavy_mask, d_counts_out));
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     switch (n_qubits) {
 #define FBX_QV_COUNT(NQ) case NQ: return launch_qv_count<NQ>(B, n_shots, d_bits, d_heavy_mask, d_counts_out)
@@ -429,23 +416,15 @@ int fbx_qv_count_heavy_dev(int n_qubits, int64_t B, int64_t n_shots, const uint8
 
 int fbx_qv_count_heavy(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* bits, const uint64_t* heavy_mask,
                        int64_t* counts_out) {
-    FBX_REQUIRE(B >= 0 && n_shots >= 0, "fbx_qv_count_heavy: need B >= 0 and n_shots >= 0");
-    FBX_REQUIRE(B == 0 || (heavy_mask && counts_out && (bits || n_shots == 0)), "fbx_qv_count_heavy: NULL buffer");
-    int rc = qv_check_width(n_qubits, "fbx_qv_count_heavy");
-    if (rc) return rc;
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(qv_count_heavy_check(n_qubits, B, n_shots, bits, heavy_mask, counts_out));
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const size_t N = (size_t)1 << n_qubits, W = N >= 64 ? N / 64 : 1;
-    const size_t nb = (size_t)B * n_shots * n_qubits;
-    DevBuf db, dm, dc;
-    if ((rc = db.alloc(nb)) || (rc = dm.alloc(sizeof(uint64_t) * B * W)) || (rc = dc.alloc(sizeof(int64_t) * B))) return rc;
-    if (nb) FBX_HIP(hipMemcpyAsync(db.p, bits, nb, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(dm.p, heavy_mask, sizeof(uint64_t) * B * W, hipMemcpyHostToDevice, stream()));
-    rc = fbx_qv_count_heavy_dev(n_qubits, B, n_shots, db.as<uint8_t>(), dm.as<uint64_t>(), dc.as<int64_t>());
-    if (rc) return rc;
-    FBX_HIP(hipMemcpyAsync(counts_out, dc.p, sizeof(int64_t) * B, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    HostIO io; uint8_t* db; uint64_t* dm; int64_t* dc;
+    FBX_TRY(io.in(bits, (size_t)B * n_shots * n_qubits, &db)); FBX_TRY(io.in(heavy_mask, (size_t)B * W, &dm));
+    FBX_TRY(io.out(counts_out, (size_t)B, &dc));
+    FBX_TRY(fbx_qv_count_heavy_dev(n_qubits, B, n_shots, db, dm, dc));
+    return io.finish();
 }
 
 }  // namespace fbx C ABI

@@ -245,8 +245,7 @@ int fbx_random_operators_dev(int kind, int dim, int cols_or_rank, int64_t B, uin
             FBX_REQUIRE(cols_or_rank <= dim, "The rank of the state matrix cannot exceed the dimension.");
         }
     }
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     if (kind == FBX_RAND_GINIBRE) {
         const long long total = (long long)B * dim * cols_or_rank, want = (total + 255) / 256;
@@ -267,8 +266,7 @@ int fbx_random_kraus_dev(int n_qubits, int64_t B, int K, uint64_t seed, int64_t 
     FBX_REQUIRE(K >= 1 && K <= 64, "fbx_random_kraus: 1 <= K <= 64 Kraus operators");
     FBX_REQUIRE(B >= 0 && (B == 0 || d_kraus_out), "fbx_random_kraus: bad batch / NULL buffer");
     FBX_REQUIRE(first_item >= 0, "fbx_random_kraus: negative first_item");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const int d = 1 << n_qubits;
     const unsigned grid = (unsigned)(B < 256 * 32 ? B : 256 * 32);
@@ -291,35 +289,26 @@ static size_t random_out_doubles(int kind, int dim, int cols_or_rank) {
 
 int fbx_random_operators(int kind, int dim, int cols_or_rank, int64_t B, uint64_t seed, int64_t first_item, double* out) {
     FBX_REQUIRE(B >= 0 && (B == 0 || out), "fbx_random_operators: bad batch / NULL buffer");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     FBX_REQUIRE(kind >= FBX_RAND_GINIBRE && kind <= FBX_RAND_BURES_STATE && dim >= 1 && cols_or_rank >= (kind == FBX_RAND_GINIBRE || kind == FBX_RAND_GINIBRE_STATE ? 1 : 0),
                 "fbx_random_operators: bad kind / shape");
     const size_t n = random_out_doubles(kind, dim, cols_or_rank) * (size_t)B;
-    DevBuf d;
-    if ((rc = d.alloc(sizeof(double) * n))) return rc;
-    rc = fbx_random_operators_dev(kind, dim, cols_or_rank, B, seed, first_item, d.as<double>());
-    if (rc) return rc;
-    FBX_HIP(hipMemcpyAsync(out, d.p, sizeof(double) * n, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    HostIO io; double* d;
+    FBX_TRY(io.out(out, n, &d));
+    FBX_TRY(fbx_random_operators_dev(kind, dim, cols_or_rank, B, seed, first_item, d));
+    return io.finish();
 }
 
 int fbx_random_kraus(int n_qubits, int64_t B, int K, uint64_t seed, int64_t first_item, double* kraus_out) {
     FBX_REQUIRE(B >= 0 && (B == 0 || kraus_out), "fbx_random_kraus: bad batch / NULL buffer");
     FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 3 && K >= 1 && K <= 64, "fbx_random_kraus: n_qubits must be 1..3, 1 <= K <= 64");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
-    const size_t n = 2 * (size_t)B * K * (1u << (2 * n_qubits));
-    DevBuf d;
-    if ((rc = d.alloc(sizeof(double) * n))) return rc;
-    rc = fbx_random_kraus_dev(n_qubits, B, K, seed, first_item, d.as<double>());
-    if (rc) return rc;
-    FBX_HIP(hipMemcpyAsync(kraus_out, d.p, sizeof(double) * n, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    HostIO io; double* d;
+    FBX_TRY(io.out(kraus_out, 2 * (size_t)B * K * (1u << (2 * n_qubits)), &d));
+    FBX_TRY(fbx_random_kraus_dev(n_qubits, B, K, seed, first_item, d));
+    return io.finish();
 }
 
 }  // extern "C"

@@ -272,69 +272,16 @@ static int rpe_check_depths(int K, const char* who) {
     return FBX_OK;
 }
 
-}  // namespace fbx
-
-using namespace fbx;
-
-extern "C" {
-
-int fbx_rpe_phase_dev(int64_t B, int K, const double* d_x, const double* d_y, const double* d_x_err, const double* d_y_err,
-                      int errors_are_variances, const double* d_xz, const double* d_yz, const double* d_xz_err,
-                      const double* d_yz_err, int post_select, double* d_phase_out, int32_t* d_depth_reached_out,
-                      double* d_bloch_out) {
-    FBX_REQUIRE(B >= 0 && K >= 1, "fbx_rpe_phase: need B >= 0 and K >= 1");
-    FBX_REQUIRE(B == 0 || (d_x && d_y && d_x_err && d_y_err), "fbx_rpe_phase: NULL moments");
-    FBX_REQUIRE((d_xz != nullptr) == (d_yz != nullptr) && (d_xz != nullptr) == (d_xz_err != nullptr) &&
-                (d_xz != nullptr) == (d_yz_err != nullptr), "fbx_rpe_phase: the four partner arrays come together or not at all");
-    FBX_REQUIRE(post_select == 0 || post_select == 1, "fbx_rpe_phase: post_select must be 0 or 1");
-    FBX_REQUIRE(d_phase_out || d_depth_reached_out || d_bloch_out, "fbx_rpe_phase: no output asked for");
-    int rc = rpe_check_depths(K, "fbx_rpe_phase");
-    if (rc) return rc;
-    if ((rc = ensure_device())) return rc;
-    if (B == 0) return FBX_OK;
-    const long long want = ((long long)B + 255) / 256;
-    const unsigned grid = (unsigned)(want < 256 * 32 ? want : 256 * 32);
-    hipLaunchKernelGGL(rpe_phase_kernel, dim3(grid), dim3(256), 0, stream(), (long long)B, K, d_x, d_y, d_x_err, d_y_err, d_xz, d_yz,
-                       d_xz_err, d_yz_err, errors_are_variances ? 1 : 0, post_select, d_phase_out, (int*)d_depth_reached_out,
-                       d_bloch_out);
-    FBX_HIP(hipGetLastError());
-    return FBX_OK;
-}
-
-int fbx_rpe_phase(int64_t B, int K, const double* x, const double* y, const double* x_err, const double* y_err,
-                  int errors_are_variances, const double* xz, const double* yz, const double* xz_err, const double* yz_err,
-                  int post_select, double* phase_out, int32_t* depth_reached_out, double* bloch_out) {
+static int rpe_phase_check(int64_t B, int K, const void* x, const void* y, const void* x_err, const void* y_err, const void* xz,
+                           const void* yz, const void* xz_err, const void* yz_err, int post_select, const void* phase,
+                           const void* depth, const void* bloch) {
     FBX_REQUIRE(B >= 0 && K >= 1, "fbx_rpe_phase: need B >= 0 and K >= 1");
     FBX_REQUIRE(B == 0 || (x && y && x_err && y_err), "fbx_rpe_phase: NULL moments");
     FBX_REQUIRE((xz != nullptr) == (yz != nullptr) && (xz != nullptr) == (xz_err != nullptr) && (xz != nullptr) == (yz_err != nullptr),
                 "fbx_rpe_phase: the four partner arrays come together or not at all");
     FBX_REQUIRE(post_select == 0 || post_select == 1, "fbx_rpe_phase: post_select must be 0 or 1");
-    FBX_REQUIRE(phase_out || depth_reached_out || bloch_out, "fbx_rpe_phase: no output asked for");
-    int rc = rpe_check_depths(K, "fbx_rpe_phase");
-    if (rc) return rc;
-    if ((rc = ensure_device())) return rc;
-    if (B == 0) return FBX_OK;
-    const size_t n = (size_t)B * K, bytes = sizeof(double) * n;
-    const double* src[8] = {x, y, x_err, y_err, xz, yz, xz_err, yz_err};
-    DevBuf in[8], dphase, ddepth, dbloch;
-    const int n_in = xz ? 8 : 4;
-    for (int a = 0; a < n_in; ++a) {
-        if ((rc = in[a].alloc(bytes))) return rc;
-        FBX_HIP(hipMemcpyAsync(in[a].p, src[a], bytes, hipMemcpyHostToDevice, stream()));
-    }
-    if (phase_out && (rc = dphase.alloc(sizeof(double) * B))) return rc;
-    if (depth_reached_out && (rc = ddepth.alloc(sizeof(int32_t) * B))) return rc;
-    if (bloch_out && (rc = dbloch.alloc(2 * bytes))) return rc;
-    rc = fbx_rpe_phase_dev(B, K, in[0].as<double>(), in[1].as<double>(), in[2].as<double>(), in[3].as<double>(), errors_are_variances,
-                           xz ? in[4].as<double>() : nullptr, xz ? in[5].as<double>() : nullptr, xz ? in[6].as<double>() : nullptr,
-                           xz ? in[7].as<double>() : nullptr, post_select, phase_out ? dphase.as<double>() : nullptr,
-                           depth_reached_out ? ddepth.as<int32_t>() : nullptr, bloch_out ? dbloch.as<double>() : nullptr);
-    if (rc) return rc;
-    if (phase_out) FBX_HIP(hipMemcpyAsync(phase_out, dphase.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream()));
-    if (depth_reached_out) FBX_HIP(hipMemcpyAsync(depth_reached_out, ddepth.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream()));
-    if (bloch_out) FBX_HIP(hipMemcpyAsync(bloch_out, dbloch.p, 2 * bytes, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    FBX_REQUIRE(phase || depth || bloch, "fbx_rpe_phase: no output asked for");
+    return rpe_check_depths(K, "fbx_rpe_phase");
 }
 
 static int rpe_shots_check(int n_qubits, int64_t B, int K, int64_t n_shots, const void* x_bits, const void* y_bits, int col, int zcol,
@@ -349,13 +296,59 @@ static int rpe_shots_check(int n_qubits, int64_t B, int K, int64_t n_shots, cons
     return rpe_check_depths(K, "fbx_rpe_from_shots");
 }
 
+static int circular_stats_check(int64_t R, int64_t B, const void* angles, const void* mean, const void* sd, const void* nan_count) {
+    FBX_REQUIRE(R >= 0 && B >= 0, "fbx_circular_stats: need R >= 0 and B >= 0");
+    FBX_REQUIRE(R * B == 0 || angles, "fbx_circular_stats: NULL angles");
+    FBX_REQUIRE(mean || sd || nan_count, "fbx_circular_stats: no output asked for");
+    return FBX_OK;
+}
+
+}  // namespace fbx
+
+using namespace fbx;
+
+extern "C" {
+
+int fbx_rpe_phase_dev(int64_t B, int K, const double* d_x, const double* d_y, const double* d_x_err, const double* d_y_err,
+                      int errors_are_variances, const double* d_xz, const double* d_yz, const double* d_xz_err,
+                      const double* d_yz_err, int post_select, double* d_phase_out, int32_t* d_depth_reached_out,
+                      double* d_bloch_out) {
+    FBX_TRY(rpe_phase_check(B, K, d_x, d_y, d_x_err, d_y_err, d_xz, d_yz, d_xz_err, d_yz_err, post_select, d_phase_out,
+                            d_depth_reached_out, d_bloch_out));
+    FBX_TRY(ensure_device());
+    if (B == 0) return FBX_OK;
+    const long long want = ((long long)B + 255) / 256;
+    const unsigned grid = (unsigned)(want < 256 * 32 ? want : 256 * 32);
+    hipLaunchKernelGGL(rpe_phase_kernel, dim3(grid), dim3(256), 0, stream(), (long long)B, K, d_x, d_y, d_x_err, d_y_err, d_xz, d_yz,
+                       d_xz_err, d_yz_err, errors_are_variances ? 1 : 0, post_select, d_phase_out, (int*)d_depth_reached_out,
+                       d_bloch_out);
+    FBX_HIP(hipGetLastError());
+    return FBX_OK;
+}
+
+int fbx_rpe_phase(int64_t B, int K, const double* x, const double* y, const double* x_err, const double* y_err,
+                  int errors_are_variances, const double* xz, const double* yz, const double* xz_err, const double* yz_err,
+                  int post_select, double* phase_out, int32_t* depth_reached_out, double* bloch_out) {
+    FBX_TRY(rpe_phase_check(B, K, x, y, x_err, y_err, xz, yz, xz_err, yz_err, post_select, phase_out, depth_reached_out, bloch_out));
+    FBX_TRY(ensure_device());
+    if (B == 0) return FBX_OK;
+    const size_t n = (size_t)B * K;
+    const double* src[8] = {x, y, x_err, y_err, xz, yz, xz_err, yz_err};
+    HostIO io; double *din[8] = {}, *dphase, *dbloch; int32_t* ddepth;
+    for (int a = 0; a < (xz ? 8 : 4); ++a) FBX_TRY(io.in(src[a], n, &din[a]));
+    FBX_TRY(io.out_opt(phase_out, (size_t)B, &dphase)); FBX_TRY(io.out_opt(depth_reached_out, (size_t)B, &ddepth));
+    FBX_TRY(io.out_opt(bloch_out, 2 * n, &dbloch));
+    FBX_TRY(fbx_rpe_phase_dev(B, K, din[0], din[1], din[2], din[3], errors_are_variances, din[4], din[5], din[6], din[7], post_select,
+                              dphase, ddepth, dbloch));
+    return io.finish();
+}
+
 int fbx_rpe_from_shots_dev(int n_qubits, int64_t B, int K, int64_t n_shots, const uint8_t* d_x_bits, const uint8_t* d_y_bits,
                            int col, int zcol, int post_select, double* d_phase_out, int32_t* d_depth_reached_out,
                            double* d_bloch_out, double* d_moments_out) {
-    int rc = rpe_shots_check(n_qubits, B, K, n_shots, d_x_bits, d_y_bits, col, zcol, post_select, d_phase_out, d_depth_reached_out,
-                             d_bloch_out, d_moments_out);
-    if (rc) return rc;
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(rpe_shots_check(n_qubits, B, K, n_shots, d_x_bits, d_y_bits, col, zcol, post_select, d_phase_out, d_depth_reached_out,
+                            d_bloch_out, d_moments_out));
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     switch (n_qubits) {
 #define FBX_RPE_SHOTS(NQ) case NQ: return launch_rpe_shots<NQ>(B, K, n_shots, d_x_bits, d_y_bits, col, zcol, post_select, \
@@ -370,39 +363,23 @@ int fbx_rpe_from_shots_dev(int n_qubits, int64_t B, int K, int64_t n_shots, cons
 int fbx_rpe_from_shots(int n_qubits, int64_t B, int K, int64_t n_shots, const uint8_t* x_bits, const uint8_t* y_bits, int col,
                        int zcol, int post_select, double* phase_out, int32_t* depth_reached_out, double* bloch_out,
                        double* moments_out) {
-    int rc = rpe_shots_check(n_qubits, B, K, n_shots, x_bits, y_bits, col, zcol, post_select, phase_out, depth_reached_out, bloch_out,
-                             moments_out);
-    if (rc) return rc;
-    if ((rc = ensure_device())) return rc;
+    FBX_TRY(rpe_shots_check(n_qubits, B, K, n_shots, x_bits, y_bits, col, zcol, post_select, phase_out, depth_reached_out, bloch_out,
+                            moments_out));
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const size_t items = (size_t)B * K, nb = items * (size_t)n_shots * (size_t)n_qubits;
-    DevBuf dx, dy, dphase, ddepth, dbloch, dmom;
-    if ((rc = dx.alloc(nb)) || (rc = dy.alloc(nb))) return rc;
-    if (phase_out && (rc = dphase.alloc(sizeof(double) * B))) return rc;
-    if (depth_reached_out && (rc = ddepth.alloc(sizeof(int32_t) * B))) return rc;
-    if (bloch_out && (rc = dbloch.alloc(sizeof(double) * 2 * items))) return rc;
-    if (moments_out && (rc = dmom.alloc(sizeof(double) * 4 * items))) return rc;
-    FBX_HIP(hipMemcpyAsync(dx.p, x_bits, nb, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(dy.p, y_bits, nb, hipMemcpyHostToDevice, stream()));
-    rc = fbx_rpe_from_shots_dev(n_qubits, B, K, n_shots, dx.as<uint8_t>(), dy.as<uint8_t>(), col, zcol, post_select,
-                                phase_out ? dphase.as<double>() : nullptr, depth_reached_out ? ddepth.as<int32_t>() : nullptr,
-                                bloch_out ? dbloch.as<double>() : nullptr, moments_out ? dmom.as<double>() : nullptr);
-    if (rc) return rc;
-    if (phase_out) FBX_HIP(hipMemcpyAsync(phase_out, dphase.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream()));
-    if (depth_reached_out) FBX_HIP(hipMemcpyAsync(depth_reached_out, ddepth.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream()));
-    if (bloch_out) FBX_HIP(hipMemcpyAsync(bloch_out, dbloch.p, sizeof(double) * 2 * items, hipMemcpyDeviceToHost, stream()));
-    if (moments_out) FBX_HIP(hipMemcpyAsync(moments_out, dmom.p, sizeof(double) * 4 * items, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    HostIO io; uint8_t *dx, *dy; double *dphase, *dbloch, *dmom; int32_t* ddepth;
+    FBX_TRY(io.in(x_bits, nb, &dx)); FBX_TRY(io.in(y_bits, nb, &dy));
+    FBX_TRY(io.out_opt(phase_out, (size_t)B, &dphase)); FBX_TRY(io.out_opt(depth_reached_out, (size_t)B, &ddepth));
+    FBX_TRY(io.out_opt(bloch_out, 2 * items, &dbloch)); FBX_TRY(io.out_opt(moments_out, 4 * items, &dmom));
+    FBX_TRY(fbx_rpe_from_shots_dev(n_qubits, B, K, n_shots, dx, dy, col, zcol, post_select, dphase, ddepth, dbloch, dmom));
+    return io.finish();
 }
 
 int fbx_circular_stats_dev(int64_t R, int64_t B, const double* d_angles, double* d_mean_out, double* d_std_out,
                            int32_t* d_nan_count_out) {
-    FBX_REQUIRE(R >= 0 && B >= 0, "fbx_circular_stats: need R >= 0 and B >= 0");
-    FBX_REQUIRE(R * B == 0 || d_angles, "fbx_circular_stats: NULL angles");
-    FBX_REQUIRE(d_mean_out || d_std_out || d_nan_count_out, "fbx_circular_stats: no output asked for");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(circular_stats_check(R, B, d_angles, d_mean_out, d_std_out, d_nan_count_out));
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const long long want = ((long long)B + 255) / 256;
     const unsigned grid = (unsigned)(want < 256 * 32 ? want : 256 * 32);
@@ -413,27 +390,15 @@ int fbx_circular_stats_dev(int64_t R, int64_t B, const double* d_angles, double*
 }
 
 int fbx_circular_stats(int64_t R, int64_t B, const double* angles, double* mean_out, double* std_out, int32_t* nan_count_out) {
-    FBX_REQUIRE(R >= 0 && B >= 0, "fbx_circular_stats: need R >= 0 and B >= 0");
-    FBX_REQUIRE(R * B == 0 || angles, "fbx_circular_stats: NULL angles");
-    FBX_REQUIRE(mean_out || std_out || nan_count_out, "fbx_circular_stats: no output asked for");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(circular_stats_check(R, B, angles, mean_out, std_out, nan_count_out));
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
-    const size_t n = (size_t)R * B;
-    DevBuf da, dm, ds, dn;
-    if ((rc = da.alloc(sizeof(double) * n))) return rc;
-    if (mean_out && (rc = dm.alloc(sizeof(double) * B))) return rc;
-    if (std_out && (rc = ds.alloc(sizeof(double) * B))) return rc;
-    if (nan_count_out && (rc = dn.alloc(sizeof(int32_t) * B))) return rc;
-    if (n) FBX_HIP(hipMemcpyAsync(da.p, angles, sizeof(double) * n, hipMemcpyHostToDevice, stream()));
-    rc = fbx_circular_stats_dev(R, B, da.as<double>(), mean_out ? dm.as<double>() : nullptr, std_out ? ds.as<double>() : nullptr,
-                                nan_count_out ? dn.as<int32_t>() : nullptr);
-    if (rc) return rc;
-    if (mean_out) FBX_HIP(hipMemcpyAsync(mean_out, dm.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream()));
-    if (std_out) FBX_HIP(hipMemcpyAsync(std_out, ds.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream()));
-    if (nan_count_out) FBX_HIP(hipMemcpyAsync(nan_count_out, dn.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    HostIO io; double *da, *dm, *ds; int32_t* dn;
+    FBX_TRY(io.in(angles, (size_t)R * B, &da));
+    FBX_TRY(io.out_opt(mean_out, (size_t)B, &dm)); FBX_TRY(io.out_opt(std_out, (size_t)B, &ds));
+    FBX_TRY(io.out_opt(nan_count_out, (size_t)B, &dn));
+    FBX_TRY(fbx_circular_stats_dev(R, B, da, dm, ds, dn));
+    return io.finish();
 }
 
 }  // extern "C"

@@ -421,6 +421,29 @@ calibrate_kernel(long long B, long long m, const double* __restrict__ expect, co
     }
 }
 
+static int calibrate_check(int64_t B, int64_t m, const void* expect, const void* std_err, const void* cal_index, int64_t n_cal,
+                           const void* cal_mean, const void* cal_var, const void* mean, const void* err) {
+    FBX_REQUIRE(B >= 0 && m >= 0 && n_cal >= 0, "fbx_calibrate_expectations: negative size");
+    FBX_REQUIRE(B * m == 0 || (expect && std_err && cal_mean && cal_var && mean && err), "fbx_calibrate_expectations: NULL buffer");
+    FBX_REQUIRE(cal_index != nullptr || n_cal == m, "fbx_calibrate_expectations: without cal_index there must be one calibration per setting");
+    return FBX_OK;
+}
+
+static int shots_check(int n_qubits, int64_t n_settings, int64_t n_shots, const void* bits, const void* obs_mask, const void* mean,
+                       const void* var) {
+    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 64, "fbx_shots_to_moments: n_qubits must be 1..64");
+    FBX_REQUIRE(n_settings >= 0 && n_shots >= 1, "fbx_shots_to_moments: need n_settings >= 0 and n_shots >= 1");
+    FBX_REQUIRE(n_settings == 0 || (bits && obs_mask && mean && var), "fbx_shots_to_moments: NULL buffer");
+    return FBX_OK;
+}
+
+static int beta_resample_check(int64_t n, int64_t R, const void* expect, const void* counts, double prior_counts, const void* out) {
+    FBX_REQUIRE(n >= 0 && R >= 0, "fbx_beta_resample: need n >= 0 and R >= 0");
+    FBX_REQUIRE(prior_counts > 0.0, "fbx_beta_resample: prior_counts must be positive");
+    FBX_REQUIRE(n * R == 0 || (expect && counts && out), "fbx_beta_resample: NULL buffer");
+    return FBX_OK;
+}
+
 }  // namespace fbx
 
 using namespace fbx;
@@ -430,12 +453,8 @@ extern "C" {
 int fbx_calibrate_expectations_dev(int64_t B, int64_t m, const double* d_expect, const double* d_std_err,
                                    const int32_t* d_cal_index, int64_t n_cal, const double* d_cal_mean,
                                    const double* d_cal_var, double* d_mean_out, double* d_err_out) {
-    FBX_REQUIRE(B >= 0 && m >= 0 && n_cal >= 0, "fbx_calibrate_expectations: negative size");
-    FBX_REQUIRE(B * m == 0 || (d_expect && d_std_err && d_cal_mean && d_cal_var && d_mean_out && d_err_out),
-                "fbx_calibrate_expectations: NULL buffer");
-    FBX_REQUIRE(d_cal_index != nullptr || n_cal == m, "fbx_calibrate_expectations: without cal_index there must be one calibration per setting");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(calibrate_check(B, m, d_expect, d_std_err, d_cal_index, n_cal, d_cal_mean, d_cal_var, d_mean_out, d_err_out));
+    FBX_TRY(ensure_device());
     if (B * m == 0) return FBX_OK;
     const long long total = (long long)B * m, want = (total + 255) / 256;
     hipLaunchKernelGGL(calibrate_kernel, dim3((unsigned)(want < 256 * 32 ? want : 256 * 32)), dim3(256), 0, stream(),
@@ -448,44 +467,27 @@ int fbx_calibrate_expectations_dev(int64_t B, int64_t m, const double* d_expect,
 int fbx_calibrate_expectations(int64_t B, int64_t m, const double* expect, const double* std_err,
                                const int32_t* cal_index, int64_t n_cal, const double* cal_mean,
                                const double* cal_var, double* mean_out, double* err_out) {
-    FBX_REQUIRE(B >= 0 && m >= 0 && n_cal >= 0, "fbx_calibrate_expectations: negative size");
-    FBX_REQUIRE(B * m == 0 || (expect && std_err && cal_mean && cal_var && mean_out && err_out),
-                "fbx_calibrate_expectations: NULL buffer");
-    FBX_REQUIRE(cal_index != nullptr || n_cal == m, "fbx_calibrate_expectations: without cal_index there must be one calibration per setting");
+    FBX_TRY(calibrate_check(B, m, expect, std_err, cal_index, n_cal, cal_mean, cal_var, mean_out, err_out));
     if (cal_index)
         for (int64_t k = 0; k < m; ++k)
             FBX_REQUIRE(cal_index[k] >= 0 && cal_index[k] < n_cal, "fbx_calibrate_expectations: calibration index out of range");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(ensure_device());
     if (B * m == 0) return FBX_OK;
     const size_t n = (size_t)B * m;
-    DevBuf de, ds, di, dcm, dcv, dm, dr;
-    if ((rc = de.alloc(sizeof(double) * n)) || (rc = ds.alloc(sizeof(double) * n)) || (rc = di.alloc(sizeof(int32_t) * (m ? m : 1))) ||
-        (rc = dcm.alloc(sizeof(double) * (n_cal ? n_cal : 1))) || (rc = dcv.alloc(sizeof(double) * (n_cal ? n_cal : 1))) ||
-        (rc = dm.alloc(sizeof(double) * n)) || (rc = dr.alloc(sizeof(double) * n)))
-        return rc;
-    FBX_HIP(hipMemcpyAsync(de.p, expect, sizeof(double) * n, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(ds.p, std_err, sizeof(double) * n, hipMemcpyHostToDevice, stream()));
-    if (cal_index) FBX_HIP(hipMemcpyAsync(di.p, cal_index, sizeof(int32_t) * m, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(dcm.p, cal_mean, sizeof(double) * n_cal, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(dcv.p, cal_var, sizeof(double) * n_cal, hipMemcpyHostToDevice, stream()));
-    rc = fbx_calibrate_expectations_dev(B, m, de.as<double>(), ds.as<double>(), cal_index ? di.as<int32_t>() : nullptr, n_cal,
-                                        dcm.as<double>(), dcv.as<double>(), dm.as<double>(), dr.as<double>());
-    if (rc) return rc;
-    FBX_HIP(hipMemcpyAsync(mean_out, dm.p, sizeof(double) * n, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipMemcpyAsync(err_out, dr.p, sizeof(double) * n, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    HostIO io; double *de, *ds, *dcm, *dcv, *dm, *dr; int32_t* di = nullptr;
+    FBX_TRY(io.in(expect, n, &de)); FBX_TRY(io.in(std_err, n, &ds));
+    if (cal_index) FBX_TRY(io.in(cal_index, (size_t)m, &di));
+    FBX_TRY(io.in(cal_mean, (size_t)n_cal, &dcm)); FBX_TRY(io.in(cal_var, (size_t)n_cal, &dcv));
+    FBX_TRY(io.out(mean_out, n, &dm)); FBX_TRY(io.out(err_out, n, &dr));
+    FBX_TRY(fbx_calibrate_expectations_dev(B, m, de, ds, di, n_cal, dcm, dcv, dm, dr));
+    return io.finish();
 }
 
 int fbx_shots_to_moments_dev(int n_qubits, int64_t n_settings, int64_t n_shots, const uint8_t* d_bits,
                              const uint8_t* d_obs_mask, const double* d_coefs, int beta_prior,
                              double* d_mean_out, double* d_var_out) {
-    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 64, "fbx_shots_to_moments: n_qubits must be 1..64");
-    FBX_REQUIRE(n_settings >= 0 && n_shots >= 1, "fbx_shots_to_moments: need n_settings >= 0 and n_shots >= 1");
-    FBX_REQUIRE(n_settings == 0 || (d_bits && d_obs_mask && d_mean_out && d_var_out), "fbx_shots_to_moments: NULL buffer");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(shots_check(n_qubits, n_settings, n_shots, d_bits, d_obs_mask, d_mean_out, d_var_out));
+    FBX_TRY(ensure_device());
     if (n_settings == 0) return FBX_OK;
     // short records (below 16 KB per setting): a wavefront per setting, four settings per workgroup
     const bool per_wave = n_shots * n_qubits < 16384 && n_settings >= 4;
@@ -527,27 +529,16 @@ int fbx_shots_to_moments_dev(int n_qubits, int64_t n_settings, int64_t n_shots, 
 int fbx_shots_to_moments(int n_qubits, int64_t n_settings, int64_t n_shots, const uint8_t* bits,
                          const uint8_t* obs_mask, const double* coefs, int beta_prior,
                          double* mean_out, double* var_out) {
-    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 64, "fbx_shots_to_moments: n_qubits must be 1..64");
-    FBX_REQUIRE(n_settings >= 0 && n_shots >= 1, "fbx_shots_to_moments: need n_settings >= 0 and n_shots >= 1");
-    FBX_REQUIRE(n_settings == 0 || (bits && obs_mask && mean_out && var_out), "fbx_shots_to_moments: NULL buffer");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(shots_check(n_qubits, n_settings, n_shots, bits, obs_mask, mean_out, var_out));
+    FBX_TRY(ensure_device());
     if (n_settings == 0) return FBX_OK;
-    const size_t nb = (size_t)n_settings * n_shots * n_qubits, nm = (size_t)n_settings * n_qubits;
-    DevBuf db, dm, dc, dmean, dvar;
-    if ((rc = db.alloc(nb)) || (rc = dm.alloc(nm)) || (rc = dc.alloc(sizeof(double) * n_settings)) ||
-        (rc = dmean.alloc(sizeof(double) * n_settings)) || (rc = dvar.alloc(sizeof(double) * n_settings)))
-        return rc;
-    FBX_HIP(hipMemcpyAsync(db.p, bits, nb, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(dm.p, obs_mask, nm, hipMemcpyHostToDevice, stream()));
-    if (coefs) FBX_HIP(hipMemcpyAsync(dc.p, coefs, sizeof(double) * n_settings, hipMemcpyHostToDevice, stream()));
-    rc = fbx_shots_to_moments_dev(n_qubits, n_settings, n_shots, db.as<uint8_t>(), dm.as<uint8_t>(),
-                                  coefs ? dc.as<double>() : nullptr, beta_prior, dmean.as<double>(), dvar.as<double>());
-    if (rc) return rc;
-    FBX_HIP(hipMemcpyAsync(mean_out, dmean.p, sizeof(double) * n_settings, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipMemcpyAsync(var_out, dvar.p, sizeof(double) * n_settings, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    const size_t ns = (size_t)n_settings;
+    HostIO io; uint8_t *db, *dm; double *dc = nullptr, *dmean, *dvar;
+    FBX_TRY(io.in(bits, ns * n_shots * n_qubits, &db)); FBX_TRY(io.in(obs_mask, ns * n_qubits, &dm));
+    if (coefs) FBX_TRY(io.in(coefs, ns, &dc));
+    FBX_TRY(io.out(mean_out, ns, &dmean)); FBX_TRY(io.out(var_out, ns, &dvar));
+    FBX_TRY(fbx_shots_to_moments_dev(n_qubits, n_settings, n_shots, db, dm, dc, beta_prior, dmean, dvar));
+    return io.finish();
 }
 
 int fbx_dfe_estimate(int n_qubits, int kind, int64_t B, int64_t m, const double* expect, const double* std_err,
@@ -556,33 +547,23 @@ int fbx_dfe_estimate(int n_qubits, int kind, int64_t B, int64_t m, const double*
     FBX_REQUIRE(kind == FBX_KIND_STATE || kind == FBX_KIND_PROCESS, "fbx_dfe_estimate: kind must be FBX_KIND_STATE or FBX_KIND_PROCESS");
     FBX_REQUIRE(B >= 0 && m >= 1, "fbx_dfe_estimate: need B >= 0 and m >= 1");
     FBX_REQUIRE(B == 0 || (expect && std_err && mean_out && err_out), "fbx_dfe_estimate: NULL buffer");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const size_t n = (size_t)B * m;
-    DevBuf de, ds, dm, dr;
-    if ((rc = de.alloc(sizeof(double) * n)) || (rc = ds.alloc(sizeof(double) * n)) ||
-        (rc = dm.alloc(sizeof(double) * B)) || (rc = dr.alloc(sizeof(double) * B)))
-        return rc;
-    FBX_HIP(hipMemcpyAsync(de.p, expect, sizeof(double) * n, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(ds.p, std_err, sizeof(double) * n, hipMemcpyHostToDevice, stream()));
+    HostIO io; double *de, *ds, *dm, *dr;
+    FBX_TRY(io.in(expect, n, &de)); FBX_TRY(io.in(std_err, n, &ds));
+    FBX_TRY(io.out(mean_out, (size_t)B, &dm)); FBX_TRY(io.out(err_out, (size_t)B, &dr));
     const unsigned grid = (unsigned)(B < 65536 ? B : 65536);
     hipLaunchKernelGGL(dfe_kernel, dim3(grid), dim3(64), 0, stream(), n_qubits, kind == FBX_KIND_PROCESS ? 1 : 0,
-                       (long long)B, (long long)m, de.as<double>(), ds.as<double>(), dm.as<double>(), dr.as<double>());
+                       (long long)B, (long long)m, de, ds, dm, dr);
     FBX_HIP(hipGetLastError());
-    FBX_HIP(hipMemcpyAsync(mean_out, dm.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipMemcpyAsync(err_out, dr.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    return io.finish();
 }
 
 int fbx_beta_resample_dev(int64_t n, int64_t R, const double* d_expect, const double* d_counts, double prior_counts,
                           uint64_t seed, double* d_out, double* d_counts_out) {
-    FBX_REQUIRE(n >= 0 && R >= 0, "fbx_beta_resample: need n >= 0 and R >= 0");
-    FBX_REQUIRE(prior_counts > 0.0, "fbx_beta_resample: prior_counts must be positive");
-    FBX_REQUIRE(n * R == 0 || (d_expect && d_counts && d_out), "fbx_beta_resample: NULL buffer");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(beta_resample_check(n, R, d_expect, d_counts, prior_counts, d_out));
+    FBX_TRY(ensure_device());
     if (n * R == 0) return FBX_OK;
     const long long total = (long long)n * R, want = (total + 255) / 256;
     const unsigned grid = (unsigned)(want < 256 * 32 ? want : 256 * 32);
@@ -594,23 +575,13 @@ int fbx_beta_resample_dev(int64_t n, int64_t R, const double* d_expect, const do
 
 int fbx_beta_resample(int64_t n, int64_t R, const double* expect, const double* counts, double prior_counts,
                       uint64_t seed, double* out) {
-    FBX_REQUIRE(n >= 0 && R >= 0, "fbx_beta_resample: need n >= 0 and R >= 0");
-    FBX_REQUIRE(prior_counts > 0.0, "fbx_beta_resample: prior_counts must be positive");
-    FBX_REQUIRE(n * R == 0 || (expect && counts && out), "fbx_beta_resample: NULL buffer");
-    int rc = ensure_device();
-    if (rc) return rc;
+    FBX_TRY(beta_resample_check(n, R, expect, counts, prior_counts, out));
+    FBX_TRY(ensure_device());
     if (n * R == 0) return FBX_OK;
-    DevBuf de, dc, dout;
-    if ((rc = de.alloc(sizeof(double) * n)) || (rc = dc.alloc(sizeof(double) * n)) ||
-        (rc = dout.alloc(sizeof(double) * n * R)))
-        return rc;
-    FBX_HIP(hipMemcpyAsync(de.p, expect, sizeof(double) * n, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(dc.p, counts, sizeof(double) * n, hipMemcpyHostToDevice, stream()));
-    rc = fbx_beta_resample_dev(n, R, de.as<double>(), dc.as<double>(), prior_counts, seed, dout.as<double>(), nullptr);
-    if (rc) return rc;
-    FBX_HIP(hipMemcpyAsync(out, dout.p, sizeof(double) * n * R, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    HostIO io; double *de, *dc, *dout;
+    FBX_TRY(io.in(expect, (size_t)n, &de)); FBX_TRY(io.in(counts, (size_t)n, &dc)); FBX_TRY(io.out(out, (size_t)n * R, &dout));
+    FBX_TRY(fbx_beta_resample_dev(n, R, de, dc, prior_counts, seed, dout, nullptr));
+    return io.finish();
 }
 
 }  // extern "C"

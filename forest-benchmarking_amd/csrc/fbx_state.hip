@@ -1611,37 +1611,6 @@ static int launch_proj_big(int64_t B, const double* rho, double* out) {
 }
 
 namespace {
-struct HostIO {
-    std::vector<DevBuf*> bufs;
-    ~HostIO() { for (auto* b : bufs) delete b; }
-    template <class T> int in(const T* host, size_t count, T** dev) {
-        auto* b = new DevBuf(); bufs.push_back(b);
-        int rc = b->alloc(sizeof(T) * count);
-        if (rc) return rc;
-        if (host && count) {
-            hipError_t e = hipMemcpyAsync(b->p, host, sizeof(T) * count, hipMemcpyHostToDevice, stream());
-            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(H2D)", __FILE__, __LINE__);
-        }
-        *dev = b->as<T>();
-        return FBX_OK;
-    }
-    template <class T> int out(size_t count, T** dev) {
-        auto* b = new DevBuf(); bufs.push_back(b);
-        int rc = b->alloc(sizeof(T) * count);
-        if (rc) return rc;
-        *dev = b->as<T>();
-        return FBX_OK;
-    }
-    template <class T> int back(T* host, const T* dev, size_t count) {
-        if (!host || !count) return FBX_OK;
-        hipError_t e = hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, stream());
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(D2H)", __FILE__, __LINE__);
-        return FBX_OK;
-    }
-    int sync() { FBX_HIP(hipStreamSynchronize(stream())); return FBX_OK; }
-};
-#define FBX_TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
-
 #define FBX_DISPATCH_NQ(n, KERNEL, lds, B, ...)                                                    \
     do {                                                                                           \
         if ((n) == 1) hipLaunchKernelGGL(KERNEL<1>, dim3((unsigned)(B)), dim3(64), (lds), stream(), __VA_ARGS__); \
@@ -1717,10 +1686,9 @@ int fbx_linv_state(const fbx_design* design, int64_t B, const double* expect, do
     if (B == 0) return FBX_OK;
     const size_t m = design->dev.m, D = design->dev.D;
     HostIO io; double *de, *dr;
-    FBX_TRY(io.in(expect, m * B, &de)); FBX_TRY(io.out(D * 2 * B, &dr));
+    FBX_TRY(io.in(expect, m * B, &de)); FBX_TRY(io.out(rho_out, D * 2 * B, &dr));
     FBX_TRY(fbx_linv_state_dev(design, B, de, dr));
-    FBX_TRY(io.back(rho_out, dr, D * 2 * B));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_mle_state_dev(const fbx_design* design, int64_t B, const double* d_expect, const double* d_counts,
@@ -1766,11 +1734,9 @@ int fbx_mle_state(const fbx_design* design, int64_t B, const double* expect, con
     const size_t m = design->dev.m, D = design->dev.D;
     HostIO io; double *de, *dc, *dr; int32_t *di, *dh;
     FBX_TRY(io.in(expect, m * B, &de)); FBX_TRY(io.in(counts, m * B, &dc));
-    FBX_TRY(io.out(D * 2 * B, &dr)); FBX_TRY(io.out((size_t)B, &di)); FBX_TRY(io.out((size_t)B, &dh));
+    FBX_TRY(io.out(rho_out, D * 2 * B, &dr)); FBX_TRY(io.out(iters_out, (size_t)B, &di)); FBX_TRY(io.out(hit_max_out, (size_t)B, &dh));
     FBX_TRY(fbx_mle_state_dev(design, B, de, dc, epsilon, entropy_penalty, beta, tol, maxiter, dr, di, dh));
-    FBX_TRY(io.back(rho_out, dr, D * 2 * B)); FBX_TRY(io.back(iters_out, di, (size_t)B));
-    FBX_TRY(io.back(hit_max_out, dh, (size_t)B));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_r_operator_dev(const fbx_design* design, int64_t B, const double* d_rho, const double* d_expect, double* d_r_out) {
@@ -1793,10 +1759,9 @@ int fbx_r_operator(const fbx_design* design, int64_t B, const double* rho, const
     if (B == 0) return FBX_OK;
     const size_t m = design->dev.m, D = design->dev.D;
     HostIO io; double *dr, *de, *dout;
-    FBX_TRY(io.in(rho, D * 2 * B, &dr)); FBX_TRY(io.in(expect, m * B, &de)); FBX_TRY(io.out(D * 2 * B, &dout));
+    FBX_TRY(io.in(rho, D * 2 * B, &dr)); FBX_TRY(io.in(expect, m * B, &de)); FBX_TRY(io.out(r_out, D * 2 * B, &dout));
     FBX_TRY(fbx_r_operator_dev(design, B, dr, de, dout));
-    FBX_TRY(io.back(r_out, dout, D * 2 * B));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_state_log_likelihood_dev(const fbx_design* design, int64_t B, const double* d_rho, const double* d_expect,
@@ -1821,10 +1786,9 @@ int fbx_state_log_likelihood(const fbx_design* design, int64_t B, const double* 
     const size_t m = design->dev.m, D = design->dev.D;
     HostIO io; double *dr, *de, *dc, *dout;
     FBX_TRY(io.in(rho, D * 2 * B, &dr)); FBX_TRY(io.in(expect, m * B, &de)); FBX_TRY(io.in(counts, m * B, &dc));
-    FBX_TRY(io.out((size_t)B, &dout));
+    FBX_TRY(io.out(ll_out, (size_t)B, &dout));
     FBX_TRY(fbx_state_log_likelihood_dev(design, B, dr, de, dc, dout));
-    FBX_TRY(io.back(ll_out, dout, (size_t)B));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_matmul_dev(int N, int64_t B, const double* d_a, int conj_t_a, const double* d_scale, const double* d_b, int conj_t_b,
@@ -1850,10 +1814,9 @@ int fbx_matmul(int N, int64_t B, const double* a, int conj_t_a, const double* sc
     HostIO io; double *da, *db, *ds = nullptr, *dout;
     FBX_TRY(io.in(a, nn, &da)); FBX_TRY(io.in(b, nn, &db));
     if (scale) FBX_TRY(io.in(scale, (size_t)N * B, &ds));
-    FBX_TRY(io.out(nn, &dout));
+    FBX_TRY(io.out(out, nn, &dout));
     FBX_TRY(fbx_matmul_dev(N, B, da, conj_t_a, ds, db, conj_t_b, dout));
-    FBX_TRY(io.back(out, dout, nn));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_eigh_dev(int N, int64_t B, const double* d_a, double* d_w_out, double* d_v_out) {
@@ -1892,12 +1855,10 @@ int fbx_eigh(int N, int64_t B, const double* a, double* w_out, double* v_out) {
     if (N > 64) Np = N + (N & 1);           // the HBM-resident solver takes any even size
     if (Np == N) {
         const size_t nn = (size_t)N * N * 2 * B;
-        HostIO io; double *da, *dw, *dv = nullptr;
-        FBX_TRY(io.in(a, nn, &da)); FBX_TRY(io.out((size_t)N * B, &dw));
-        if (v_out) FBX_TRY(io.out(nn, &dv));
+        HostIO io; double *da, *dw, *dv;
+        FBX_TRY(io.in(a, nn, &da)); FBX_TRY(io.out(w_out, (size_t)N * B, &dw)); FBX_TRY(io.out_opt(v_out, nn, &dv));
         FBX_TRY(fbx_eigh_dev(N, B, da, dw, dv));
-        FBX_TRY(io.back(w_out, dw, (size_t)N * B)); FBX_TRY(io.back(v_out, dv, nn));
-        return io.sync();
+        return io.finish();
     }
     // Any other size (e.g. a qutrit's 3 x 3, a 9 x 9 Choi matrix): embedded in the next power of two
     // with zero rows / columns.  The padding coordinates are decoupled and stay so exactly (a pivot
@@ -1911,10 +1872,10 @@ int fbx_eigh(int N, int64_t B, const double* a, double* w_out, double* v_out) {
             memcpy(&ap[(b * np2 + (size_t)r * Np) * 2], &a[((size_t)b * N * N + (size_t)r * N) * 2], sizeof(double) * 2 * N);
     {
         HostIO io; double *da, *dw, *dv;
-        FBX_TRY(io.in(ap.data(), ap.size(), &da)); FBX_TRY(io.out(wp.size(), &dw)); FBX_TRY(io.out(vp.size(), &dv));
+        FBX_TRY(io.in(ap.data(), ap.size(), &da));
+        FBX_TRY(io.out(wp.data(), wp.size(), &dw)); FBX_TRY(io.out(vp.data(), vp.size(), &dv));
         FBX_TRY(fbx_eigh_dev(Np, B, da, dw, dv));
-        FBX_TRY(io.back(wp.data(), dw, wp.size())); FBX_TRY(io.back(vp.data(), dv, vp.size()));
-        FBX_TRY(io.sync());
+        FBX_TRY(io.finish());
     }
     const double nan = std::numeric_limits<double>::quiet_NaN();
     for (int64_t b = 0; b < B; ++b) {
@@ -2034,10 +1995,9 @@ int fbx_choi2kraus(int n_qubits, int64_t B, const double* choi, double tol, doub
     if (B == 0) return FBX_OK;
     const size_t D = (size_t)1 << (2 * n_qubits), nn = D * D * 2 * (size_t)B;
     HostIO io; double *dc, *dk; int32_t* dn;
-    FBX_TRY(io.in(choi, nn, &dc)); FBX_TRY(io.out(nn, &dk)); FBX_TRY(io.out((size_t)B, &dn));
+    FBX_TRY(io.in(choi, nn, &dc)); FBX_TRY(io.out(kraus_out, nn, &dk)); FBX_TRY(io.out(count_out, (size_t)B, &dn));
     FBX_TRY(fbx_choi2kraus_dev(n_qubits, B, dc, tol, dk, dn));
-    FBX_TRY(io.back(kraus_out, dk, nn)); FBX_TRY(io.back(count_out, dn, (size_t)B));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_proj_state_physical_dev(int n_qubits, int64_t B, const double* d_rho, double* d_out) {
@@ -2059,10 +2019,9 @@ int fbx_proj_state_physical(int n_qubits, int64_t B, const double* rho, double* 
     if (B == 0) return FBX_OK;
     const size_t d = (size_t)1 << n_qubits, D = d * d;
     HostIO io; double *dr, *dout;
-    FBX_TRY(io.in(rho, D * 2 * B, &dr)); FBX_TRY(io.out(D * 2 * B, &dout));
+    FBX_TRY(io.in(rho, D * 2 * B, &dr)); FBX_TRY(io.out(out, D * 2 * B, &dout));
     FBX_TRY(fbx_proj_state_physical_dev(n_qubits, B, dr, dout));
-    FBX_TRY(io.back(out, dout, D * 2 * B));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_state_measures_dev(int n_qubits, int64_t B, const double* d_rho, const double* d_sigma, double* d_purity_out,
@@ -2086,16 +2045,12 @@ int fbx_state_measures(int n_qubits, int64_t B, const double* rho, const double*
     FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const size_t d = (size_t)1 << n_qubits, D = d * d;
-    HostIO io; double *dr, *ds, *dp = nullptr, *df = nullptr, *dt = nullptr, *dh = nullptr;
+    HostIO io; double *dr, *ds, *dp, *df, *dt, *dh;
     FBX_TRY(io.in(rho, D * 2 * B, &dr)); FBX_TRY(io.in(sigma, D * 2 * B, &ds));
-    if (purity_out) FBX_TRY(io.out((size_t)B, &dp));
-    if (fidelity_out) FBX_TRY(io.out((size_t)B, &df));
-    if (trace_dist_out) FBX_TRY(io.out((size_t)B, &dt));
-    if (hs_ip_out) FBX_TRY(io.out((size_t)B, &dh));
+    FBX_TRY(io.out_opt(purity_out, (size_t)B, &dp)); FBX_TRY(io.out_opt(fidelity_out, (size_t)B, &df));
+    FBX_TRY(io.out_opt(trace_dist_out, (size_t)B, &dt)); FBX_TRY(io.out_opt(hs_ip_out, (size_t)B, &dh));
     FBX_TRY(fbx_state_measures_dev(n_qubits, B, dr, ds, dp, df, dt, dh));
-    FBX_TRY(io.back(purity_out, dp, (size_t)B)); FBX_TRY(io.back(fidelity_out, df, (size_t)B));
-    FBX_TRY(io.back(trace_dist_out, dt, (size_t)B)); FBX_TRY(io.back(hs_ip_out, dh, (size_t)B));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_pauli_vector_dev(int n_qubits, int64_t B, const double* d_rho, double* d_out) {
@@ -2116,10 +2071,9 @@ int fbx_pauli_vector(int n_qubits, int64_t B, const double* rho, double* out) {
     if (B == 0) return FBX_OK;
     const size_t DD = (size_t)1 << (2 * n_qubits);
     HostIO io; double *dr, *dout;
-    FBX_TRY(io.in(rho, DD * 2 * B, &dr)); FBX_TRY(io.out(DD * B, &dout));
+    FBX_TRY(io.in(rho, DD * 2 * B, &dr)); FBX_TRY(io.out(out, DD * B, &dout));
     FBX_TRY(fbx_pauli_vector_dev(n_qubits, B, dr, dout));
-    FBX_TRY(io.back(out, dout, DD * B));
-    return io.sync();
+    return io.finish();
 }
 
 }  // extern "C"

@@ -1423,39 +1423,6 @@ int linv_process3_launch(const fbx_design* des, int64_t B, const double* d_expec
 
 using namespace fbx;
 
-namespace {
-struct HostIO {     // host <-> device staging for the host-pointer entry points
-    std::vector<DevBuf*> bufs;
-    ~HostIO() { for (auto* b : bufs) delete b; }
-    template <class T> int in(const T* host, size_t count, T** dev) {
-        auto* b = new DevBuf(); bufs.push_back(b);
-        int rc = b->alloc(sizeof(T) * count);
-        if (rc) return rc;
-        if (host && count) {
-            hipError_t e = hipMemcpyAsync(b->p, host, sizeof(T) * count, hipMemcpyHostToDevice, stream());
-            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(H2D)", __FILE__, __LINE__);
-        }
-        *dev = b->as<T>();
-        return FBX_OK;
-    }
-    template <class T> int out(size_t count, T** dev) {
-        auto* b = new DevBuf(); bufs.push_back(b);
-        int rc = b->alloc(sizeof(T) * count);
-        if (rc) return rc;
-        *dev = b->as<T>();
-        return FBX_OK;
-    }
-    template <class T> int back(T* host, const T* dev, size_t count) {
-        if (!host || !count) return FBX_OK;
-        hipError_t e = hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, stream());
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(D2H)", __FILE__, __LINE__);
-        return FBX_OK;
-    }
-    int sync() { FBX_HIP(hipStreamSynchronize(stream())); return FBX_OK; }
-};
-#define FBX_TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
-}  // namespace
-
 // ---- Kraus bookkeeping for batches (operator_tools/compose_superoperators.py:7-44) and the Pauli twirl
 // (channel_approximation.py:31-49).  Output operator p = j * K2 + l (the reference's list order: k1 outer,
 // k2 inner) is kron(k2[l], k1[j]) for the tensor form, k2[l] . k1[j] for the composition; one output
@@ -1549,10 +1516,9 @@ int fbx_kraus_pairs(int tensor, int64_t B, int K2, int rows2, int cols2, int K1,
     const size_t ro = tensor ? (size_t)rows2 * rows1 : rows2, co = tensor ? (size_t)cols2 * cols1 : cols1;
     const size_t no = (size_t)B * K1 * K2 * ro * co * 2;
     HostIO io; double *d2, *d1, *dout;
-    FBX_TRY(io.in(k2, n2, &d2)); FBX_TRY(io.in(k1, n1, &d1)); FBX_TRY(io.out(no, &dout));
+    FBX_TRY(io.in(k2, n2, &d2)); FBX_TRY(io.in(k1, n1, &d1)); FBX_TRY(io.out(out, no, &dout));
     FBX_TRY(fbx_kraus_pairs_dev(tensor, B, K2, rows2, cols2, K1, rows1, cols1, d2, d1, dout));
-    FBX_TRY(io.back(out, dout, no));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_pauli_twirl_chi_dev(int64_t B, int D, const double* d_chi, double* d_out) {
@@ -1574,10 +1540,9 @@ int fbx_pauli_twirl_chi(int64_t B, int D, const double* chi, double* out) {
     if (B == 0) return FBX_OK;
     const size_t n = (size_t)B * D * D * 2;
     HostIO io; double *dc, *dout;
-    FBX_TRY(io.in(chi, n, &dc)); FBX_TRY(io.out(n, &dout));
+    FBX_TRY(io.in(chi, n, &dc)); FBX_TRY(io.out(out, n, &dout));
     FBX_TRY(fbx_pauli_twirl_chi_dev(B, D, dc, dout));
-    FBX_TRY(io.back(out, dout, n));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_linv_process_dev(const fbx_design* design, int64_t B, const double* d_expect, double* d_choi_out) {
@@ -1602,10 +1567,9 @@ int fbx_linv_process(const fbx_design* design, int64_t B, const double* expect, 
     if (B == 0) return FBX_OK;
     const size_t m = design->dev.m, D = design->dev.D;
     HostIO io; double *de, *dout;
-    FBX_TRY(io.in(expect, m * B, &de)); FBX_TRY(io.out(D * D * 2 * B, &dout));
+    FBX_TRY(io.in(expect, m * B, &de)); FBX_TRY(io.out(choi_out, D * D * 2 * B, &dout));
     FBX_TRY(fbx_linv_process_dev(design, B, de, dout));
-    FBX_TRY(io.back(choi_out, dout, D * D * 2 * B));
-    return io.sync();
+    return io.finish();
 }
 
 static int convert_check(int from_rep, int to_rep, int n_qubits, int64_t B, const void* in, int K, const void* out) {
@@ -1692,10 +1656,9 @@ int fbx_partial_trace(int dim_a, int dim_b, int keep, int64_t B, const double* i
     if (B == 0) return FBX_OK;
     const size_t N = (size_t)dim_a * dim_b, n = keep == 0 ? dim_a : dim_b;
     HostIO io; double *d_in, *d_out;
-    FBX_TRY(io.in(in, N * N * 2 * B, &d_in)); FBX_TRY(io.out(n * n * 2 * B, &d_out));
+    FBX_TRY(io.in(in, N * N * 2 * B, &d_in)); FBX_TRY(io.out(out, n * n * 2 * B, &d_out));
     FBX_TRY(fbx_partial_trace_dev(dim_a, dim_b, keep, B, d_in, d_out));
-    FBX_TRY(io.back(out, d_out, n * n * 2 * B));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_convert_general_dev(int from_rep, int to_rep, int dim, int64_t B, const double* d_in, int K, double* d_out) {
@@ -1716,10 +1679,9 @@ int fbx_convert_general(int from_rep, int to_rep, int dim, int64_t B, const doub
     const size_t D = (size_t)dim * dim;
     const size_t n_in = (from_rep == FBX_REP_KRAUS ? (size_t)K * D : D * D) * 2 * B, n_out = D * D * 2 * B;
     HostIO io; double *d_in, *d_out;
-    FBX_TRY(io.in(in, n_in, &d_in)); FBX_TRY(io.out(n_out, &d_out));
+    FBX_TRY(io.in(in, n_in, &d_in)); FBX_TRY(io.out(out, n_out, &d_out));
     FBX_TRY(fbx_convert_general_dev(from_rep, to_rep, dim, B, d_in, K, d_out));
-    FBX_TRY(io.back(out, d_out, n_out));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_convert(int from_rep, int to_rep, int n_qubits, int64_t B, const double* in, int K, double* out) {
@@ -1729,10 +1691,9 @@ int fbx_convert(int from_rep, int to_rep, int n_qubits, int64_t B, const double*
     const size_t d = (size_t)1 << n_qubits, D = d * d;
     const size_t n_in = (from_rep == FBX_REP_KRAUS ? (size_t)K * D : D * D) * 2 * B, n_out = D * D * 2 * B;
     HostIO io; double *d_in, *d_out;
-    FBX_TRY(io.in(in, n_in, &d_in)); FBX_TRY(io.out(n_out, &d_out));
+    FBX_TRY(io.in(in, n_in, &d_in)); FBX_TRY(io.out(out, n_out, &d_out));
     FBX_TRY(fbx_convert_dev(from_rep, to_rep, n_qubits, B, d_in, K, d_out));
-    FBX_TRY(io.back(out, d_out, n_out));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_kraus_sweep_dev(int n_qubits, int64_t B, int K, const double* d_kraus, const double* d_ptm_ref,
@@ -1779,17 +1740,13 @@ int fbx_kraus_sweep(int n_qubits, int64_t B, int K, const double* kraus, const d
                                    ptm_out ? ptm_out + om : nullptr, chi_out ? chi_out + om : nullptr, fid_out ? fid_out + lo : nullptr);
         });
     }
-    HostIO io; double *dk, *dr = nullptr, *dc = nullptr, *dp = nullptr, *dx = nullptr, *df = nullptr;
+    HostIO io; double *dk, *dr = nullptr, *dc, *dp, *dx, *df;
     FBX_TRY(io.in(kraus, (size_t)K * D * 2 * B, &dk));
     if (ptm_ref) FBX_TRY(io.in(ptm_ref, D * D * 2, &dr));
-    if (choi_out) FBX_TRY(io.out(nm, &dc));
-    if (ptm_out) FBX_TRY(io.out(nm, &dp));
-    if (chi_out) FBX_TRY(io.out(nm, &dx));
-    if (fid_out) FBX_TRY(io.out((size_t)B, &df));
+    FBX_TRY(io.out_opt(choi_out, nm, &dc)); FBX_TRY(io.out_opt(ptm_out, nm, &dp));
+    FBX_TRY(io.out_opt(chi_out, nm, &dx)); FBX_TRY(io.out_opt(fid_out, (size_t)B, &df));
     FBX_TRY(fbx_kraus_sweep_dev(n_qubits, B, K, dk, dr, dc, dp, dx, df));
-    FBX_TRY(io.back(choi_out, dc, nm)); FBX_TRY(io.back(ptm_out, dp, nm)); FBX_TRY(io.back(chi_out, dx, nm));
-    FBX_TRY(io.back(fid_out, df, (size_t)B));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_proj_choi_dev(int proj_kind, int n_qubits, int64_t B, const double* d_choi, double* d_out, int32_t* d_iters_out) {
@@ -1822,10 +1779,9 @@ int fbx_proj_choi(int proj_kind, int n_qubits, int64_t B, const double* choi, do
     if (B == 0) return FBX_OK;
     const size_t d = (size_t)1 << n_qubits, D = d * d, nm = D * D * 2 * B;
     HostIO io; double *d_in, *d_out; int32_t* d_it;
-    FBX_TRY(io.in(choi, nm, &d_in)); FBX_TRY(io.out(nm, &d_out)); FBX_TRY(io.out((size_t)B, &d_it));
+    FBX_TRY(io.in(choi, nm, &d_in)); FBX_TRY(io.out(out, nm, &d_out)); FBX_TRY(io.out(iters_out, (size_t)B, &d_it));
     FBX_TRY(fbx_proj_choi_dev(proj_kind, n_qubits, B, d_in, d_out, d_it));
-    FBX_TRY(io.back(out, d_out, nm)); FBX_TRY(io.back(iters_out, d_it, (size_t)B));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_apply_choi_dev(int n_qubits, int64_t B, const double* d_choi, const double* d_rho, double* d_out) {
@@ -1847,10 +1803,9 @@ int fbx_apply_choi(int n_qubits, int64_t B, const double* choi, const double* rh
     if (B == 0) return FBX_OK;
     const size_t d = (size_t)1 << n_qubits, D = d * d;
     HostIO io; double *dc, *dr, *dout;
-    FBX_TRY(io.in(choi, D * D * 2 * B, &dc)); FBX_TRY(io.in(rho, D * 2 * B, &dr)); FBX_TRY(io.out(D * 2 * B, &dout));
+    FBX_TRY(io.in(choi, D * D * 2 * B, &dc)); FBX_TRY(io.in(rho, D * 2 * B, &dr)); FBX_TRY(io.out(out, D * 2 * B, &dout));
     FBX_TRY(fbx_apply_choi_dev(n_qubits, B, dc, dr, dout));
-    FBX_TRY(io.back(out, dout, D * 2 * B));
-    return io.sync();
+    return io.finish();
 }
 
 int fbx_process_fidelity_dev(int n_qubits, int64_t B, const double* d_ptm0, const double* d_ptm1, double* d_fe_out, double* d_fp_out) {
@@ -1872,10 +1827,9 @@ int fbx_process_fidelity(int n_qubits, int64_t B, const double* ptm0, const doub
     const size_t d = (size_t)1 << n_qubits, D = d * d, nm = D * D * 2 * B;
     HostIO io; double *da, *db, *dfe, *dfp;
     FBX_TRY(io.in(ptm0, nm, &da)); FBX_TRY(io.in(ptm1, nm, &db));
-    FBX_TRY(io.out((size_t)B, &dfe)); FBX_TRY(io.out((size_t)B, &dfp));
+    FBX_TRY(io.out(fe_out, (size_t)B, &dfe)); FBX_TRY(io.out(fp_out, (size_t)B, &dfp));
     FBX_TRY(fbx_process_fidelity_dev(n_qubits, B, da, db, dfe, dfp));
-    FBX_TRY(io.back(fe_out, dfe, (size_t)B)); FBX_TRY(io.back(fp_out, dfp, (size_t)B));
-    return io.sync();
+    return io.finish();
 }
 
 }  // extern "C"

@@ -95,7 +95,7 @@ pgdb_cost_grad_kernel(DesignDev des, long long B, const double* __restrict__ nve
     FBX_WAVE_SYNC();
     choi_to_pauli_real<NQ>(L.choi.Mw, L.Rb, lane);
     FBX_WAVE_SYNC();
-    predict_table<NQ>(L.Rb, L.Cl, L.Test, S, lane);
+    predict_table<NQ, 3>(L.Rb, L.Cl, L.Test, S, lane);
     double* Wt = L.Tupd;                        // [S][D]
     for (int idx = lane; idx < D * S; idx += 64) Wt[idx] = 0.0;
     FBX_WAVE_SYNC();
@@ -120,22 +120,7 @@ pgdb_cost_grad_kernel(DesignDev des, long long B, const double* __restrict__ nve
     if (lane == 0 && cost_out) cost_out[item] = acc;
     FBX_WAVE_SYNC();
     if (!grad_out) return;
-    {
-        constexpr int JB = (D * D + 63) / 64;
-        const int i = lane % D, j0 = (lane / D) * JB;
-        if (j0 < D) {
-            double a[JB];
-#pragma unroll
-            for (int r = 0; r < JB; ++r) a[r] = 0.0;
-            for (int st = 0; st < S; ++st) {
-                const double w = Wt[st * D + i];
-#pragma unroll
-                for (int r = 0; r < JB; ++r) a[r] = fma(w, L.Cl[st * D + j0 + r], a[r]);
-            }
-#pragma unroll
-            for (int r = 0; r < JB; ++r) L.Rb[(j0 + r) * D + i] = -a[r] / (double)(d * d);
-        }
-    }
+    grad_coefficients<NQ>(Wt, L.Cl, L.Rb, S, lane);
     FBX_WAVE_SYNC();
     const Blk grad = pauli_real_to_choi_blk<NQ>(L.Rb, L.choi.Mw, lane);
     if (lane < NACT) {

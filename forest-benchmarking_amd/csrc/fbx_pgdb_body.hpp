@@ -89,23 +89,114 @@ __host__ __device__ constexpr bool pgdb_ct_fits(int S) {
 // ...: per state D/2 broadcast 16-byte loads of the state's Bloch vector (Ct is [S][D]) and D FMAs, all
 // straight-line code -- the D x S loop over (s, i) pairs with two 8-byte loads per FMA it replaces
 // took 16k cycles per call for the 36-state design.
-template <int NQ>
+//
+// U = states per trip.  A lone wavefront has nobody to hide an LDS round trip behind, and the scheduler, left alone, sinks half of a
+// state's loads in between its FMAs: five full `s_waitcnt lgkmcnt(0)` per state (profiles/r07/outer_phases_before.txt).  With
+// U > 1 the Bloch vectors of U states (s, s + STEP, ...) are ALL requested before the first FMA -- a scheduling barrier keeps
+// them there -- so a trip pays one round trip, not five per state; the data arrive in order while the FMA chains run.  Every
+// accumulator sees the operands it saw before in the order it saw them (acc0 / acc1 per state, j ascending, acc0 + acc1): same
+// bits.  U = 1 is the plain loop, one state per trip and no barrier (the register-capped two-waves kernel keeps it: DESIGN.md 4.2).
+template <int NQ, int U>
+__device__ __forceinline__ void predict_states(const double* r, const double* Ct, double* T, int s, int i) {
+    constexpr int D = ChoiLds<NQ>::D, STEP = 64 / D;
+    double2 c[U][D / 2];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const double2* c2 = reinterpret_cast<const double2*>(Ct + (size_t)(s + u * STEP) * D);
+#pragma unroll
+        for (int j = 0; j < D / 2; ++j) c[u][j] = c2[j];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+        for (int j = 0; j < D / 2; ++j) {
+            acc0 = fma(r[2 * j], c[u][j].x, acc0);
+            acc1 = fma(r[2 * j + 1], c[u][j].y, acc1);
+        }
+        T[(s + u * STEP) * D + i] = acc0 + acc1;
+    }
+}
+template <int NQ, int U = 1>
 __device__ void predict_table(const double* Rb, const double* Ct, double* T, int S, int lane) {
     constexpr int D = ChoiLds<NQ>::D, STEP = 64 / D;
+    static_assert(U >= 1 && U <= 3, "one, two or three states per trip");
     const int i = lane % D, q = lane / D;
     double r[D];
 #pragma unroll
     for (int j = 0; j < D; ++j) r[j] = Rb[j * D + i];
-    for (int s = q; s < S; s += STEP) {
-        const double2* c2 = reinterpret_cast<const double2*>(Ct + (size_t)s * D);
-        double acc0 = 0.0, acc1 = 0.0;
-#pragma unroll
-        for (int j = 0; j < D / 2; ++j) {
-            const double2 c = c2[j];
-            acc0 = fma(r[2 * j], c.x, acc0);
-            acc1 = fma(r[2 * j + 1], c.y, acc1);
+    if constexpr (U > 1) {
+        int s = q;
+        for (; s + (U - 1) * STEP < S; s += U * STEP) predict_states<NQ, U>(r, Ct, T, s, i);
+        // the one or two states left over: a pair in one trip, then a single one
+        if constexpr (U == 3) {
+            if (s + STEP < S) { predict_states<NQ, 2>(r, Ct, T, s, i); s += 2 * STEP; }
         }
-        T[s * D + i] = acc0 + acc1;
+        if (s < S) predict_states<NQ, 1>(r, Ct, T, s, i);
+    } else {
+        for (int s = q; s < S; s += STEP) {
+            const double2* c2 = reinterpret_cast<const double2*>(Ct + (size_t)s * D);
+            double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+            for (int j = 0; j < D / 2; ++j) {
+                const double2 c = c2[j];
+                acc0 = fma(r[2 * j], c.x, acc0);
+                acc1 = fma(r[2 * j + 1], c.y, acc1);
+            }
+            T[s * D + i] = acc0 + acc1;
+        }
+    }
+}
+
+// R-coefficients of the gradient: Rg_ij = -(1/d^2) sum_s W[i][s] C[j][s], written TRANSPOSED into Rb.  Lane (i = lane % D,
+// jq = lane / D) owns the outputs j = JB jq .. JB jq + JB - 1: per state one conflict-free load of Wt[s][i] and JB broadcast
+// coefficients of the state's Bloch vector.
+//
+// Four states per trip (the one-wave kernels; the two-waves kernel has its own plain loop), their four weights and four Bloch-vector pieces (16-byte loads where
+// JB is even: Ct[st * D + j0 ..] is 16-byte aligned then) requested before the first FMA and held there by a scheduling
+// barrier.  The plain loop compiled to one exposed LDS round trip per 16-byte load: 63 full waits for 36 states
+// (profiles/r07/outer_phases_before.txt).  Each acc[r] still receives st = 0, 1, 2, ... in order: same bits.
+template <int NQ>
+__device__ __forceinline__ void grad_coefficients(const double* Wt, const double* Ct, double* Rb, int S, int lane) {
+    constexpr int d = 1 << NQ, D = d * d, JB = (D * D + 63) / 64, UG = 4;
+    const int i = lane % D, j0 = (lane / D) * JB;
+    if (j0 < D) {
+        double acc[JB];
+#pragma unroll
+        for (int r = 0; r < JB; ++r) acc[r] = 0.0;
+        int st = 0;
+        {
+            for (; st + UG <= S; st += UG) {
+                double w[UG], c[UG][JB];
+#pragma unroll
+                for (int u = 0; u < UG; ++u) w[u] = Wt[(st + u) * D + i];
+#pragma unroll
+                for (int u = 0; u < UG; ++u) {
+                    if constexpr (JB % 2 == 0) {
+                        const double2* c2 = reinterpret_cast<const double2*>(Ct + (st + u) * D + j0);
+#pragma unroll
+                        for (int r = 0; r < JB / 2; ++r) { const double2 v = c2[r]; c[u][2 * r] = v.x; c[u][2 * r + 1] = v.y; }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < JB; ++r) c[u][r] = Ct[(st + u) * D + j0 + r];
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < UG; ++u) {
+#pragma unroll
+                    for (int r = 0; r < JB; ++r) acc[r] = fma(w[u], c[u][r], acc[r]);
+                }
+            }
+        }
+        for (; st < S; ++st) {
+            const double w = Wt[st * D + i];
+#pragma unroll
+            for (int r = 0; r < JB; ++r) acc[r] = fma(w, Ct[st * D + j0 + r], acc[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < JB; ++r) Rb[(j0 + r) * D + i] = -acc[r] / (double)(d * d);
     }
 }
 
@@ -143,6 +234,9 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
     // s_set_gpr_idx): unrolled they are 6.4 KB of code per slot -- 58 of the 91 KB of the 540-setting instantiation, against a
     // 64 KB instruction cache that eight wavefronts in eight different phases share.
     constexpr int SLOT_UNROLL = LEAN ? 1 : MAXJ;
+    // states per trip of the table products (predict_table): three in the one-wave kernel -- the 36-state design is three trips per
+    // lane, the 16-state one a trip and a single state; the two-waves kernel has no registers for more than one
+    constexpr int TABLE_U = LEAN ? 1 : 3;
     int lane = threadIdx.x & 63;
     const long long item = item_;
     const int m = des.m, S = des.S;
@@ -376,7 +470,7 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
         stage_ct();                                 // (LEAN) stays in place for the gradient product below
         FBX_WAVE_SYNC();
         PH_STOP(pc, 3);
-        predict_table<NQ>(L.Rb, Ct, L.Test, S, lane);
+        predict_table<NQ, TABLE_U>(L.Rb, Ct, L.Test, S, lane);
         load_slots();
         FBX_WAVE_SYNC();
         PH_STOP(pc, 7);
@@ -409,10 +503,10 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
             }
         }
         FBX_WAVE_SYNC();
-        // R-coefficients of the gradient: Rg_ij = -(1/d^2) sum_s W[i][s] C[j][s].  Lane (i = lane % D,
-        // jq = lane / D) owns the outputs j = JB jq .. JB jq + JB - 1: per state one conflict-free load of
-        // Wt[s][i] and JB broadcast coefficients of the state's Bloch vector.
-        {
+        // R-coefficients of the gradient, Rg = -(W C^T) / d^2: four states per trip in the one-wave kernel (grad_coefficients, above);
+        // the register-capped two-waves kernel keeps the plain loop, so that its code -- 9 spilled registers -- stays what it was
+        if constexpr (!LEAN) grad_coefficients<NQ>(Wt, Ct, L.Rb, S, lane);
+        else {
             constexpr int JB = (D * D + 63) / 64;
             const int i = lane % D, j0 = (lane / D) * JB;
             if (j0 < D) {
@@ -475,7 +569,7 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
         FBX_WAVE_SYNC();
         stage_ct();
         FBX_WAVE_SYNC();
-        predict_table<NQ>(L.Rb, Ct, L.Tupd, S, lane);
+        predict_table<NQ, TABLE_U>(L.Rb, Ct, L.Tupd, S, lane);
         load_slots();
         FBX_WAVE_SYNC();
         load_probs(L.Test, pep, pem, 1.0);      // again: not kept in registers across the projection

@@ -22,6 +22,10 @@ FIT_CONVERGED_FTOL, FIT_CONVERGED_XTOL, FIT_MAX_ITERS, FIT_BAD_START = 1, 2, 3, 
 FIT_SINGULAR_COVAR = 16
 FIT_GRAD_FLOOR = 4096 * 2.0 ** -52
 FIT_PREPARE_RB, FIT_PREPARE_UNITARITY = 0, 1
+HIST_JOINT, HIST_WEIGHT = 0, 1
+HIST_MAX_JOINT_K = 10
+HIST_MAX_SHOTS = 2 ** 31 - 1
+HIST_WAVE_BYTES = 16384         # records below this many bytes get a wavefront each (csrc/fbx_histogram.hip)
 
 
 class FbxError(RuntimeError):
@@ -161,6 +165,12 @@ PROTOTYPES = {
     "fbx_rpe_from_shots_dev": [C.c_int, _i64, C.c_int, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
     "fbx_circular_stats": [_i64, _i64, _dp, _dp, _dp, _ip],
     "fbx_circular_stats_dev": [_i64, _i64, _vp, _vp, _vp, _vp],
+    "fbx_bit_histogram": [C.c_int, _i64, _i64, _u8p, C.c_int, _u8p, C.c_int, _u8p, C.c_int, C.POINTER(C.c_int64)],
+    "fbx_bit_histogram_dev": [C.c_int, _i64, _i64, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp],
+    "fbx_counts_to_frequencies": [_i64, C.POINTER(C.c_int64), _i64, _dp],
+    "fbx_counts_to_frequencies_dev": [_i64, _vp, _i64, _vp],
+    "fbx_marginalize_confusion": [C.c_int, _i64, C.c_int, _u8p, _dp, _dp],
+    "fbx_marginalize_confusion_dev": [C.c_int, _i64, C.c_int, _u8p, _vp, _vp],
 }
 
 

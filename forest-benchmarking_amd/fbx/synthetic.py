@@ -193,3 +193,52 @@ def spectroscopy_data(kind, xs, shots=500, batch=1, seed=5000, **params):
         p1 = np.clip(models[kind](xs, **{k: v[b] for k, v in cols.items()}), 0.0, 1.0)
         e[b] = 1.0 - 2.0 * rng.binomial(int(shots), p1) / float(shots)
     return e, np.sqrt(np.clip(1.0 - e * e, 0.0, None) / float(shots))
+
+
+def readout_shots(confusion, shots, seed=6000):
+    """Measured bitstrings of a joint readout characterisation: ``confusion [G, 2^g, 2^g]`` (or one ``[2^g, 2^g]`` matrix), row =
+    the prepared bitstring, column = the observed one, rows summing to 1 -> ``[G, 2^g, shots, g]`` uint8 (``[2^g, shots, g]`` for
+    one matrix) as ``readout.joint_confusion_matrices_batch`` takes them: the observed strings of row r of group G are drawn from
+    that row by ``np.random.default_rng([seed, G, r])``, first column = most significant bit."""
+    c = np.asarray(confusion, dtype=np.float64)
+    single = c.ndim == 2
+    c = c[None] if single else c
+    if c.ndim != 3 or c.shape[1] != c.shape[2] or c.shape[1] < 2 or c.shape[1] & (c.shape[1] - 1):
+        raise ValueError("confusion must be [G, 2^g, 2^g]")
+    if int(shots) < 0 or c.min() < 0.0 or not np.allclose(c.sum(axis=2), 1.0):
+        raise ValueError("need shots >= 0 and rows that are probability distributions")
+    G, N = c.shape[:2]
+    g = N.bit_length() - 1
+    shifts = np.arange(g - 1, -1, -1)
+    out = np.empty((G, N, int(shots), g), dtype=np.uint8)
+    for grp in range(G):
+        for r in range(N):
+            idx = np.random.default_rng([int(seed), grp, r]).choice(N, size=int(shots), p=c[grp, r] / c[grp, r].sum())
+            out[grp, r] = (idx[:, None] >> shifts) & 1
+    return out[0] if single else out
+
+
+def adder_shots(n_bits, flip_probability, shots, seed=7000):
+    """Results of an n-bit ripple-carry adder run in the layout of the reference's ``get_n_bit_adder_results``: ``[4^n, shots,
+    n + 1]`` uint8, row r = the addition a + b that the 2n-bit number r spells; every answer bit of every shot is flipped
+    independently with ``flip_probability``; addition r draws from ``np.random.default_rng([seed, r])``."""
+    from .classical_logic.ripple_carry_adder import adder_expected_bits
+    if not 0.0 <= flip_probability <= 1.0 or int(shots) < 0:
+        raise ValueError("need 0 <= flip_probability <= 1 and shots >= 0")
+    ans = adder_expected_bits(int(n_bits))
+    out = np.empty((ans.shape[0], int(shots), ans.shape[1]), dtype=np.uint8)
+    for r in range(ans.shape[0]):
+        flips = np.random.default_rng([int(seed), r]).random((int(shots), ans.shape[1])) < flip_probability
+        out[r] = ans[r] ^ flips
+    return out
+
+
+def ghz_shots(n, flip_probability, shots, seed=8000):
+    """Bitstrings measured on an n-qubit GHZ state: ``[shots, n]`` uint8, every shot all zeros or all ones with equal probability,
+    then every bit flipped independently with ``flip_probability``; drawn from ``np.random.default_rng(seed)``."""
+    if int(n) < 1 or not 0.0 <= flip_probability <= 1.0 or int(shots) < 0:
+        raise ValueError("need n >= 1, 0 <= flip_probability <= 1 and shots >= 0")
+    rng = np.random.default_rng(int(seed))
+    side = rng.integers(0, 2, size=(int(shots), 1), dtype=np.uint8)
+    flips = rng.random((int(shots), int(n))) < flip_probability
+    return (side ^ flips).astype(np.uint8)

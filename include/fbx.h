@@ -628,6 +628,42 @@ int fbx_circular_stats(int64_t R, int64_t B, const double* angles, double* mean_
 int fbx_circular_stats_dev(int64_t R, int64_t B, const double* d_angles, double* d_mean_out, double* d_std_out,
                            int32_t* d_nan_count_out);
 
+/* ---------------------------------------------------------------- histograms of measured bitstrings
+ * How often each bitstring, or each Hamming weight, occurred in every one of B records: the reduction under the joint readout
+ * confusion matrices (readout.py:69-180, 236-335: row = the prepared string, one record per row), the ripple-carry adder's success
+ * probabilities and error-weight distributions (classical_logic/ripple_carry_adder.py:317-384) and ghz_state_statistics
+ * (entangled_states.py:36-51).  bits is [B][n_shots][n_cols] bytes, the records of fbx_shots_to_moments; only bit 0 of a byte is read.
+ * cols selects k columns in any order (repeats allowed): [k] shared by the batch when cols_shared != 0, else [B][k]; NULL = columns
+ * 0..k-1.  expected ([B][k] of 0 / 1, or NULL) is XORed onto the selected bits.
+ *   FBX_HIST_JOINT   2^k bins, k in 1..10: bin = sum_i bit_i 2^(k-1-i), the first selected column most significant (the order of
+ *                    itertools.product([0, 1], repeat=k) and of utils.bit_array_to_int)
+ *   FBX_HIST_WEIGHT  k + 1 bins, k in 1..64: bin = the Hamming weight of the selected bits after the XOR (bin 0 = the shot matches
+ *                    `expected` bit for bit)
+ * counts_out[B][bins] are exact integers that sum to n_shots per record: they depend on nothing but the record, and two runs agree
+ * bit for bit.  n_cols 1..64; n_shots 1..2^31 - 1 (32-bit counters on the chip).  The host form rejects a column index >= n_cols;
+ * the _dev form cannot read the selection and instead fills the bins of a record whose selection has such an entry with -1, reading
+ * nothing of that record.  One wavefront per record below 16 KB, one workgroup per longer record; a record is never split over
+ * workgroups.  B == 0 returns FBX_OK.  The _dev forms enqueue on the calling thread's stream and do not synchronise. */
+#define FBX_HIST_JOINT  0
+#define FBX_HIST_WEIGHT 1
+int fbx_bit_histogram(int n_cols, int64_t B, int64_t n_shots, const uint8_t* bits, int k, const uint8_t* cols, int cols_shared,
+                      const uint8_t* expected, int kind, int64_t* counts_out);
+int fbx_bit_histogram_dev(int n_cols, int64_t B, int64_t n_shots, const uint8_t* d_bits, int k, const uint8_t* d_cols, int cols_shared,
+                          const uint8_t* d_expected, int kind, int64_t* d_counts_out);
+
+/* out[i] = counts[i] / denom, one IEEE division per element on the device: the relative frequencies of a histogram (denom = n_shots;
+ * the number of trials for the reset confusion matrices).  denom >= 1. */
+int fbx_counts_to_frequencies(int64_t n, const int64_t* counts, int64_t denom, double* out);
+int fbx_counts_to_frequencies_dev(int64_t n, const int64_t* d_counts, int64_t denom, double* d_out);
+
+/* marginalize_confusion_matrix (readout.py:183-233) for a batch in[B][2^n][2^n] of float64 matrices, n = n_qubits in 1..10: keep[k]
+ * lists the qubit positions that stay (position 0 = the most significant bit of a row / column index), strictly ascending, k in
+ * 1..n; out[B][2^k][2^k], element = the sum of the 4^(n-k) inputs whose row and column bits agree with it on the kept positions,
+ * divided by 2^(n-k).  The sum has one fixed order, so repeated calls agree bit for bit and an item does not depend on B.  keep is a
+ * HOST pointer in both forms (a design argument, read and checked before any device work). */
+int fbx_marginalize_confusion(int n_qubits, int64_t B, int k, const uint8_t* keep, const double* in, double* out);
+int fbx_marginalize_confusion_dev(int n_qubits, int64_t B, int k, const uint8_t* keep, const double* d_in, double* d_out);
+
 /* ---------------------------------------------------------------- random operators
  * operator_tools/random_operators.py:21-157 for batches, generated on the device.  Item b (global id
  * first_item + b) owns a counter-based Philox4x32-10 stream keyed by `seed`, so an item's matrices

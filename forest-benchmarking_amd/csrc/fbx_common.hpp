@@ -374,6 +374,19 @@ __device__ __forceinline__ double fast_log_pos(double x) {
     return dk * 6.93147180369123816490e-01 - ((hfsq - fma(s, hfsq + R, dk * 1.90821492927058770002e-10)) - f);
 }
 
+// One Philox4x32-10 block (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", 2011): the counter-based generator of
+// every random stream of the library (fbx_random.hip, fbx_shots.hip, fbx_clifford.hip), counter in and four words out in c.
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
 // Pauli index (base-4 digits, qubit 0 most significant) -> x / z bit masks over the
 // computational index (qubit 0 = most significant bit) and number of Y factors.
 template <int NQ>

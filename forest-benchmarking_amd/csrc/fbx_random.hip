@@ -18,22 +18,11 @@
 
 namespace fbx {
 
-__device__ __forceinline__ void philox_block(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
 // one complex standard normal N(0,1) + i N(0,1): Box-Muller on the first two words of the block
 // (item, element, tag); the two outputs of one Box-Muller pair are independent normals
 __device__ __forceinline__ cplx ginibre_entry(unsigned long long seed, long long item, uint32_t elem, uint32_t tag) {
     uint32_t c[4] = {(uint32_t)item, (uint32_t)((unsigned long long)item >> 32), elem, tag};
-    philox_block(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     const double u1 = ((double)c[0] + 0.5) * 0x1p-32, u2 = ((double)c[1] + 0.5) * 0x1p-32;
     const double mag = sqrt(-2.0 * log(u1));
     double sn, cs;

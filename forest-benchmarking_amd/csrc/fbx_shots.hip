@@ -345,16 +345,6 @@ dfe_kernel(int n_qubits, int process, long long B, long long m, const double* __
 // gammas by Marsaglia-Tsang squeeze-free rejection, one Philox block (two 32-bit uniforms for the
 // Box-Muller normal, one 53-bit uniform for the acceptance test) per attempt.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 struct PhiloxStream {
     uint32_t k0, k1, e0, e1, draw;
     __device__ __forceinline__ void next(double& u1, double& u2, double& u3) {

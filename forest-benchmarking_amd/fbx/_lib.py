@@ -26,6 +26,8 @@ HIST_JOINT, HIST_WEIGHT = 0, 1
 HIST_MAX_JOINT_K = 10
 HIST_MAX_SHOTS = 2 ** 31 - 1
 HIST_WAVE_BYTES = 16384         # records below this many bytes get a wavefront each (csrc/fbx_histogram.hip)
+CLIFFORD_NONE = 0xFFFFFFFF      # no element: "no interleaved gate" / "no such index" (include/fbx.h)
+RB_MAX_NOISE_PTMS = 16
 
 
 class FbxError(RuntimeError):
@@ -45,6 +47,8 @@ _lib = None
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _u8p = C.POINTER(C.c_uint8)
+_u32p = C.POINTER(C.c_uint32)
+_i64p = C.POINTER(C.c_int64)
 _vp = C.c_void_p
 _i64 = C.c_int64
 
@@ -171,6 +175,12 @@ PROTOTYPES = {
     "fbx_counts_to_frequencies_dev": [_i64, _vp, _i64, _vp],
     "fbx_marginalize_confusion": [C.c_int, _i64, C.c_int, _u8p, _dp, _dp],
     "fbx_marginalize_confusion_dev": [C.c_int, _i64, C.c_int, _u8p, _vp, _vp],
+    "fbx_clifford_from_index": [C.c_int, _i64, _u32p, _u32p],
+    "fbx_clifford_from_index_dev": [C.c_int, _i64, _vp, _vp],
+    "fbx_rb_sequences": [C.c_int, _i64, _i64p, C.c_uint64, C.c_uint32, C.c_int, _u32p, _u8p],
+    "fbx_rb_sequences_dev": [C.c_int, _i64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp],
+    "fbx_rb_simulate": [C.c_int, _i64, _i64p, _u32p, _u8p, C.c_int, _dp, _dp, _dp],
+    "fbx_rb_simulate_dev": [C.c_int, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
 }
 
 

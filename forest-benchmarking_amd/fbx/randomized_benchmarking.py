@@ -4,14 +4,20 @@ The analysis half of the reference's module under its own names: survival statis
 unitarity, the decay fits, and the interleaved-RB bounds.  ``fit_rb_results_batch`` / ``fit_unitarity_results_batch`` take
 ``[B, S, .]`` arrays (B decays of S sequences each) and run statistics -> weights and guess -> fit as one chain of device calls
 (fbx_rb_survival_dev / fbx_rb_purity_dev -> fbx_fit_prepare_dev -> fbx_curve_fit_dev); the single-experiment functions are that
-chain with B = 1.  The scalar conversion and bound formulas are plain numpy and accept arrays.  Sequence generation and data
-acquisition (``generate_*``, ``acquire_*``, ``do_rb``) need pyquil, quilc and a QuantumComputer and are not part of this package.
+chain with B = 1.  The scalar conversion and bound formulas are plain numpy and accept arrays.
+
+Sequence generation (``generate_rb_sequence``, ``generate_rb_experiment_sequences``) keeps the reference's names and rules but
+needs no quilc: a Clifford is an element word of ``fbx.clifford`` (include/fbx.h, "Clifford elements"), a sequence an array of
+words drawn, composed and inverted on the device (fbx_rb_sequences); ``clifford.to_gates`` turns a word into native gates.
+``simulate_rb_sequences_batch`` runs sequences under Pauli-transfer-matrix noise (fbx_rb_simulate), ``simulate_rb_experiment_batch``
+turns that into the arrays ``fit_rb_results_batch`` takes.  Data acquisition on a QuantumComputer (``acquire_*``, ``do_rb``) needs
+pyquil and is not part of this package.
 """
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, clifford
 from .analysis import fitting
 from .observable_estimation import get_results_by_qubit_groups
 
@@ -255,3 +261,181 @@ def average_gate_error_to_rb_decay(gate_error, dimension: int):
 def rb_decay_to_gate_error(rb_decay, dimension: int):
     """1 - rb_decay - (1 - rb_decay) / d (randomized_benchmarking.py:791-800)."""
     return 1 - rb_decay - (1 - rb_decay) / dimension
+
+
+# ---------------------------------------------------------------- sequences and their simulation (fbx_rb_sequences / fbx_rb_simulate)
+def _n_qubits(n):
+    n = int(n)
+    if n > 2:
+        raise ValueError("No RB gateset for more than two qubits.")
+    if n < 1:
+        raise ValueError("RB sequences need at least one qubit.")
+    return n
+
+
+def _interleaved_word(n, interleaved_gate):
+    if interleaved_gate is None:
+        return _lib.CLIFFORD_NONE
+    if not clifford.is_valid(int(interleaved_gate), n):
+        raise ValueError(f"interleaved_gate is not a valid {n}-qubit Clifford element word")
+    return int(interleaved_gate)
+
+
+def _seed64(random_seed):
+    if random_seed is None:
+        return int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+    return int(random_seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def z_product_indices(n_qubits: int) -> np.ndarray:
+    """Pauli indices of the 2^n - 1 non-identity I/Z products, observable z = 1 .. 2^n - 1 read as a bit mask whose lowest bit is
+    the LAST qubit (the order of ``synthetic.rb_data``): [3] for one qubit, [3, 12, 15] = IZ, ZI, ZZ for two."""
+    n = _n_qubits(n_qubits)
+    return np.array([sum(3 << (2 * t) for t in range(n) if (z >> t) & 1) for z in range(1, 1 << n)], dtype=np.int64)
+
+
+def _rb_sequences(n, lengths, seed, interleaved, self_inverting):
+    lengths = np.asarray(lengths, dtype=np.int64).ravel()
+    if lengths.size and lengths.min() < 0:
+        raise ValueError("sequence lengths must not be negative")
+    offsets = np.zeros(lengths.size + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    total = int(offsets[-1])
+    elems = np.empty(total, dtype=np.uint32)
+    noise_ids = np.empty(total, dtype=np.uint8)
+    _lib.check(_lib.lib().fbx_rb_sequences(n, lengths.size, offsets.ctypes.data_as(_lib._i64p), seed, interleaved, int(bool(self_inverting)),
+                                           elems.ctypes.data_as(_lib._u32p), noise_ids.ctypes.data_as(_lib._u8p)))
+    return offsets, elems, noise_ids
+
+
+def _length_of_depth(depth, interleaved, self_inverting):
+    """Elements of a sequence of ``depth`` Cliffords (the inverse included when self-inverting): an interleaved gate follows every
+    random element."""
+    randoms = depth - 1 if self_inverting else depth
+    return (2 * randoms if interleaved != _lib.CLIFFORD_NONE else randoms) + (1 if self_inverting else 0)
+
+
+def generate_rb_sequence(benchmarker, qubits: Sequence[int], depth: int, interleaved_gate: Optional[int] = None,
+                         random_seed: Optional[int] = None) -> np.ndarray:
+    """A complete self-inverting RB sequence (randomized_benchmarking.py:105-126) as a uint32 array of Clifford element words:
+    ``depth`` Cliffords, the last one the inverse of the rest; with ``interleaved_gate`` (an element word) that gate follows each
+    of the depth - 1 random Cliffords.  ``benchmarker`` is accepted for the reference's signature and ignored (None is fine); only
+    ``len(qubits)`` matters, the words count their qubits 0, 1."""
+    if depth < 2:
+        raise ValueError("Sequence depth must be at least 2 for rb sequences, or at least 1 for "
+                         "unitarity sequences.")
+    n = _n_qubits(len(qubits))
+    inter = _interleaved_word(n, interleaved_gate)
+    return _rb_sequences(n, [_length_of_depth(int(depth), inter, True)], _seed64(random_seed), inter, True)[1]
+
+
+def generate_rb_experiment_sequences(benchmarker, qubits: Sequence[int], depths: Sequence[int], interleaved_gate: Optional[int] = None,
+                                     random_seed: Optional[int] = None, use_self_inv_seqs: bool = True) -> List[np.ndarray]:
+    """One sequence per entry of ``depths`` (randomized_benchmarking.py:129-174).  As in the reference, ``random_seed`` advances
+    by one per depth, and ``use_self_inv_seqs=False`` generates depth + 1 Cliffords without an interleaved gate and strips the
+    inverse."""
+    sequences = []
+    for depth in depths:
+        if random_seed is not None:
+            random_seed += 1
+        if use_self_inv_seqs:
+            sequence = generate_rb_sequence(benchmarker, qubits, depth, interleaved_gate, random_seed)
+        else:
+            sequence = generate_rb_sequence(benchmarker, qubits, depth + 1, random_seed=random_seed)[:-1]
+        sequences.append(sequence)
+    return sequences
+
+
+def generate_rb_sequences_batch(n_qubits: int, depths: Sequence[int], num_sequences: int, interleaved_gate: Optional[int] = None,
+                                seed: Optional[int] = None, self_inverting: bool = True):
+    """``num_sequences`` sequences for every entry of ``depths`` in one device call: ``(offsets, elems, noise_ids)`` with
+    sequence ``i * num_sequences + s`` (depth i, repetition s) in ``elems[offsets[b]:offsets[b + 1]]`` and ``noise_ids`` 1 on
+    the interleaved elements.  A depth counts Cliffords as ``generate_rb_sequence`` does (inverse included when self-inverting).
+    Sequence b depends on ``(seed, b)`` only."""
+    n = _n_qubits(n_qubits)
+    inter = _interleaved_word(n, interleaved_gate)
+    depths = [int(d) for d in depths]
+    if any(d < (2 if self_inverting else 1) for d in depths):
+        raise ValueError("Sequence depth must be at least 2 for rb sequences, or at least 1 for "
+                         "unitarity sequences.")
+    lengths = np.repeat([_length_of_depth(d, inter, self_inverting) for d in depths], int(num_sequences))
+    return _rb_sequences(n, lengths, _seed64(seed), inter, self_inverting)
+
+
+def simulate_rb_sequences_batch(n_qubits: int, offsets, elems, noise_ptms, noise_ids=None, prep=None) -> np.ndarray:
+    """Final Pauli vectors ``[B, 4^n]`` of the sequences ``elems[offsets[b]:offsets[b + 1]]``: from ``prep`` (default |0..0>), every
+    element's signed permutation followed by the Pauli transfer matrix ``noise_ptms[noise_ids[.]]`` (``[G, 4^n, 4^n]`` or one
+    matrix; ``noise_ids`` default all 0)."""
+    n = _n_qubits(n_qubits)
+    D = 4 ** n
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    elems = np.ascontiguousarray(elems, dtype=np.uint32)
+    ptms = np.ascontiguousarray(noise_ptms, dtype=np.float64)
+    if ptms.ndim == 2:
+        ptms = ptms[None]
+    if ptms.ndim != 3 or ptms.shape[1:] != (D, D):
+        raise ValueError(f"noise_ptms must be [G, {D}, {D}]")
+    if offsets.ndim != 1 or offsets.size < 1:
+        raise ValueError("offsets must be [B + 1]")
+    B = offsets.size - 1
+    if B and (offsets[0] != 0 or offsets[-1] != elems.size):
+        raise ValueError("offsets must start at 0 and end at len(elems)")
+    ids = None
+    if noise_ids is not None:
+        ids = np.ascontiguousarray(noise_ids, dtype=np.uint8)
+        if ids.shape != elems.shape:
+            raise ValueError("noise_ids must have the shape of elems")
+    p = None
+    if prep is not None:
+        p = np.ascontiguousarray(prep, dtype=np.float64)
+        if p.shape != (D,):
+            raise ValueError(f"prep must be a Pauli vector of {D} components")
+    out = np.empty((B, D))
+    _lib.check(_lib.lib().fbx_rb_simulate(n, B, offsets.ctypes.data_as(_lib._i64p), elems.ctypes.data_as(_lib._u32p),
+                                          None if ids is None else ids.ctypes.data_as(_lib._u8p), ptms.shape[0], _lib.dptr(ptms),
+                                          _lib.dptr(p), _lib.dptr(out)))
+    return out
+
+
+def simulate_rb_experiment_batch(n_qubits: int, depths: Sequence[int], num_sequences: int, noise_ptms, interleaved_gate: Optional[int] = None,
+                                 seed: Optional[int] = None, shots: Optional[int] = None, prep=None):
+    """RB (or, with ``interleaved_gate``, IRB) experiments from noise channels: ``noise_ptms`` is ``[G, 4^n, 4^n]`` for one
+    experiment or ``[E, G, 4^n, 4^n]`` for E of them (PTM 0 follows every random Clifford and the inverse, PTM 1 the interleaved
+    gate); every experiment draws ``num_sequences`` self-inverting sequences per depth (seed + experiment index) and simulates
+    them.  Returns ``(z_expectations, z_std_errs)``, both ``[E, len(depths), 2^n - 1]`` as ``fit_rb_results_batch`` takes them: the
+    I/Z-product expectations (``z_product_indices``) averaged over the sequences of a depth, and the standard error of that mean
+    (0 for a single sequence without shots).  ``shots`` samples every sequence's expectations first
+    (``synthetic.sample_expectations``, independent observables; its streams are keyed by a hash of the experiment's seed, so
+    another seed gives other sequences AND other shot noise).  For two qubits ``fit_rb_results_batch`` asks for ``num_shots``
+    (the covariance of IZ, ZI, ZZ estimated from one set of shots): pass ``shots``, or a large number such as 10^12 for the exact
+    expectations of ``shots=None``, whose covariance term vanishes."""
+    n = _n_qubits(n_qubits)
+    D = 4 ** n
+    ptms = np.asarray(noise_ptms, dtype=np.float64)
+    if ptms.ndim == 2:
+        ptms = ptms[None]
+    if ptms.ndim == 3:
+        ptms = ptms[None]
+    if ptms.ndim != 4 or ptms.shape[2:] != (D, D):
+        raise ValueError(f"noise_ptms must be [G, {D}, {D}] or [E, G, {D}, {D}]")
+    if interleaved_gate is not None and ptms.shape[1] < 2:
+        raise ValueError("an interleaved experiment needs two noise PTMs: [0] after the random Cliffords, [1] after the gate")
+    S, K = len(depths), int(num_sequences)
+    if K < 1:
+        raise ValueError("num_sequences must be positive")
+    cols = z_product_indices(n)
+    base = _seed64(seed)
+    e_out, s_out = np.empty((ptms.shape[0], S, cols.size)), np.empty((ptms.shape[0], S, cols.size))
+    for x in range(ptms.shape[0]):
+        offsets, elems, ids = generate_rb_sequences_batch(n, depths, K, interleaved_gate, (base + x) & 0xFFFFFFFFFFFFFFFF, True)
+        z = simulate_rb_sequences_batch(n, offsets, elems, ptms[x], ids, prep)[:, cols]             # [S K, 2^n - 1]
+        shot_var = 0.0
+        if shots is not None:
+            from . import synthetic
+            # the binomial streams follow the seed too: RandomState(seed_base + sequence index), seed_base a hash of (seed + x)
+            z, _ = synthetic.sample_expectations(z, int(shots), seed_base=(((base + x) * 0x9E3779B1) >> 7) % (2 ** 31))
+            shot_var = np.clip(1.0 - z * z, 0.0, None).reshape(S, K, -1).mean(axis=1) / float(shots)
+        z = z.reshape(S, K, -1)
+        e_out[x] = z.mean(axis=1)
+        s_out[x] = np.sqrt(z.var(axis=1, ddof=1) / K) if K > 1 else np.sqrt(shot_var + np.zeros_like(e_out[x]))
+    return e_out, s_out

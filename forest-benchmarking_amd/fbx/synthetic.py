@@ -173,6 +173,16 @@ def rb_data(n_qubits, depths, decay=0.97, shots=500, batch=1, seed=4000):
     return e, np.sqrt(np.clip(1.0 - e * e, 0.0, None) / float(shots))
 
 
+def rb_sequence_data(n_qubits, depths, noise_ptms, num_sequences=32, interleaved_gate=None, shots=None, seed=4000):
+    """Randomized-benchmarking statistics from actual sequences under actual noise, in the shapes of ``rb_data``: Clifford
+    sequences are drawn and simulated on the device under the Pauli transfer matrices ``noise_ptms`` ([G, 4^n, 4^n], or
+    [batch, G, 4^n, 4^n] for a batch of experiments) and averaged per depth -- no decay is assumed
+    (``randomized_benchmarking.simulate_rb_experiment_batch``)."""
+    from . import randomized_benchmarking as rb
+    return rb.simulate_rb_experiment_batch(n_qubits, depths, num_sequences, noise_ptms, interleaved_gate=interleaved_gate, seed=seed,
+                                           shots=shots)
+
+
 def spectroscopy_data(kind, xs, shots=500, batch=1, seed=5000, **params):
     """Synthetic single-qubit spectroscopy statistics for ``qubit_spectroscopy.fit_*_results_batch``: ``(expectations, std_errs)``,
     both [batch, len(xs)].  ``kind``: 't1' (amplitude, decay_time, offset), 't2' (amplitude, decay_time, offset, baseline,

@@ -692,6 +692,59 @@ int fbx_random_kraus(int n_qubits, int64_t B, int K, uint64_t seed, int64_t firs
 int fbx_random_kraus_dev(int n_qubits, int64_t B, int K, uint64_t seed, int64_t first_item,
                          double* d_kraus_out);
 
+/* ---------------------------------------------------------------- Clifford elements, RB sequences and their simulation
+ * The reference hands the Clifford group work of randomized benchmarking to quilc through a BenchmarkConnection
+ * (randomized_benchmarking.py:105-174: sample a uniform Clifford, compose, invert, conjugate a Pauli); here it is on the device, for
+ * n_qubits = 1 and 2 as in the reference (get_rb_gateset, :77-90).  n_qubits > 2: FBX_ERR_UNSUPPORTED; < 1: FBX_ERR_BAD_ARG.
+ *
+ * Clifford elements.  An element C of the group modulo global phase is one uint32 word: the signed Pauli images C g C^+ of the
+ * generators g_0 = X_0, g_1 = Z_0 (n = 1) and g_2 = X_1, g_3 = Z_1 (n = 2), image j in bits [5 j, 5 j + 5) --
+ *     bits 5 j .. 5 j + 3   Pauli index of the image (the order of the project's PTMs: base-4 digits I X Y Z = 0 1 2 3, qubit 0
+ *                           the most significant digit; 0..3 for n = 1, 0..15 for n = 2)
+ *     bit  5 j + 4          1 when the image carries a minus sign
+ * and every bit from 10 n on zero.  The identity is 0x61 (n = 1) and 0x18584 (n = 2).  A word is VALID when the images of X_q and
+ * Z_q anticommute and images that belong to different qubits commute (which makes every image a non-identity Pauli); 24 and
+ * 11 520 words are.  FBX_CLIFFORD_NONE is no element: "no interleaved gate" on the way in, "no such index" on the way out.
+ * The Pauli transfer matrix of an element is the signed permutation with C P_k C^+ = +- P_perm(k); fbx/clifford.py is the host
+ * mirror (from_index, compose, inverse, apply_to_pauli, to_ptm, to_gates) and documents the enumeration behind
+ * fbx_clifford_from_index: elems_out[i] = the idx[i]-th element, a bijection from range(24) / range(11520) onto the group.  The
+ * host form rejects an index that is not below the order; the _dev form writes FBX_CLIFFORD_NONE for it. */
+#define FBX_CLIFFORD_NONE 0xFFFFFFFFu
+int fbx_clifford_from_index(int n_qubits, int64_t B, const uint32_t* idx, uint32_t* elems_out);
+int fbx_clifford_from_index_dev(int n_qubits, int64_t B, const uint32_t* d_idx, uint32_t* d_elems_out);
+
+/* B randomized-benchmarking sequences (the quilc call behind generate_rb_sequence, randomized_benchmarking.py:105-126).  Sequence b
+ * fills elems_out[offsets[b] .. offsets[b + 1]) (offsets[B + 1] int64, starting at 0, never decreasing; its length L_b may be 0):
+ *   - interleaved_elem == FBX_CLIFFORD_NONE: elements 0, 1, 2, ... are independent uniform draws from the group;
+ *     otherwise (interleaved RB) the even positions are the draws and every odd position holds interleaved_elem;
+ *   - self_inverting != 0: the LAST element is instead the inverse of the composition of everything before it, interleaved
+ *     elements included, so that the sequence composes to the identity (L_b = 1: the identity).  self_inverting == 0: that last
+ *     element is simply not there -- the sequence equals the first L_b elements of the self-inverting sequence of length L_b + 1.
+ * noise_id_out (may be NULL) marks interleaved elements 1 and every other element 0: the `noise_ids` of fbx_rb_simulate.
+ * Sequence b owns the Philox4x32-10 stream keyed by (seed, b) (as fbx_random_operators' items do): its content depends on neither B
+ * nor the launch shape, and the draws at the even positions of an interleaved sequence are the draws of the plain one.  A draw is
+ * exactly uniform (multiply-high with rejection, no modulo).  The host form rejects offsets that do not start at 0 or decrease
+ * and an interleaved_elem that is not a valid word; the _dev form cannot read its offsets and trusts them. */
+int fbx_rb_sequences(int n_qubits, int64_t B, const int64_t* offsets, uint64_t seed, uint32_t interleaved_elem, int self_inverting,
+                     uint32_t* elems_out, uint8_t* noise_id_out);
+int fbx_rb_sequences_dev(int n_qubits, int64_t B, const int64_t* d_offsets, uint64_t seed, uint32_t interleaved_elem, int self_inverting,
+                         uint32_t* d_elems_out, uint8_t* d_noise_id_out);
+
+/* Noisy simulation of B sequences in the Pauli basis, D = 4^n_qubits: sequence b starts from the Pauli vector prep[D] (component
+ * k = tr(P_k rho); NULL = |0..0>, 1 on the I/Z products and 0 elsewhere) and for each of its elements applies the element's signed
+ * permutation and then the D x D Pauli transfer matrix noise_ptms[noise_ids[.]] (row-major [G][D][D], G in 1..16; noise_ids NULL =
+ * all 0); out[B][D] is the final vector, prep itself for a sequence of length 0.  elems must not be NULL when B > 0, even if every
+ * sequence is empty.  The RB observables are the I/Z-product columns
+ * of out, the unitarity ones all of them.  The permutation is exact and a row of the noise step is one chain of D fused
+ * multiply-adds in ascending column order from 0.0, so a sequence's result depends on nothing but the sequence.
+ * Bad input: the host form rejects (FBX_ERR_BAD_ARG) an invalid element word, a noise id >= G and malformed offsets before any
+ * device work; the _dev form reads nothing through such a value and fills out[b] with NaN for that sequence only.  A non-finite
+ * PTM entry reaches only the sequences that use that PTM; every other sequence is bit-identical to a run with finite PTMs. */
+int fbx_rb_simulate(int n_qubits, int64_t B, const int64_t* offsets, const uint32_t* elems, const uint8_t* noise_ids, int G,
+                    const double* noise_ptms, const double* prep, double* out);
+int fbx_rb_simulate_dev(int n_qubits, int64_t B, const int64_t* d_offsets, const uint32_t* d_elems, const uint8_t* d_noise_ids, int G,
+                        const double* d_noise_ptms, const double* d_prep, double* d_out);
+
 /* out[b] = op(a[b]) diag(scale[b]) op(b[b]) for stacks of N x N complex matrices, N in 1..1024: op = the matrix itself
  * (conj_t = 0) or its conjugate transpose (conj_t = 1); scale is [B][N] real or NULL.  The products around fbx_eigh:
  * V f(lambda) V^H (sqrtm_psd, calculational.py:77-91), sqrt(rho) sigma sqrt(rho) (fidelity, distance_measures.py:64-84). */

@@ -1,7 +1,13 @@
 // fbx_state.hip -- batched state-tomography estimators and state measures on d x d (d = 2^n,
-// n <= 3) density matrices.  One 64-lane wavefront per item; lane t < d*d owns matrix entry
-// (t / d, t % d); Pauli expectations and the R operator are evaluated through the sparsity of
-// the Pauli matrices (P_p[r][c] != 0 iff c = r ^ x_p), never by building d x d operators.
+// n <= 5) density matrices, and the Pauli-Liouville vector of a state.  Pauli expectations and the
+// R operator are evaluated through the sparsity of the Pauli matrices (P_p[r][c] != 0 iff
+// c = r ^ x_p), never by building d x d operators.
+//   1-3 qubits: one 64-lane wavefront per item; lane t < d*d owns matrix entry (t / d, t % d).
+//   4-5 qubits (second half of the file): one workgroup per item, d*d threads for the estimators,
+//   (d/2)^2 -- the Jacobi solver's grid -- for the projection and the measures.
+// The formulas both halves share (setting_ratio, div_by_trace, loglik_partial, spectral_function,
+// lower_blk, herm_part_blk) are written once, in front of the 1-3-qubit kernels.  The general
+// eigensolver, matrix product and choi2kraus live in fbx_linalg.hip.
 //
 // Reference functions (file:line under forest/benchmarking/):
 //   linear_inv_state_estimate        tomography.py:130-165
@@ -9,17 +15,10 @@
 //   state_log_likelihood             tomography.py:341-375
 //   project_state_matrix_to_physical operator_tools/project_state_matrix.py:6-52
 //   purity / fidelity / trace_distance / hilbert_schmidt_ip   distance_measures.py:14-114,198-216
-//   sqrtm_psd                        operator_tools/calculational.py:77-91
 #include "fbx_eigh64.hpp"
-#include <hip/hip_cooperative_groups.h>
 #include <cfloat>
 #include <cmath>
-#include <limits>
-#include <type_traits>
-#include <cstdlib>
-#include <algorithm>
-#include <vector>
-#include <cstring>
+#include <string>
 
 namespace fbx {
 
@@ -218,6 +217,79 @@ __device__ __forceinline__ LaneSetting load_lane_setting(const DesignDev& des, c
     return s;
 }
 
+// One setting of the R operator (tomography.py:326-336): from its coefficient, the measured expectation `me` and the state's
+// expectation `pe` of its observable, the half-sum of the two outcome ratios (the identity's weight) and their half-difference
+// times the coefficient (the observable's weight).  (0.5 * x is exact, so a sum that adds `hs` rounds as one that fuses the product.)
+struct SettingRatio { double hs, hd; };
+__device__ __forceinline__ SettingRatio setting_ratio(double cf, double me, double pe) {
+    const double gp = ((1.0 + me) * 0.5) / ((1.0 + pe) * 0.5 + DBL_MIN);
+    const double gm = ((1.0 - me) * 0.5) / ((1.0 - pe) * 0.5 + DBL_MIN);
+    SettingRatio q; q.hs = 0.5 * (gp + gm); q.hd = cf * 0.5 * (gp - gm);
+    return q;
+}
+
+// v / tr for a complex trace (tr_re, tr_im)
+__device__ __forceinline__ cplx div_by_trace(const cplx v, double tr_re, double tr_im) {
+    const double den = tr_re * tr_re + tr_im * tr_im;
+    cplx q; q.re = (v.re * tr_re + v.im * tr_im) / den; q.im = (v.im * tr_re - v.re * tr_im) / den;
+    return q;
+}
+
+// This thread's share of the log-likelihood (log10) of tomography.py:341-375: settings t, t + NT, ... of one item (`e`, `cnt`: its
+// expectations and counts), r = the state's Pauli expectations
+template <int NT>
+__device__ __forceinline__ double loglik_partial(const DesignDev& des, const double* __restrict__ e, const double* __restrict__ cnt,
+                                                 const double* r, int t) {
+    double ll = 0.0;
+    for (int g = t; g < des.m; g += NT) {
+        const int k = des.order[g], p = des.sp[g] & 0xffff;
+        const double cf = des.unit_coefs ? 1.0 : des.coef[g];
+        const double n = cnt[k], me = e[k], pe = cf * r[p];
+        const double pp = (1.0 + pe) / 2, pm = (1.0 - pe) / 2;
+        if (pp > 0.0) ll += n * (1.0 + me) / 2 * log10(pp);
+        if (pm > 0.0) ll += n * (1.0 - me) / 2 * log10(pm);
+    }
+    return ll;
+}
+
+// f(lambda) of herm_function / herm_function_big: fn 0: log, 1: pseudo-inverse (lmax = the largest |lambda|), 2: sqrt(max(., 0))
+template <int d>
+__device__ __forceinline__ double spectral_function(int fn, double l, double lmax) {
+    if (fn == 0) return log(l);
+    if (fn == 1) return (fabs(l) > d * DBL_EPSILON * lmax) ? 1.0 / l : 0.0;   // scipy pinv cut-off
+    return sqrt(l > 0.0 ? l : 0.0);
+}
+
+// block t of the Hermitian matrix in the lower triangle of row-major `src` (what scipy / numpy eigh read)
+template <int d>
+__device__ __forceinline__ Blk lower_blk(const cplx* src, int t) {
+    constexpr int NB = d / 2;
+    const int I = t / NB, J = t % NB;
+    Blk h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int r = 2 * I + (e >> 1), c = 2 * J + (e & 1);
+        const cplx v = r >= c ? src[r * d + c] : src[c * d + r];
+        h.re[e] = v.re;
+        h.im[e] = r > c ? v.im : r < c ? -v.im : 0.0;
+    }
+    return h;
+}
+// block t of the Hermitian part of row-major `src`
+template <int d>
+__device__ __forceinline__ Blk herm_part_blk(const cplx* src, int t) {
+    constexpr int NB = d / 2;
+    const int I = t / NB, J = t % NB;
+    Blk h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int r = 2 * I + (e >> 1), c = 2 * J + (e & 1);
+        const cplx a = src[r * d + c], b = src[c * d + r];
+        h.re[e] = 0.5 * (a.re + b.re); h.im[e] = 0.5 * (a.im - b.im);
+    }
+    return h;
+}
+
 // R operator of tomography.py:273-338 for the state in L.rho; result element of this lane.
 // the register-resident-settings form of r_operator_elem below (designs of at most 64 settings) with the Pauli passes as tables: what
 // the iterative-MLE loop runs.  Same operations in the same order.
@@ -230,11 +302,9 @@ __device__ __forceinline__ cplx r_operator_tab(const DesignDev& des, StateLds<NQ
     FBX_WAVE_SYNC();
     double s0 = 0.0;
     if (mine.valid) {
-        const double pe = mine.cf * L.r[mine.p];
-        const double gp = ((1.0 + mine.e) * 0.5) / ((1.0 + pe) * 0.5 + DBL_MIN);
-        const double gm = ((1.0 - mine.e) * 0.5) / ((1.0 - pe) * 0.5 + DBL_MIN);
-        s0 = 0.5 * (gp + gm);
-        atomicAdd(&L.w[mine.p], mine.cf * 0.5 * (gp - gm));
+        const SettingRatio q = setting_ratio(mine.cf, mine.e, mine.cf * L.r[mine.p]);
+        s0 = q.hs;
+        atomicAdd(&L.w[mine.p], q.hd);
     }
     s0 = wave_sum(s0);
     FBX_WAVE_SYNC();
@@ -245,72 +315,32 @@ __device__ __forceinline__ cplx r_operator_tab(const DesignDev& des, StateLds<NQ
     return out;
 }
 
+// Any number of settings (the reference loops over whatever list it is given, tomography.py:326-336).  Up to 64 KiB of per-setting
+// scratch the weighted half-differences are STAGED in L.hd and lane p adds those of its Pauli in setting order; beyond, they are
+// STREAMED: added to w[p] with LDS atomics as every lane walks its settings (one wavefront: the same order in every run).
 template <int NQ>
-__device__ cplx r_operator_elem(const DesignDev& des, const double* __restrict__ e, StateLds<NQ>& L, int lane,
-                                const LaneSetting* mine = nullptr) {
+__device__ cplx r_operator_elem(const DesignDev& des, const double* __restrict__ e, StateLds<NQ>& L, int lane) {
     constexpr int d = 1 << NQ, D = d * d;
     const int m = des.m;
+    const bool staged = StateLds<NQ>::staged(m);
     pauli_expectations<NQ>(L.rho, L.r, lane);
-    if (mine && m <= 64) {                    // register-resident settings, weights through LDS atomics
-        if (lane < D) L.w[lane] = 0.0;
-        FBX_WAVE_SYNC();
-        double s0 = 0.0;
-        if (mine->valid) {
-            const double pe = mine->cf * L.r[mine->p];
-            const double gp = ((1.0 + mine->e) * 0.5) / ((1.0 + pe) * 0.5 + DBL_MIN);
-            const double gm = ((1.0 - mine->e) * 0.5) / ((1.0 - pe) * 0.5 + DBL_MIN);
-            s0 = 0.5 * (gp + gm);
-            atomicAdd(&L.w[mine->p], mine->cf * 0.5 * (gp - gm));
-        }
-        s0 = wave_sum(s0);
-        FBX_WAVE_SYNC();
-        if (lane < D) L.w[lane] = L.w[lane] / m;
-        FBX_WAVE_SYNC();
-        cplx out; out.re = 0.0; out.im = 0.0;
-        if (lane < D) out = pauli_synthesis<NQ>(L.w, s0 / m + 0.0, lane / d, lane % d);
-        return out;
-    }
-    if (!StateLds<NQ>::staged(m)) {
-        // Streamed (any number of settings; the reference loops over whatever list it is given, tomography.py:326-336): every lane
-        // walks its settings straight from HBM and adds their weights to w[p] with LDS atomics (one wavefront: the same order
-        // in every run) -- no per-setting scratch.
-        if (lane < D) L.w[lane] = 0.0;
-        FBX_WAVE_SYNC();
-        double s0 = 0.0;
-        for (int g = lane; g < m; g += 64) {
-            const int p = des.sp[g] & 0xffff;
-            const double cf = des.unit_coefs ? 1.0 : des.coef[g];
-            const double me = e[des.order[g]], pe = cf * L.r[p];
-            const double gp = ((1.0 + me) * 0.5) / ((1.0 + pe) * 0.5 + DBL_MIN);
-            const double gm = ((1.0 - me) * 0.5) / ((1.0 - pe) * 0.5 + DBL_MIN);
-            s0 += 0.5 * (gp + gm);
-            atomicAdd(&L.w[p], cf * 0.5 * (gp - gm));
-        }
-        s0 = wave_sum(s0);
-        FBX_WAVE_SYNC();
-        if (lane < D) L.w[lane] = L.w[lane] / m;
-        FBX_WAVE_SYNC();
-        cplx out; out.re = 0.0; out.im = 0.0;
-        if (lane < D) out = pauli_synthesis<NQ>(L.w, s0 / m + 0.0, lane / d, lane % d);
-        return out;
-    }
+    if (!staged && lane < D) L.w[lane] = 0.0;
     FBX_WAVE_SYNC();
     double s0 = 0.0;
     for (int g = lane; g < m; g += 64) {
         const int p = des.sp[g] & 0xffff;
         const double cf = des.unit_coefs ? 1.0 : des.coef[g];
-        const double me = e[des.order[g]], pe = cf * L.r[p];
-        const double gp = ((1.0 + me) * 0.5) / ((1.0 + pe) * 0.5 + DBL_MIN);
-        const double gm = ((1.0 - me) * 0.5) / ((1.0 - pe) * 0.5 + DBL_MIN);
-        L.hs[g] = 0.5 * (gp + gm);
-        L.hd[g] = cf * 0.5 * (gp - gm);
-        s0 += 0.5 * (gp + gm);
+        const SettingRatio q = setting_ratio(cf, e[des.order[g]], cf * L.r[p]);
+        if (staged) { L.hs[g] = q.hs; L.hd[g] = q.hd; }
+        else atomicAdd(&L.w[p], q.hd);
+        s0 += q.hs;
     }
     s0 = wave_sum(s0);
     FBX_WAVE_SYNC();
     if (lane < D) {
         double acc = 0.0;
-        for (int g = 0; g < m; ++g) if ((int)(des.sp[g] & 0xffff) == lane) acc += L.hd[g];
+        if (staged) { for (int g = 0; g < m; ++g) if ((int)(des.sp[g] & 0xffff) == lane) acc += L.hd[g]; }
+        else acc = L.w[lane];
         L.w[lane] = acc / m;
     }
     FBX_WAVE_SYNC();
@@ -321,26 +351,13 @@ __device__ cplx r_operator_elem(const DesignDev& des, const double* __restrict__
 }
 
 // Hermitian function of a d x d matrix staged row-major in `src`: out = V f(lambda) V^H with
-// f selected by `fn` (0: log, 1: pseudo-inverse, 2: sqrt(max(.,0))); eigenvalues left in L.lam
+// f selected by `fn` (spectral_function); eigenvalues left in L.lam.  The matrix is the lower triangle of
+// `src` (lower_only: what scipy / numpy eigh read) or its Hermitian part.
 template <int NQ>
 __device__ void herm_function(const cplx* src, cplx* dst, int fn, StateLds<NQ>& L, int lane, bool lower_only) {
     constexpr int d = 1 << NQ, NB = d / 2;
     Blk h = blk_zero();
-    if (lane < NB * NB) {
-        const int I = lane / NB, J = lane % NB;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = 2 * I + (e >> 1), c = 2 * J + (e & 1);
-            if (lower_only) {                       // scipy / numpy eigh read the lower triangle
-                if (r > c) { h.re[e] = src[r * d + c].re; h.im[e] = src[r * d + c].im; }
-                else if (r < c) { h.re[e] = src[c * d + r].re; h.im[e] = -src[c * d + r].im; }
-                else { h.re[e] = src[r * d + c].re; h.im[e] = 0.0; }
-            } else {
-                const cplx a = src[r * d + c], b = src[c * d + r];
-                h.re[e] = 0.5 * (a.re + b.re); h.im[e] = 0.5 * (a.im - b.im);
-            }
-        }
-    }
+    if (lane < NB * NB) h = lower_only ? lower_blk<d>(src, lane) : herm_part_blk<d>(src, lane);
     FBX_WAVE_SYNC();
     sys_store<d>(L.Ms, lane, h);
     FBX_WAVE_SYNC();
@@ -348,14 +365,7 @@ __device__ void herm_function(const cplx* src, cplx* dst, int fn, StateLds<NQ>& 
     double lmax = 0.0;
     if (lane < d) lmax = fabs(L.Ms[sys_index<d>(lane, lane)].re);
     lmax = wave_max(lmax);
-    if (lane < d) {
-        const double l = L.Ms[sys_index<d>(lane, lane)].re;
-        double f;
-        if (fn == 0) f = log(l);
-        else if (fn == 1) f = (fabs(l) > d * DBL_EPSILON * lmax) ? 1.0 / l : 0.0;   // scipy pinv cut-off
-        else f = sqrt(l > 0.0 ? l : 0.0);
-        L.lam[lane] = f;
-    }
+    if (lane < d) L.lam[lane] = spectral_function<d>(fn, L.Ms[sys_index<d>(lane, lane)].re, lmax);
     FBX_WAVE_SYNC();
     const Blk o = reconstruct_blk<d>(L.Vs, L.lam, lane);
     blk_store<d, d>(dst, lane, o);
@@ -407,7 +417,7 @@ mle_state_body(char* smem, const DesignDev& des, long long B, const double* __re
         if (iteration >= maxiter) { hit = 1; break; }            // tomography.py:244-246
         cplx T;                                                    // R(rho)
         if constexpr (PLAIN) T = r_operator_tab<NQ>(des, L, lane, mine, tab);
-        else T = des.m <= 64 ? r_operator_tab<NQ>(des, L, lane, mine, tab) : r_operator_elem<NQ>(des, e, L, lane, &mine);
+        else T = des.m <= 64 ? r_operator_tab<NQ>(des, L, lane, mine, tab) : r_operator_elem<NQ>(des, e, L, lane);
         if (act && row == col) T.re -= 1.0;                        // Tk = R - I
         if (!PLAIN && entropy_penalty > 0.0) {                     // tomography.py:252-254
             herm_function<NQ>(L.rho, L.aux, 0, L, lane, false);    // logm(rho)
@@ -437,11 +447,7 @@ mle_state_body(char* smem, const DesignDev& des, long long B, const double* __re
         cplx nr = matmul_elem<NQ>(L.U, L.tmp, lane);               // U rho U
         double tr_re = (act && row == col) ? nr.re : 0.0, tr_im = (act && row == col) ? nr.im : 0.0;
         tr_re = wave_sum(tr_re); tr_im = wave_sum(tr_im);
-        {   // complex division by the trace
-            const double den = tr_re * tr_re + tr_im * tr_im;
-            const double qr = (nr.re * tr_re + nr.im * tr_im) / den, qi = (nr.im * tr_re - nr.re * tr_im) / den;
-            nr.re = qr; nr.im = qi;
-        }
+        nr = div_by_trace(nr, tr_re, tr_im);
         double diff = act ? (nr.re - rho.re) * (nr.re - rho.re) + (nr.im - rho.im) * (nr.im - rho.im) : 0.0;
         diff = uniform(wave_sum(diff));
         rho = nr;
@@ -524,11 +530,9 @@ mle_state_packed_kernel(DesignDev des, long long B, const double* __restrict__ e
         FBX_WAVE_SYNC();
         double s0 = 0.0;
         if (has) {
-            const double pe = cf * r_l[sp];
-            const double gp = ((1.0 + me) * 0.5) / ((1.0 + pe) * 0.5 + DBL_MIN);
-            const double gm = ((1.0 - me) * 0.5) / ((1.0 - pe) * 0.5 + DBL_MIN);
-            s0 = 0.5 * (gp + gm);
-            atomicAdd(&w_l[sp], cf * 0.5 * (gp - gm));
+            const SettingRatio q = setting_ratio(cf, me, cf * r_l[sp]);
+            s0 = q.hs;
+            atomicAdd(&w_l[sp], q.hd);
         }
         s0 = group_sum<D>(s0);
         FBX_WAVE_SYNC();
@@ -545,11 +549,7 @@ mle_state_packed_kernel(DesignDev des, long long B, const double* __restrict__ e
         FBX_WAVE_SYNC();
         cplx nr = matmul_elem<NQ>(U_l, tmp_l, t);                               // U rho U
         const double tr_re = group_sum<D>((row == col) ? nr.re : 0.0), tr_im = group_sum<D>((row == col) ? nr.im : 0.0);
-        {
-            const double den = tr_re * tr_re + tr_im * tr_im;
-            const double qr = (nr.re * tr_re + nr.im * tr_im) / den, qi = (nr.im * tr_re - nr.re * tr_im) / den;
-            nr.re = qr; nr.im = qi;
-        }
+        nr = div_by_trace(nr, tr_re, tr_im);
         const double diff = group_sum<D>((nr.re - rho.re) * (nr.re - rho.re) + (nr.im - rho.im) * (nr.im - rho.im));
         FBX_WAVE_SYNC();
         if (running) { rho = nr; rho_l[t] = rho; }
@@ -593,16 +593,7 @@ loglik_kernel(DesignDev des, long long B, const double* __restrict__ rho_in, con
     FBX_WAVE_SYNC();
     pauli_expectations<NQ>(L.rho, L.r, lane);
     FBX_WAVE_SYNC();
-    double ll = 0.0;
-    for (int g = lane; g < des.m; g += 64) {
-        const int k = des.order[g], p = des.sp[g] & 0xffff;
-        const double cf = des.unit_coefs ? 1.0 : des.coef[g];
-        const double n = counts[item * des.m + k], me = expect[item * des.m + k], pe = cf * L.r[p];
-        const double pp = (1.0 + pe) / 2, pm = (1.0 - pe) / 2;
-        if (pp > 0.0) ll += n * (1.0 + me) / 2 * log10(pp);
-        if (pm > 0.0) ll += n * (1.0 - me) / 2 * log10(pm);
-    }
-    ll = wave_sum(ll);
+    const double ll = wave_sum(loglik_partial<64>(des, expect + item * des.m, counts + item * des.m, L.r, lane));
     if (lane == 0) ll_out[item] = ll;
 }
 
@@ -645,23 +636,13 @@ proj_state_kernel(long long B, const double* __restrict__ rho_in, double* __rest
     if (act) { v.re = rho_in[(item * D + lane) * 2]; v.im = rho_in[(item * D + lane) * 2 + 1]; }
     double tr_re = (act && lane / d == lane % d) ? v.re : 0.0, tr_im = (act && lane / d == lane % d) ? v.im : 0.0;
     tr_re = wave_sum(tr_re); tr_im = wave_sum(tr_im);
-    const double den = tr_re * tr_re + tr_im * tr_im;
-    cplx q; q.re = (v.re * tr_re + v.im * tr_im) / den; q.im = (v.im * tr_re - v.re * tr_im) / den;
+    const cplx q = div_by_trace(v, tr_re, tr_im);
     if (act) L.rho[lane] = q;
     FBX_WAVE_SYNC();
     // eigh (lower triangle, like scipy.linalg.eigh)
     constexpr int NB = d / 2;
     Blk h = blk_zero();
-    if (lane < NB * NB) {
-        const int I = lane / NB, J = lane % NB;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = 2 * I + (e >> 1), c = 2 * J + (e & 1);
-            if (r > c) { h.re[e] = L.rho[r * d + c].re; h.im[e] = L.rho[r * d + c].im; }
-            else if (r < c) { h.re[e] = L.rho[c * d + r].re; h.im[e] = -L.rho[c * d + r].im; }
-            else { h.re[e] = L.rho[r * d + c].re; h.im[e] = 0.0; }
-        }
-    }
+    if (lane < NB * NB) h = lower_blk<d>(L.rho, lane);
     sys_store<d>(L.Ms, lane, h);
     FBX_WAVE_SYNC();
     jacobi_eigh_lds<d>(L.Ms, L.Vs, L.rec, lane);
@@ -744,382 +725,6 @@ state_measures_kernel(long long B, const double* __restrict__ rho_in, const doub
     }
 }
 
-// generic batched eigh (lower triangle read, ascending eigenvalues, eigenvectors as columns).
-// One workgroup of NT = max(64, (N/2)^2) threads per matrix: one wavefront up to 16 x 16, four for
-// 32 x 32, sixteen for 64 x 64 (128 KiB of LDS for the matrix and the eigenvectors).
-template <int N, int NT>
-__global__ void __launch_bounds__(NT)
-eigh_kernel(long long B, const double* __restrict__ a, double* __restrict__ w_out, double* __restrict__ v_out) {
-    constexpr int NB = N / 2;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    cplx* Ms = (cplx*)smem;
-    cplx* Vs = Ms + sys_elems<N>();
-    double* lam = (double*)(Vs + sys_elems<N>());
-    double* red = lam + N;
-    int* pos = (int*)(red + 64);
-    const int lane = threadIdx.x;
-    const long long item = blockIdx.x;
-    const double* src = a + item * (long long)N * N * 2;
-    Blk h = blk_zero();
-    int nonfinite = 0;                  // over the entries read: the diagonal's real parts and the strictly lower triangle
-    if (lane < NB * NB) {
-        const int I = lane / NB, J = lane % NB;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = 2 * I + (e >> 1), c = 2 * J + (e & 1);
-            if (r > c) { h.re[e] = src[2 * (r * N + c)]; h.im[e] = src[2 * (r * N + c) + 1]; }
-            else if (r < c) { h.re[e] = src[2 * (c * N + r)]; h.im[e] = -src[2 * (c * N + r) + 1]; }
-            else { h.re[e] = src[2 * (r * N + c)]; h.im[e] = 0.0; }
-            nonfinite |= !(isfinite(h.re[e]) && isfinite(h.im[e]));
-        }
-    }
-    // A non-finite item gives NaN for itself only (include/fbx.h): the solver's stopping test is false on a NaN and would
-    // hand back the sorted diagonal with the identity.  The item is solved as the zero matrix and NaN is written in its place.
-    nonfinite = __syncthreads_or(nonfinite);
-    if (nonfinite) h = blk_zero();
-    sys_store<N>(Ms, lane, h);
-    __syncthreads();
-    jacobi_eigh_block<N, NT>(Ms, Vs, lane, true, red);
-    if (nonfinite) {
-        const double nan = __longlong_as_double(0x7ff8000000000000LL);
-        if (lane < N) w_out[item * N + lane] = nan;
-        if (v_out) for (int idx = lane; idx < 2 * N * N; idx += NT) v_out[item * N * N * 2 + idx] = nan;
-        return;
-    }
-    if (lane < N) lam[lane] = Ms[sys_index<N>(lane, lane)].re;
-    __syncthreads();
-    if (lane < N) {                     // rank of eigenvalue `lane` in ascending order (stable)
-        int rank = 0;
-        for (int j = 0; j < N; ++j) rank += (lam[j] < lam[lane]) || (lam[j] == lam[lane] && j < lane);
-        pos[lane] = rank;
-        w_out[item * N + rank] = lam[lane];
-    }
-    __syncthreads();
-    if (v_out) {
-        for (int idx = lane; idx < N * N; idx += NT) {
-            const int r = idx / N, k = idx % N;
-            const cplx v = Vs[sys_index<N>(r, k)];
-            double* o = v_out + ((item * N + r) * N + pos[k]) * 2;
-            o[0] = v.re; o[1] = v.im;
-        }
-    }
-}
-
-// ---- Hermitian eigendecomposition for 64 < N <= 1024 (4- and 5-qubit Choi matrices, padded odd sizes): the same
-// systolic two-sided Jacobi with the matrix and the eigenvectors in HBM / L2 instead of LDS.  One 1024-thread
-// workgroup per matrix; a round = (a) the N/2 rotations from the pivot blocks into an LDS table, (b) every 2 x 2
-// block rotated and written to the seats the tournament permutation assigns it -- from the `cur` copies into the
-// `nxt` copies, so no entry is overwritten before it is read -- and the copies swap.  Correctness first: this
-// serves validators, choi2kraus and sqrtm of large operators, not a benchmark (one CU per matrix, ~20 us per round).
-__device__ __forceinline__ int jacobi_seat_rt(int NB, int s) {           // jacobi_seat<N> with N at run time
-    if (NB == 1) return s;
-    const int k = s >> 1;
-    if ((s & 1) == 0) {
-        if (k == 0) return 0;
-        if (k == NB - 1) return 2 * (NB - 1) + 1;
-        return 2 * (k + 1);
-    }
-    if (k == 0) return 2;
-    return 2 * (k - 1) + 1;
-}
-
-__global__ void __launch_bounds__(1024)
-eigh_big_kernel(int N, long long B, const double* __restrict__ a, double* __restrict__ w_out, double* __restrict__ v_out,
-                cplx* __restrict__ work) {
-    constexpr int NT = 1024;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double* rot = (double*)smem;                 // [N/2][4]: c, sr, si, -
-    double* lam = rot + 2 * N;                   // [N]
-    int* pos = (int*)(lam + N);                  // [N]
-    double* red = (double*)(pos + N);            // [64]
-    const int t = threadIdx.x, NB = N / 2;
-    const long long item = blockIdx.x;
-    const size_t NN = (size_t)N * N;
-    cplx* M0 = work + (size_t)item * 4 * NN;
-    cplx* M1 = M0 + NN; cplx* V0 = M1 + NN; cplx* V1 = V0 + NN;
-    const double* src = a + item * (long long)NN * 2;
-    int nonfinite = 0;
-    for (size_t idx = t; idx < NN; idx += NT) {            // numpy eigh: the lower triangle defines the matrix
-        const int r = (int)(idx / N), c = (int)(idx % N);
-        cplx h, v;
-        if (r > c) { h.re = src[2 * idx]; h.im = src[2 * idx + 1]; }
-        else if (r < c) { h.re = src[2 * ((size_t)c * N + r)]; h.im = -src[2 * ((size_t)c * N + r) + 1]; }
-        else { h.re = src[2 * idx]; h.im = 0.0; }
-        nonfinite |= !(isfinite(h.re) && isfinite(h.im));
-        v.re = r == c ? 1.0 : 0.0; v.im = 0.0;
-        M0[idx] = h; V0[idx] = v;
-    }
-    if (__syncthreads_or(nonfinite)) {                     // a non-finite item gives NaN for itself only (include/fbx.h)
-        const double nan = __longlong_as_double(0x7ff8000000000000LL);
-        for (int k = t; k < N; k += NT) w_out[item * N + k] = nan;
-        if (v_out) for (size_t idx = t; idx < 2 * NN; idx += NT) v_out[(size_t)item * NN * 2 + idx] = nan;
-        return;
-    }
-    cplx *Mc = M0, *Mn = M1, *Vc = V0, *Vn = V1;
-    for (int sweep = 0; sweep < FBX_JACOBI_MAX_SWEEPS; ++sweep) {
-        double o2 = 0.0, n2 = 0.0;
-        for (size_t idx = t; idx < NN; idx += NT) {
-            const cplx v = Mc[idx];
-            const double a2 = v.re * v.re + v.im * v.im;
-            n2 += a2;
-            if (idx / N != idx % N) o2 += a2;
-        }
-        block_sum2<NT>(o2, n2, red);
-        if (!(o2 > FBX_JACOBI_TOL2 * n2)) break;
-        for (int r = 0; r < N - 1; ++r) {
-            for (int p = t; p < NB; p += NT) {
-                const cplx b = Mc[(size_t)(2 * p) * N + 2 * p + 1];
-                const JRot q = jacobi_rotation(Mc[(size_t)(2 * p) * N + 2 * p].re, Mc[(size_t)(2 * p + 1) * N + 2 * p + 1].re, b.re, b.im);
-                rot[4 * p] = q.c; rot[4 * p + 1] = q.sr; rot[4 * p + 2] = q.si;
-            }
-            __syncthreads();
-            for (int blk = t; blk < NB * NB; blk += NT) {
-                const int I = blk / NB, J = blk % NB;
-                const size_t r0 = (size_t)(2 * I) * N + 2 * J, r1 = r0 + N;
-                cplx m00 = Mc[r0], m01 = Mc[r0 + 1], m10 = Mc[r1], m11 = Mc[r1 + 1];
-                cplx v0p = Vc[r0], v0q = Vc[r0 + 1], v1p = Vc[r1], v1q = Vc[r1 + 1];
-                const double cJ = rot[4 * J], sJr = rot[4 * J + 1], sJi = rot[4 * J + 2];
-                jacobi_apply_m(rot[4 * I], rot[4 * I + 1], rot[4 * I + 2], cJ, sJr, sJi, m00, m01, m10, m11);
-                jacobi_apply_v(cJ, sJr, sJi, v0p, v0q, v1p, v1q);
-                if (I == J) { m01.re = m01.im = 0.0; m10.re = m10.im = 0.0; m00.im = 0.0; m11.im = 0.0; }
-                const size_t ra = (size_t)jacobi_seat_rt(NB, 2 * I) * N, rb = (size_t)jacobi_seat_rt(NB, 2 * I + 1) * N;
-                const int ca = jacobi_seat_rt(NB, 2 * J), cb = jacobi_seat_rt(NB, 2 * J + 1);
-                Mn[ra + ca] = m00; Mn[ra + cb] = m01; Mn[rb + ca] = m10; Mn[rb + cb] = m11;
-                const size_t va = (size_t)(2 * I) * N, vb = va + N;                  // eigenvector ROWS stay, columns move
-                Vn[va + ca] = v0p; Vn[va + cb] = v0q; Vn[vb + ca] = v1p; Vn[vb + cb] = v1q;
-            }
-            __syncthreads();
-            cplx* q = Mc; Mc = Mn; Mn = q; q = Vc; Vc = Vn; Vn = q;
-        }
-    }
-    // (after whole sweeps the seats are the indices again)
-    for (int k = t; k < N; k += NT) lam[k] = Mc[(size_t)k * N + k].re;
-    __syncthreads();
-    for (int k = t; k < N; k += NT) {               // rank of eigenvalue k in ascending order (stable)
-        int rank = 0;
-        for (int j = 0; j < N; ++j) rank += (lam[j] < lam[k]) || (lam[j] == lam[k] && j < k);
-        pos[k] = rank;
-        w_out[item * N + rank] = lam[k];
-    }
-    __syncthreads();
-    if (v_out) {
-        for (size_t idx = t; idx < NN; idx += NT) {
-            const int r = (int)(idx / N), k = (int)(idx % N);
-            const cplx v = Vc[idx];
-            double* o = v_out + ((item * N + r) * N + pos[k]) * 2;
-            o[0] = v.re; o[1] = v.im;
-        }
-    }
-}
-
-// ---- the same decomposition with ONE matrix spread over the chip: a cooperative launch (every workgroup resident),
-// each workgroup takes a share of the 2 x 2 blocks of a round, computes the round's N/2 rotations for itself (they
-// are cheap and every block needs two of them), and a grid-wide barrier separates the rounds.  One CU moves the
-// 4 N^2 x 16 bytes of a round at ~85 GB/s; the chip moves them at L2 / HBM speed, so the barrier (a few microseconds)
-// becomes the cost of a round.  hipLaunchCooperativeKernel refuses a grid that cannot be co-resident, in which case
-// (or with fbx_set_option("eigh_cooperative", 0)) the single-workgroup kernel above takes over.
-__global__ void __launch_bounds__(256)
-eigh_coop_kernel(int N, const double* __restrict__ a, double* __restrict__ w_out, double* __restrict__ v_out,
-                 cplx* __restrict__ work, double* __restrict__ partial) {
-    namespace cg = cooperative_groups;
-    cg::grid_group grid = cg::this_grid();
-    constexpr int NT = 256;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double* rot = (double*)smem;                 // [N/2][4]
-    double* red = rot + 2 * N;                   // [16]
-    const int t = threadIdx.x, NB = N / 2, G = gridDim.x, g = blockIdx.x;
-    const size_t NN = (size_t)N * N;
-    cplx* M0 = work; cplx* M1 = M0 + NN; cplx* V0 = M1 + NN; cplx* V1 = V0 + NN;
-    int nonfinite = 0;
-    for (size_t idx = (size_t)g * NT + t; idx < NN; idx += (size_t)G * NT) {
-        const int r = (int)(idx / N), c = (int)(idx % N);
-        cplx h, v;
-        if (r > c) { h.re = a[2 * idx]; h.im = a[2 * idx + 1]; }
-        else if (r < c) { h.re = a[2 * ((size_t)c * N + r)]; h.im = -a[2 * ((size_t)c * N + r) + 1]; }
-        else { h.re = a[2 * idx]; h.im = 0.0; }
-        nonfinite |= !(isfinite(h.re) && isfinite(h.im));
-        v.re = r == c ? 1.0 : 0.0; v.im = 0.0;
-        M0[idx] = h; V0[idx] = v;
-    }
-    // a non-finite matrix gives NaN (include/fbx.h): every workgroup publishes what it saw in the slots of `partial` that
-    // are next written by the ranks at the end (G <= N), and all of them leave together
-    nonfinite = __syncthreads_or(nonfinite);
-    if (t == 0) partial[2 * G + g] = nonfinite ? 1.0 : 0.0;
-    grid.sync();
-    nonfinite = 0;
-    for (int k = 0; k < G; ++k) nonfinite |= partial[2 * G + k] != 0.0;
-    if (nonfinite) {
-        const double nan = __longlong_as_double(0x7ff8000000000000LL);
-        for (size_t idx = (size_t)g * NT + t; idx < (size_t)N; idx += (size_t)G * NT) w_out[idx] = nan;
-        if (v_out) for (size_t idx = (size_t)g * NT + t; idx < 2 * NN; idx += (size_t)G * NT) v_out[idx] = nan;
-        return;
-    }
-    cplx *Mc = M0, *Mn = M1, *Vc = V0, *Vn = V1;
-    for (int sweep = 0; sweep < FBX_JACOBI_MAX_SWEEPS; ++sweep) {
-        double o2 = 0.0, n2 = 0.0;
-        for (size_t idx = (size_t)g * NT + t; idx < NN; idx += (size_t)G * NT) {
-            const cplx v = Mc[idx];
-            const double a2 = v.re * v.re + v.im * v.im;
-            n2 += a2;
-            if (idx / N != idx % N) o2 += a2;
-        }
-        block_sum2<NT>(o2, n2, red);
-        if (t == 0) { partial[2 * g] = o2; partial[2 * g + 1] = n2; }
-        grid.sync();
-        o2 = 0.0; n2 = 0.0;
-        for (int k = 0; k < G; ++k) { o2 += partial[2 * k]; n2 += partial[2 * k + 1]; }      // same order in every workgroup
-        grid.sync();                                  // `partial` is rewritten at the next sweep
-        if (!(o2 > FBX_JACOBI_TOL2 * n2)) break;
-        for (int r = 0; r < N - 1; ++r) {
-            for (int p = t; p < NB; p += NT) {
-                const cplx b = Mc[(size_t)(2 * p) * N + 2 * p + 1];
-                const JRot q = jacobi_rotation(Mc[(size_t)(2 * p) * N + 2 * p].re, Mc[(size_t)(2 * p + 1) * N + 2 * p + 1].re, b.re, b.im);
-                rot[4 * p] = q.c; rot[4 * p + 1] = q.sr; rot[4 * p + 2] = q.si;
-            }
-            __syncthreads();
-            for (int blk = g * NT + t; blk < NB * NB; blk += G * NT) {
-                const int I = blk / NB, J = blk % NB;
-                const size_t r0 = (size_t)(2 * I) * N + 2 * J, r1 = r0 + N;
-                cplx m00 = Mc[r0], m01 = Mc[r0 + 1], m10 = Mc[r1], m11 = Mc[r1 + 1];
-                cplx v0p = Vc[r0], v0q = Vc[r0 + 1], v1p = Vc[r1], v1q = Vc[r1 + 1];
-                const double cJ = rot[4 * J], sJr = rot[4 * J + 1], sJi = rot[4 * J + 2];
-                jacobi_apply_m(rot[4 * I], rot[4 * I + 1], rot[4 * I + 2], cJ, sJr, sJi, m00, m01, m10, m11);
-                jacobi_apply_v(cJ, sJr, sJi, v0p, v0q, v1p, v1q);
-                if (I == J) { m01.re = m01.im = 0.0; m10.re = m10.im = 0.0; m00.im = 0.0; m11.im = 0.0; }
-                const size_t ra = (size_t)jacobi_seat_rt(NB, 2 * I) * N, rb = (size_t)jacobi_seat_rt(NB, 2 * I + 1) * N;
-                const int ca = jacobi_seat_rt(NB, 2 * J), cb = jacobi_seat_rt(NB, 2 * J + 1);
-                Mn[ra + ca] = m00; Mn[ra + cb] = m01; Mn[rb + ca] = m10; Mn[rb + cb] = m11;
-                const size_t va = (size_t)(2 * I) * N, vb = va + N;
-                Vn[va + ca] = v0p; Vn[va + cb] = v0q; Vn[vb + ca] = v1p; Vn[vb + cb] = v1q;
-            }
-            grid.sync();
-            cplx* q = Mc; Mc = Mn; Mn = q; q = Vc; Vc = Vn; Vn = q;
-        }
-    }
-    // eigenvalues ascending, eigenvectors as columns in that order (ranks recomputed by every thread that needs one)
-    for (size_t idx = (size_t)g * NT + t; idx < (size_t)N; idx += (size_t)G * NT) {
-        const int k = (int)idx;
-        const double lk = Mc[(size_t)k * N + k].re;
-        int rank = 0;
-        for (int j = 0; j < N; ++j) { const double lj = Mc[(size_t)j * N + j].re; rank += (lj < lk) || (lj == lk && j < k); }
-        w_out[rank] = lk;
-        partial[2 * G + k] = (double)rank;            // column k goes to column `rank`
-    }
-    grid.sync();
-    if (v_out) {
-        for (size_t idx = (size_t)g * NT + t; idx < NN; idx += (size_t)G * NT) {
-            const int r = (int)(idx / N), k = (int)(idx % N);
-            const cplx v = Vc[idx];
-            double* o = v_out + ((size_t)r * N + (int)partial[2 * G + k]) * 2;
-            o[0] = v.re; o[1] = v.im;
-        }
-    }
-}
-
-static int launch_eigh_coop(int N, int64_t B, const double* da, double* dw, double* dv, bool* done) {
-    *done = false;
-    if (!option_eigh_cooperative()) return FBX_OK;
-    int dev = current_device(), coop = 0, cus = 0;
-    if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev) != hipSuccess || !coop) { (void)hipGetLastError(); return FBX_OK; }
-    FBX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const size_t lds = sizeof(double) * (2 * (size_t)N + 16);
-    int per_cu = 0;
-    FBX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, eigh_coop_kernel, 256, lds));
-    if (per_cu < 1) return FBX_OK;
-    const long long blocks_needed = ((long long)(N / 2) * (N / 2) + 255) / 256;
-    long long G = std::min<long long>(blocks_needed, (long long)cus * std::min(per_cu, 2));
-    if (G < 2) return FBX_OK;
-    const size_t NN = (size_t)N * N;
-    void* w = nullptr;
-    { const int rc = workspace(WS_CONVERT, 4 * NN * sizeof(cplx) + sizeof(double) * (2 * (size_t)G + N), &w); if (rc) return rc; }
-    cplx* work = (cplx*)w;
-    double* partial = (double*)(work + 4 * NN);
-    for (int64_t b = 0; b < B; ++b) {
-        const double* a = da + b * NN * 2;
-        double* wo = dw + b * N;
-        double* vo = dv ? dv + b * NN * 2 : nullptr;
-        int n_arg = N;
-        void* args[] = {&n_arg, (void*)&a, (void*)&wo, (void*)&vo, (void*)&work, (void*)&partial};
-        const hipError_t e = hipLaunchCooperativeKernel((const void*)eigh_coop_kernel, dim3((unsigned)G), dim3(256), args, (unsigned)lds, stream());
-        if (e != hipSuccess) { (void)hipGetLastError(); if (b == 0) return FBX_OK; return hip_fail(e, "hipLaunchCooperativeKernel", __FILE__, __LINE__); }
-    }
-    *done = true;
-    return FBX_OK;
-}
-
-static int launch_eigh_big(int N, int64_t B, const double* da, double* dw, double* dv) {
-    const size_t lds = sizeof(double) * (2 * (size_t)N + N + 64) + sizeof(int) * N;
-    const size_t per_item = 4 * (size_t)N * N * sizeof(cplx);
-    const int64_t chunk = (int64_t)std::max<size_t>(1, std::min<size_t>((size_t)B, ((size_t)1 << 30) / per_item));
-    void* w = nullptr;
-    { const int rc = workspace(WS_CONVERT, per_item * (size_t)chunk, &w); if (rc) return rc; }
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
-        hipLaunchKernelGGL(eigh_big_kernel, dim3((unsigned)nb), dim3(1024), lds, stream(), N, (long long)nb,
-                           da + b0 * (size_t)N * N * 2, dw + b0 * N, dv ? dv + b0 * (size_t)N * N * 2 : nullptr, (cplx*)w);
-    }
-    FBX_HIP(hipGetLastError());
-    return FBX_OK;
-}
-
-// ---- out = op(A) diag(s) op(B) for stacks of N x N complex matrices, N up to 1024: the products around the large
-// eigensolver (V f(lambda) V^H of sqrtm_psd, calculational.py:77-91; sqrt(rho) sigma sqrt(rho) of fidelity,
-// distance_measures.py:64-84).  16 x 16 output tiles staged through LDS; a utility, not a tuned GEMM.
-__global__ void __launch_bounds__(256)
-matmul_kernel(int N, long long B, const double* __restrict__ a, int conj_t_a, const double* __restrict__ scale,
-              const double* __restrict__ b, int conj_t_b, double* __restrict__ out) {
-    __shared__ cplx As[16][17], Bs[16][17];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int tiles = (N + 15) / 16;
-    const long long item = blockIdx.x / (tiles * tiles);
-    const int tile = (int)(blockIdx.x % (tiles * tiles)), row0 = (tile / tiles) * 16, col0 = (tile % tiles) * 16;
-    const double* pa = a + item * (long long)N * N * 2;
-    const double* pb = b + item * (long long)N * N * 2;
-    double re = 0.0, im = 0.0;
-    for (int k0 = 0; k0 < N; k0 += 16) {
-        {   // As[ty][tx] = op(A)[row0 + ty][k0 + tx] * s[k0 + tx];  Bs[ty][tx] = op(B)[k0 + ty][col0 + tx]
-            const int r = row0 + ty, k = k0 + tx;
-            cplx v; v.re = 0.0; v.im = 0.0;
-            if (r < N && k < N) {
-                const long long idx = conj_t_a ? (long long)k * N + r : (long long)r * N + k;
-                v.re = pa[2 * idx]; v.im = conj_t_a ? -pa[2 * idx + 1] : pa[2 * idx + 1];
-                if (scale) { const double sc = scale[item * N + k]; v.re *= sc; v.im *= sc; }
-            }
-            As[ty][tx] = v;
-            const int kk = k0 + ty, c = col0 + tx;
-            cplx w; w.re = 0.0; w.im = 0.0;
-            if (kk < N && c < N) {
-                const long long idx = conj_t_b ? (long long)c * N + kk : (long long)kk * N + c;
-                w.re = pb[2 * idx]; w.im = conj_t_b ? -pb[2 * idx + 1] : pb[2 * idx + 1];
-            }
-            Bs[ty][tx] = w;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const cplx x = As[ty][k], y = Bs[k][tx];
-            re += x.re * y.re - x.im * y.im;
-            im += x.re * y.im + x.im * y.re;
-        }
-        __syncthreads();
-    }
-    const int r = row0 + ty, c = col0 + tx;
-    if (r < N && c < N) {
-        double* o = out + (item * (long long)N * N + (long long)r * N + c) * 2;
-        o[0] = re; o[1] = im;
-    }
-}
-
-template <int N>
-static int launch_eigh(int64_t B, const double* da, double* dw, double* dv) {
-    constexpr int NT = (N / 2) * (N / 2) > 64 ? (N / 2) * (N / 2) : 64;
-    const size_t lds = 2 * sizeof(cplx) * sys_elems<N>() + sizeof(double) * (N + 64) + sizeof(int) * N;
-    auto kern = eigh_kernel<N, NT>;
-    FBX_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(NT), lds, stream(), (long long)B, da, dw, dv);
-    FBX_HIP(hipGetLastError());
-    return FBX_OK;
-}
 
 }  // namespace fbx
 
@@ -1165,11 +770,9 @@ __device__ cplx r_operator_big(const DesignDev& des, const double* __restrict__ 
     for (int g = t; g < m; g += NT) {
         const int p = des.sp[g] & 0xffff;
         const double cf = des.unit_coefs ? 1.0 : des.coef[g];
-        const double me = e[des.order[g]], pe = cf * L.r[p];
-        const double gp = ((1.0 + me) * 0.5) / ((1.0 + pe) * 0.5 + DBL_MIN);
-        const double gm = ((1.0 - me) * 0.5) / ((1.0 - pe) * 0.5 + DBL_MIN);
-        s0 += 0.5 * (gp + gm);
-        atomicAdd(&L.w[p], cf * 0.5 * (gp - gm));
+        const SettingRatio q = setting_ratio(cf, e[des.order[g]], cf * L.r[p]);
+        s0 += q.hs;
+        atomicAdd(&L.w[p], q.hd);
     }
     s0 = big_sum<NQ>(s0, L);                            // (two barriers: the atomics above are complete behind them)
     L.w[t] = L.w[t] / m;
@@ -1184,15 +787,7 @@ template <int NQ>
 __device__ void herm_function_big(const cplx* src, cplx* dst, int fn, StateBigLds<NQ>& L, int t) {
     constexpr int d = 1 << NQ, NB = d / 2, NT = d * d;
     Blk h = blk_zero();
-    if (t < NB * NB) {
-        const int I = t / NB, J = t % NB;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = 2 * I + (e >> 1), c = 2 * J + (e & 1);
-            const cplx a = src[r * d + c], b = src[c * d + r];
-            h.re[e] = 0.5 * (a.re + b.re); h.im[e] = 0.5 * (a.im - b.im);
-        }
-    }
+    if (t < NB * NB) h = herm_part_blk<d>(src, t);
     __syncthreads();
     sys_store<d>(L.Ms, t, h);
     __syncthreads();
@@ -1201,14 +796,7 @@ __device__ void herm_function_big(const cplx* src, cplx* dst, int fn, StateBigLd
     double lmax = 0.0;
     if (t < d) lmax = fabs(L.Ms[sys_index<d>(t, t)].re);
     lmax = wave_max(lmax);                                   // d <= 32: the diagonal sits in the first wavefront
-    if (t < d) {
-        const double l = L.Ms[sys_index<d>(t, t)].re;
-        double f;
-        if (fn == 0) f = log(l);
-        else if (fn == 1) f = (fabs(l) > d * DBL_EPSILON * lmax) ? 1.0 / l : 0.0;
-        else f = sqrt(l > 0.0 ? l : 0.0);
-        L.lam[t] = f;
-    }
+    if (t < d) L.lam[t] = spectral_function<d>(fn, L.Ms[sys_index<d>(t, t)].re, lmax);
     __syncthreads();
     const Blk o = reconstruct_blk<d>(L.Vs, L.lam, t);
     blk_store<d, d>(dst, t, o);
@@ -1279,11 +867,7 @@ mle_state_big_kernel(DesignDev des, long long B, const double* __restrict__ expe
         cplx nr = matmul_big<NQ>(L.U, L.tmp, t);
         double tr_re = (row == col) ? nr.re : 0.0, tr_im = (row == col) ? nr.im : 0.0;
         tr_re = big_sum<NQ>(tr_re, L); tr_im = big_sum<NQ>(tr_im, L);
-        {
-            const double den = tr_re * tr_re + tr_im * tr_im;
-            const double qr = (nr.re * tr_re + nr.im * tr_im) / den, qi = (nr.im * tr_re - nr.re * tr_im) / den;
-            nr.re = qr; nr.im = qi;
-        }
+        nr = div_by_trace(nr, tr_re, tr_im);
         double diff = (nr.re - rho.re) * (nr.re - rho.re) + (nr.im - rho.im) * (nr.im - rho.im);
         diff = big_sum<NQ>(diff, L);
         rho = nr;
@@ -1336,16 +920,7 @@ state_big_kernel(int op, DesignDev des, long long B, const double* __restrict__ 
     }
     pauli_expectations<NQ>(L.rho, L.r, t);
     __syncthreads();
-    double ll = 0.0;
-    for (int g = t; g < m; g += NT) {
-        const int k = des.order[g], p = des.sp[g] & 0xffff;
-        const double cf = des.unit_coefs ? 1.0 : des.coef[g];
-        const double n = counts[item * m + k], me = expect[item * m + k], pe = cf * L.r[p];
-        const double pp = (1.0 + pe) / 2, pm = (1.0 - pe) / 2;
-        if (pp > 0.0) ll += n * (1.0 + me) / 2 * log10(pp);
-        if (pm > 0.0) ll += n * (1.0 - me) / 2 * log10(pm);
-    }
-    ll = big_sum<NQ>(ll, L);
+    const double ll = big_sum<NQ>(loglik_partial<NT>(des, expect + item * m, counts + item * m, L.r, t), L);
     if (t == 0) out[item] = ll;
 }
 
@@ -1386,21 +961,6 @@ struct PostBigLds {
 template <int NT>
 __device__ __forceinline__ void post_sync() { if constexpr (NT > 64) __syncthreads(); else FBX_WAVE_SYNC(); }
 
-// block t of the Hermitian matrix in the lower triangle of row-major `src` (what scipy / numpy eigh read)
-template <int d>
-__device__ __forceinline__ Blk lower_blk(const cplx* src, int t) {
-    constexpr int NB = d / 2;
-    const int I = t / NB, J = t % NB;
-    Blk h;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int r = 2 * I + (e >> 1), c = 2 * J + (e & 1);
-        const cplx v = r >= c ? src[r * d + c] : src[c * d + r];
-        h.re[e] = v.re;
-        h.im[e] = r > c ? v.im : r < c ? -v.im : 0.0;
-    }
-    return h;
-}
 // block t of A * Bm (row-major d x d)
 template <int d>
 __device__ __forceinline__ Blk matmul_blk(const cplx* A, const cplx* Bm, int t) {
@@ -1788,215 +1348,6 @@ int fbx_state_log_likelihood(const fbx_design* design, int64_t B, const double* 
     FBX_TRY(io.in(rho, D * 2 * B, &dr)); FBX_TRY(io.in(expect, m * B, &de)); FBX_TRY(io.in(counts, m * B, &dc));
     FBX_TRY(io.out(ll_out, (size_t)B, &dout));
     FBX_TRY(fbx_state_log_likelihood_dev(design, B, dr, de, dc, dout));
-    return io.finish();
-}
-
-int fbx_matmul_dev(int N, int64_t B, const double* d_a, int conj_t_a, const double* d_scale, const double* d_b, int conj_t_b,
-                   double* d_out) {
-    FBX_REQUIRE(N >= 1 && N <= 1024, "fbx_matmul: N must be in 1..1024");
-    FBX_REQUIRE(B >= 0 && (B == 0 || (d_a && d_b && d_out)), "fbx_matmul: bad batch / NULL buffer");
-    FBX_TRY(ensure_device());
-    if (B == 0) return FBX_OK;
-    const long long tiles = (N + 15) / 16;
-    FBX_REQUIRE(B * tiles * tiles < (1LL << 31), "fbx_matmul: batch too large for one launch");
-    hipLaunchKernelGGL(matmul_kernel, dim3((unsigned)(B * tiles * tiles)), dim3(256), 0, stream(), N, (long long)B, d_a, conj_t_a,
-                       d_scale, d_b, conj_t_b, d_out);
-    FBX_HIP(hipGetLastError());
-    return FBX_OK;
-}
-
-int fbx_matmul(int N, int64_t B, const double* a, int conj_t_a, const double* scale, const double* b, int conj_t_b, double* out) {
-    FBX_REQUIRE(N >= 1 && N <= 1024, "fbx_matmul: N must be in 1..1024");
-    FBX_REQUIRE(B >= 0 && (B == 0 || (a && b && out)), "fbx_matmul: bad batch / NULL buffer");
-    FBX_TRY(ensure_device());
-    if (B == 0) return FBX_OK;
-    const size_t nn = (size_t)N * N * 2 * B;
-    HostIO io; double *da, *db, *ds = nullptr, *dout;
-    FBX_TRY(io.in(a, nn, &da)); FBX_TRY(io.in(b, nn, &db));
-    if (scale) FBX_TRY(io.in(scale, (size_t)N * B, &ds));
-    FBX_TRY(io.out(out, nn, &dout));
-    FBX_TRY(fbx_matmul_dev(N, B, da, conj_t_a, ds, db, conj_t_b, dout));
-    return io.finish();
-}
-
-int fbx_eigh_dev(int N, int64_t B, const double* d_a, double* d_w_out, double* d_v_out) {
-    FBX_REQUIRE(N == 2 || N == 4 || N == 8 || N == 16 || N == 32 || N == 64 || (N > 64 && N <= 1024 && N % 2 == 0),
-                "fbx_eigh_dev: N must be a power of two in 2..64 or an even number in 66..1024");
-    FBX_REQUIRE(B >= 0 && (B == 0 || (d_a && d_w_out)), "fbx_eigh: bad batch / NULL buffer");
-    FBX_TRY(ensure_device());
-    if (B == 0) return FBX_OK;
-    if (N > 64) {
-        // few large matrices: one at a time over the whole chip; many: one CU each
-        // (measured: one CU per matrix 14 / 108 / 1270 / 9300 ms for N = 128 / 256 / 512 / 1024, whatever the batch up to
-        // the number of CUs; the whole chip on one matrix 6 / 25 / 200 / 820 ms each)
-        const int64_t coop_up_to = N >= 768 ? 10 : N >= 384 ? 5 : 3;
-        if (N >= 128 && B <= coop_up_to) { bool done = false; FBX_TRY(launch_eigh_coop(N, B, d_a, d_w_out, d_v_out, &done)); if (done) return FBX_OK; }
-        return launch_eigh_big(N, B, d_a, d_w_out, d_v_out);
-    }
-    switch (N) {
-        case 2: FBX_TRY(launch_eigh<2>(B, d_a, d_w_out, d_v_out)); break;
-        case 4: FBX_TRY(launch_eigh<4>(B, d_a, d_w_out, d_v_out)); break;
-        case 8: FBX_TRY(launch_eigh<8>(B, d_a, d_w_out, d_v_out)); break;
-        case 16: FBX_TRY(launch_eigh<16>(B, d_a, d_w_out, d_v_out)); break;
-        case 32: FBX_TRY(launch_eigh<32>(B, d_a, d_w_out, d_v_out)); break;
-        default: FBX_TRY(launch_eigh<64>(B, d_a, d_w_out, d_v_out)); break;
-    }
-    FBX_HIP(hipGetLastError());
-    return FBX_OK;
-}
-
-int fbx_eigh(int N, int64_t B, const double* a, double* w_out, double* v_out) {
-    FBX_REQUIRE(N >= 1 && N <= 1024, "fbx_eigh: N must be in 1..1024");
-    FBX_REQUIRE(B >= 0 && (B == 0 || (a && w_out)), "fbx_eigh: bad batch / NULL buffer");
-    FBX_TRY(ensure_device());
-    if (B == 0) return FBX_OK;
-    int Np = 2;
-    while (Np < N) Np *= 2;
-    if (N > 64) Np = N + (N & 1);           // the HBM-resident solver takes any even size
-    if (Np == N) {
-        const size_t nn = (size_t)N * N * 2 * B;
-        HostIO io; double *da, *dw, *dv;
-        FBX_TRY(io.in(a, nn, &da)); FBX_TRY(io.out(w_out, (size_t)N * B, &dw)); FBX_TRY(io.out_opt(v_out, nn, &dv));
-        FBX_TRY(fbx_eigh_dev(N, B, da, dw, dv));
-        return io.finish();
-    }
-    // Any other size (e.g. a qutrit's 3 x 3, a 9 x 9 Choi matrix): embedded in the next power of two
-    // with zero rows / columns.  The padding coordinates are decoupled and stay so exactly (a pivot
-    // with a zero off-diagonal entry gets the identity rotation), so their eigenvectors come back as
-    // unit vectors on the padding coordinates and are dropped here; the rest is the decomposition
-    // of the N x N matrix, still ascending.
-    const size_t np2 = (size_t)Np * Np;
-    std::vector<double> ap(np2 * 2 * B, 0.0), wp((size_t)Np * B), vp(np2 * 2 * B);
-    for (int64_t b = 0; b < B; ++b)
-        for (int r = 0; r < N; ++r)
-            memcpy(&ap[(b * np2 + (size_t)r * Np) * 2], &a[((size_t)b * N * N + (size_t)r * N) * 2], sizeof(double) * 2 * N);
-    {
-        HostIO io; double *da, *dw, *dv;
-        FBX_TRY(io.in(ap.data(), ap.size(), &da));
-        FBX_TRY(io.out(wp.data(), wp.size(), &dw)); FBX_TRY(io.out(vp.data(), vp.size(), &dv));
-        FBX_TRY(fbx_eigh_dev(Np, B, da, dw, dv));
-        FBX_TRY(io.finish());
-    }
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int64_t b = 0; b < B; ++b) {
-        // a non-finite item came back all NaN (no column can be told from padding): NaN for that item, as for direct sizes
-        bool nonfinite = false;
-        for (int k = 0; k < Np && !nonfinite; ++k) nonfinite = std::isnan(wp[b * Np + k]);
-        if (nonfinite) {
-            for (int k = 0; k < N; ++k) w_out[b * N + k] = nan;
-            if (v_out) for (size_t k = 0; k < (size_t)N * N * 2; ++k) v_out[(size_t)b * N * N * 2 + k] = nan;
-            continue;
-        }
-        int kept = 0;
-        for (int k = 0; k < Np; ++k) {
-            bool padding = false;
-            for (int r = N; r < Np && !padding; ++r) {
-                const double* e = &vp[(b * np2 + (size_t)r * Np + k) * 2];
-                padding = e[0] != 0.0 || e[1] != 0.0;
-            }
-            if (padding) continue;
-            if (kept < N) {
-                w_out[b * N + kept] = wp[b * Np + k];
-                if (v_out)
-                    for (int r = 0; r < N; ++r) {
-                        v_out[((size_t)b * N * N + (size_t)r * N + kept) * 2] = vp[(b * np2 + (size_t)r * Np + k) * 2];
-                        v_out[((size_t)b * N * N + (size_t)r * N + kept) * 2 + 1] = vp[(b * np2 + (size_t)r * Np + k) * 2 + 1];
-                    }
-            }
-            ++kept;
-        }
-        if (kept != N) { set_error("fbx_eigh: internal error separating the padding of a non-power-of-two matrix"); return FBX_ERR_HIP; }
-    }
-    return FBX_OK;
-}
-
-// ---- choi2kraus for a batch (superoperator_transformations.py:325-336): fbx_eigh_dev + one assembling kernel.
-// One workgroup per item.  Eigenpair k is kept when |lambda_k| > tol (the reference's test); its operator is
-// sqrt(lambda_k) unvec(v_k) -- numpy's scimath square root, i sqrt(|lambda|) for a negative eigenvalue -- with the phase of v_k
-// fixed so that its first component above 1e-12 ||v_k|| is real and positive (the convention of the host form this replaces,
-// fbx/operator_tools/superoperator_transformations.py: what LAPACK hands the reference on the operators its tests compare
-// entry by entry).  unvec is column stacking: K[r][c] = v[c d + r].  Kept operators are packed at the front of the item's D
-// slots in ascending eigenvalue order (the order of the reference's list), the other slots are zeroed.
-__global__ void __launch_bounds__(256)
-kraus_assemble_kernel(int D, int d, long long B, const double* __restrict__ w, const double* __restrict__ V, double tol,
-                      double* __restrict__ out, int* __restrict__ count) {
-    extern __shared__ __attribute__((aligned(16))) char kraus_smem[];
-    double* fre = (double*)kraus_smem;
-    double* fim = fre + D;
-    int* keep = (int*)(fim + D);
-    int* pos = keep + D;
-    const long long b = blockIdx.x;
-    const int tid = threadIdx.x;
-    const cplx* Vb = (const cplx*)V + (size_t)b * D * D;
-    const double* wb = w + (size_t)b * D;
-    for (int k = tid; k < D; k += 256) {
-        const double ev = wb[k];
-        const bool kp = fabs(ev) > tol;
-        double fr = 0.0, fi = 0.0;
-        if (kp) {
-            double n2 = 0.0;
-            for (int i = 0; i < D; ++i) { const cplx x = Vb[(size_t)i * D + k]; n2 = fma(x.re, x.re, fma(x.im, x.im, n2)); }
-            const double thr = 1e-12 * sqrt(n2);
-            double pr = 1.0, pi = 0.0;
-            for (int i = 0; i < D; ++i) {
-                const cplx x = Vb[(size_t)i * D + k];
-                const double a = sqrt(fma(x.re, x.re, x.im * x.im));
-                if (a > thr) { pr = x.re / a; pi = -x.im / a; break; }       // |x| / x
-            }
-            const double sq = sqrt(fabs(ev));
-            if (ev >= 0.0) { fr = pr * sq; fi = pi * sq; } else { fr = -pi * sq; fi = pr * sq; }    // i (pr + i pi)
-        }
-        keep[k] = kp ? 1 : 0; fre[k] = fr; fim[k] = fi;
-    }
-    __syncthreads();
-    for (int k = tid; k < D; k += 256) { int c = 0; for (int j = 0; j < k; ++j) c += keep[j]; pos[k] = c; }
-    __syncthreads();
-    const int total = pos[D - 1] + keep[D - 1];
-    cplx* ob = (cplx*)out + (size_t)b * D * D;
-    for (int idx = tid; idx < D * D; idx += 256) {
-        const int i = idx / D, k = idx % D;                    // k fastest: coalesced reads of V[i][.]
-        if (!keep[k]) continue;
-        const cplx x = Vb[idx];
-        const int r = i % d, c = i / d;
-        cplx o; o.re = fre[k] * x.re - fim[k] * x.im; o.im = fre[k] * x.im + fim[k] * x.re;
-        ob[((size_t)pos[k] * d + r) * d + c] = o;
-    }
-    for (int idx = total * D + tid; idx < D * D; idx += 256) { cplx z; z.re = 0.0; z.im = 0.0; ob[idx] = z; }
-    if (tid == 0 && count) count[b] = total;
-}
-
-int fbx_choi2kraus_dev(int n_qubits, int64_t B, const double* d_choi, double tol, double* d_kraus_out, int32_t* d_count_out) {
-    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 5, "fbx_choi2kraus: n_qubits must be 1..5");
-    FBX_REQUIRE(B >= 0 && (B == 0 || (d_choi && d_kraus_out)), "fbx_choi2kraus: bad batch / NULL buffer");
-    FBX_REQUIRE(tol >= 0.0, "fbx_choi2kraus: negative tolerance");
-    FBX_TRY(ensure_device());
-    if (B == 0) return FBX_OK;
-    const int d = 1 << n_qubits, D = d * d;
-    // the eigenvectors of a block of items at a time: 16 MiB per 5-qubit item
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(B, ((int64_t)1 << 28) / ((int64_t)D * D * 16)));
-    DevBuf dw, dv;
-    FBX_TRY(dw.alloc(sizeof(double) * D * (size_t)chunk));
-    FBX_TRY(dv.alloc(sizeof(double) * 2 * D * D * (size_t)chunk));
-    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
-        const int64_t nb = std::min(chunk, B - b0);
-        FBX_TRY(fbx_eigh_dev(D, nb, d_choi + (size_t)b0 * D * D * 2, dw.as<double>(), dv.as<double>()));
-        hipLaunchKernelGGL(kraus_assemble_kernel, dim3((unsigned)nb), dim3(256), (size_t)D * 24, stream(), D, d, (long long)nb,
-                           dw.as<double>(), dv.as<double>(), tol, d_kraus_out + (size_t)b0 * D * D * 2,
-                           d_count_out ? d_count_out + b0 : nullptr);
-        FBX_HIP(hipGetLastError());
-    }
-    return FBX_OK;
-}
-
-int fbx_choi2kraus(int n_qubits, int64_t B, const double* choi, double tol, double* kraus_out, int32_t* count_out) {
-    FBX_REQUIRE(n_qubits >= 1 && n_qubits <= 5, "fbx_choi2kraus: n_qubits must be 1..5");
-    FBX_REQUIRE(B >= 0 && (B == 0 || (choi && kraus_out)), "fbx_choi2kraus: bad batch / NULL buffer");
-    FBX_TRY(ensure_device());
-    if (B == 0) return FBX_OK;
-    const size_t D = (size_t)1 << (2 * n_qubits), nn = D * D * 2 * (size_t)B;
-    HostIO io; double *dc, *dk; int32_t* dn;
-    FBX_TRY(io.in(choi, nn, &dc)); FBX_TRY(io.out(kraus_out, nn, &dk)); FBX_TRY(io.out(count_out, (size_t)B, &dn));
-    FBX_TRY(fbx_choi2kraus_dev(n_qubits, B, dc, tol, dk, dn));
     return io.finish();
 }
 

@@ -1,5 +1,7 @@
-"""Bit-for-bit comparison of two builds of the library on the same inputs (2-qubit PGDB, both kernels; 3-qubit PGDB).
-usage: python scripts/compare_libs.py libA.so libB.so"""
+"""Bit-for-bit comparison of two builds of the library on the same inputs: PGDB (2 qubits on both kernels, 1 and 3 qubits), the
+state estimators and measures for 1-4 qubits incl. designs of more than 64 settings, Choi projections, conversions, the Kraus
+sweeps, and fbx_eigh / fbx_matmul / fbx_choi2kraus at every size class.
+usage: python scripts/compare_libs.py libA.so libB.so      (names inside forest-benchmarking_amd/; FBX_LIBRARY selects each build)"""
 import os, subprocess, sys, hashlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = r'''
@@ -55,6 +57,48 @@ for n, B in ((2, 1001), (3, 33)):
     _lib.check(lib.fbx_kraus_sweep(n, B, K, _lib.dptr(k.view(np.float64)), _lib.dptr(ref.view(np.float64)), _lib.dptr(choi.view(np.float64)),
                                    _lib.dptr(ptm.view(np.float64)), _lib.dptr(chi.view(np.float64)), _lib.dptr(fid)))
     out.append(H(choi, ptm, chi, fid))
+# the state path entry point by entry point (1-4 qubits; designs of 66-126 settings: the staged R operator, 4200: the streamed one)
+# and the general linear algebra of csrc/fbx_linalg.hip
+from fbx import design as fd, distance_measures as dm
+def rand_states(B, d, seed):
+    r = np.random.RandomState(seed)
+    a = r.randn(B, d, d) + 1j * r.randn(B, d, d)
+    a = a @ a.conj().transpose(0, 2, 1)
+    return a / np.trace(a, axis1=1, axis2=2)[:, None, None]
+def state_calls(design, e, c, rho, mle_kws):
+    for kw in mle_kws:
+        out.append(H(tomography.iterative_mle_state_estimate_batch(design, e, c, **kw)))
+    out.append(H(tomography._R_batch(rho, design, e)))
+    out.append(H(tomography.state_log_likelihood_batch(rho, design, e, c)))
+    out.append(H(tomography.linear_inv_state_estimate_batch(design, e)))
+def measures(rho, sig):
+    m = dm.state_measures_batch(rho, sig)
+    out.append(H(*[m[k] for k in ("purity", "fidelity", "trace_distance", "hs_ip")]))
+for n, B in ((1, 64), (2, 64), (3, 16)):
+    design, _, e, c = synthetic.state_batch(n, B, mixed=0.05)
+    state_calls(design, e, c, rand_states(B, 2 ** n, 11 + n), (dict(maxiter=30, entropy_penalty=0.005),))
+    measures(rand_states(B, 2 ** n, 21 + n), rand_states(B, 2 ** n, 31 + n))
+design, _, e, c = synthetic.state_batch(4, 2, mixed=0.05)
+state_calls(design, e, c, rand_states(2, 16, 15), (dict(maxiter=8), dict(maxiter=8, beta=0.5), dict(maxiter=8, entropy_penalty=0.005)))
+out.append(H(psm.project_state_matrix_to_physical_batch(rs.randn(2, 16, 16) + 1j * rs.randn(2, 16, 16) + np.eye(16))))
+measures(rand_states(2, 16, 25), rand_states(2, 16, 35))
+variants = (dict(maxiter=40), dict(beta=0.5, epsilon=1e-4, maxiter=12), dict(entropy_penalty=0.005, maxiter=12))
+for n, reps in ((1, 22), (2, 5), (3, 2)):
+    p = np.tile(fd.traceless_pauli_codes(n), (reps, 1))
+    design = fd.Design(n, "state", None, p)
+    e = np.random.RandomState(40 + n).uniform(-0.6, 0.6, (4, design.m))
+    state_calls(design, e, np.full(e.shape, 500.0), rand_states(4, 2 ** n, 41 + n), variants)
+g = np.load(os.path.join(sys.argv[1], "tests", "golden", "repeated.npz"))
+state_calls(fd.Design(1, "state", None, g["s1_paulis"]), g["s1_e"], g["s1_c"], g["s1_mle40"], variants[:2])
+for N in (2, 4, 8, 16, 32, 64, 66, 130, 3):
+    a = rs.randn(3, N, N) + 1j * rs.randn(3, N, N)
+    out.append(H(*_lib.eigh_batch(a), _lib.eigh_batch(a, eigenvectors=False)))
+for N in (5, 33):
+    a, b, sc = rs.randn(3, N, N) + 1j * rs.randn(3, N, N), rs.randn(3, N, N) + 1j * rs.randn(3, N, N), rs.randn(3, N)
+    out.append(H(*[_lib.matmul_batch(a, b, conj_t_a=ta, conj_t_b=tb, scale=sc) for ta in (False, True) for tb in (False, True)]))
+for n in (1, 2):
+    choi = st_.convert_batch("kraus", "choi", synthetic.kraus_batch(n, 3, 8, seed=7))
+    out.append(H(*st_.choi2kraus_batch(choi)))
 print(" ".join(out))
 '''
 res = []
@@ -62,5 +106,7 @@ for lib in sys.argv[1:3]:
     r = subprocess.run([sys.executable, "-c", CHILD, ROOT], env=dict(os.environ, FBX_LIBRARY=os.path.join(ROOT, "forest-benchmarking_amd", lib)),
                        capture_output=True, text=True)
     print(f"{lib:24s} {r.stdout.strip()} {r.stderr.strip()[-300:]}")
+    if r.returncode != 0:                     # a build that failed is not followed by another run on the same device
+        sys.exit(f"{lib}: exit status {r.returncode}")
     res.append(r.stdout.strip())
 print("IDENTICAL" if res[0] == res[1] and res[0] else "DIFFERENT")

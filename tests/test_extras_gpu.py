@@ -172,7 +172,7 @@ def test_estimate_by_qubit_groups_batches_pairs(gpu):
 
 @pytest.mark.parametrize("N", [66, 100, 129, 256])
 def test_eigh_beyond_lds_sizes(gpu, N):
-    """64 < N <= 1024: the HBM-resident Jacobi (csrc/fbx_state.hip eigh_big_kernel) with numpy.linalg.eigh
+    """64 < N <= 1024: the HBM-resident Jacobi (csrc/fbx_linalg.hip eigh_big_kernel) with numpy.linalg.eigh
     semantics -- lower triangle, ascending eigenvalues, A V = V diag(w), V unitary; odd sizes are padded."""
     from fbx import _lib
     rs = np.random.RandomState(N)

@@ -116,6 +116,37 @@ def test_state_tomography_of_a_repeated_dataset(gpu, tag, n):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n,reps", [(1, 22), (2, 5), (3, 2)])
+def test_state_tomography_of_a_staged_design(gpu, n, reps):
+    """More than 64 settings (no setting per lane, no packed or plain kernel) but within the 64 KiB of per-setting LDS staging:
+    mle_state_kernel with the STAGED form of r_operator_elem, which the fixtures above (4200 settings: streamed) and
+    tests/test_state_gpu.py (at most 63) do not reach.  The non-identity Pauli design measured `reps` times, against the oracle
+    on the same list, item by item, with the tolerances of the 4200-setting fixtures."""
+    import warnings
+    from fbx import design as fd, tomography
+    from fbx_oracle import design as od, estimators as oe
+    p = np.tile(fd.traceless_pauli_codes(n), (reps, 1))
+    d, o = (mod.Design(n, "state", np.full_like(p, 4), p, np.ones(len(p))) for mod in (fd, od))
+    assert d.m == {1: 66, 2: 75, 3: 126}[n]
+    B = 4
+    e = np.random.RandomState(40 + n).uniform(-0.6, 0.6, (B, d.m))
+    c = np.full((B, d.m), 500.0)
+    variants = (dict(maxiter=40), dict(beta=0.5, epsilon=1e-4, maxiter=12), dict(entropy_penalty=0.005, maxiter=12))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                   # 'Maximum number of iterations reached', from both sides
+        got = [tomography.iterative_mle_state_estimate_batch(d, e, c, **kw) for kw in variants]
+        want = [np.array([oe.iterative_mle_state_estimate(o, e[b], c[b], **kw) for b in range(B)]) for kw in variants]
+    for g_, w_, bound in zip(got, want, (1e-11, 1e-10, 1e-10)):
+        assert np.abs(g_ - w_).max(axis=(1, 2)).max() < bound
+    rho = want[0]
+    r_want = np.array([oe.R_operator(rho[b], o, e[b]) for b in range(B)])
+    assert np.abs(tomography._R_batch(rho, d, e) - r_want).max() < 1e-10
+    ll_want = np.array([oe.state_log_likelihood(rho[b], o, e[b], c[b]) for b in range(B)])
+    ll = tomography.state_log_likelihood_batch(rho, d, e, c)
+    assert (np.abs(ll - ll_want) < 1e-9 * np.abs(ll_want)).all()
+
+
+@pytest.mark.gpu
 def test_three_qubit_repeated_dataset(gpu):
     """16 128 settings (the 3-qubit SIC design measured four times): beyond the 14 336 of the resident 3-qubit instantiations; the
     kernel's 32-slot instantiation keeps its per-slot arrays in scratch.  tests/golden/repeated_3q.npz holds the reference's

@@ -27,6 +27,15 @@ struct ChoiLds {
     static constexpr int LDpt = LEAN ? D : LD;     // leading dimension of the partial-trace staging
     static constexpr bool lean = LEAN;
     static constexpr bool two_workers = TWO_WORKERS && D == 16;
+    // Every non-LEAN work area belongs to a kernel that runs the projection as ONE wavefront per SIMD or close to it (the
+    // one-wave PGDB kernels, proj_choi_kernel): nobody hides that wavefront's LDS round trips, so its projections request the
+    // operands of a whole step together (`batched`: the eigenvalue terms of the reconstruction recon_terms per trip, the
+    // partial trace's entries, one load of the pt cell a lane subtracts) and keep the clamped eigenvalues in registers.
+    // Same operations on the same operands in the same order: bit-identical to the plain loops, which the register-capped
+    // LEAN kernel keeps.  (Three terms per trip: 11.59 / 11.45 / 11.60 ms for two / three / four with nothing else changed,
+    // 11.28 / 11.25 / 11.32 ms with the rest of the batching, parent 11.73 ms; docs/history/experiments.md.)
+    static constexpr bool batched = !LEAN;
+    static constexpr int recon_terms = LEAN ? 1 : 3;
     cplx* Mw;      // [D * LD]   row-major staging matrix (Pauli transforms); LEAN: = Ms, running into Vs
     cplx* Mpt;     // partial-trace staging: Mw, or Ms (LEAN)
     cplx* Ts;      // scratch of the generic warm-start basis change (D != 16): Mw, or (LEAN, where Mw IS Ms) a block of its own
@@ -121,20 +130,25 @@ __device__ Blk proj_cp_blk(const Blk& x, LdsT& L, int lane, int& sweeps, bool wa
     }
     sweeps += sw;
     PH_STOP(*L.pc, 0);
-    {
-        const double l = lane < D ? L.Ms[sys_index<D>(lane, lane)].re : 0.0;
+    const double l = lane < D ? L.Ms[sys_index<D>(lane, lane)].re : 0.0;
+    Blk out;
+    if constexpr (LdsT::batched) {
+        // the clamped eigenvalue of lane k stays in its register (lanes from D on hold 0): nothing reads L.lam after a CP projection
+        L.terms += __popcll(__ballot(l > 0.0));
+        out = reconstruct_blk<D, LdsT::recon_terms>(L.Vs, l < 0.0 ? 0.0 : l, lane);
+    } else {
         if (lane < D) L.lam[lane] = l < 0.0 ? 0.0 : l;
         L.terms += __popcll(__ballot(l > 0.0));
+        FBX_WAVE_SYNC();
+        out = reconstruct_blk<D>(L.Vs, L.lam, lane);
     }
-    FBX_WAVE_SYNC();
-    const Blk out = reconstruct_blk<D>(L.Vs, L.lam, lane);
     PH_STOP(*L.pc, 1);
     return out;
 }
 
 // ---- partial trace over the output space into L.pt (d x d): calculational.py:5-35 with
-// keep=[0], dims=[d, d].  Stages `x` through Mw.
-template <int NQ, class LdsT>
+// keep=[0], dims=[d, d].  Stages `x` through Mw.  MINUS_I: L.pt receives pt - I (the lanes of the diagonal subtract 1 before they store).
+template <int NQ, bool MINUS_I = false, class LdsT>
 __device__ void partial_trace_out(const Blk& x, LdsT& L, int lane) {
     constexpr int d = LdsT::d, D = LdsT::D, LD = LdsT::LDpt, LDs = LdsT::LDs;
     FBX_WAVE_SYNC();
@@ -143,11 +157,21 @@ __device__ void partial_trace_out(const Blk& x, LdsT& L, int lane) {
     if (lane < d * d) {
         const int i = lane / d, ip = lane % d;
         cplx s; s.re = 0.0; s.im = 0.0;
+        if constexpr (LdsT::batched) {          // the d entries requested together, then added in the same order
+            cplx v[d];
 #pragma unroll
-        for (int o = 0; o < d; ++o) {
-            const cplx v = L.Mpt[(i * d + o) * LD + ip * d + o];
-            s.re += v.re; s.im += v.im;
+            for (int o = 0; o < d; ++o) v[o] = L.Mpt[(i * d + o) * LD + ip * d + o];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int o = 0; o < d; ++o) { s.re += v[o].re; s.im += v[o].im; }
+        } else {
+#pragma unroll
+            for (int o = 0; o < d; ++o) {
+                const cplx v = L.Mpt[(i * d + o) * LD + ip * d + o];
+                s.re += v.re; s.im += v.im;
+            }
         }
+        if (MINUS_I && i == ip) s.re -= 1.0;
         L.pt[i * LDs + ip] = s;
     }
     FBX_WAVE_SYNC();
@@ -158,7 +182,17 @@ template <int NQ, class LdsT>
 __device__ __forceinline__ Blk subtract_kron_pt(const Blk& x, const LdsT& L, int lane) {
     constexpr int d = LdsT::d, D = LdsT::D, LDs = LdsT::LDs, NB = D / 2;
     Blk r = x;
-    if (lane < NB * NB) {
+    if constexpr (LdsT::batched) {
+        // d is even: rows 2I, 2I + 1 lie in one d-block and so do columns 2J, 2J + 1, and row % d == col % d only holds for the two
+        // diagonal elements of the 2 x 2 block, both or neither -- one cell of pt per lane, loaded once
+        static_assert(d % 2 == 0, "a 2 x 2 block lies inside one d x d block");
+        const int I = lane / NB, J = lane % NB;
+        if (lane < NB * NB && ((2 * I) % d) == ((2 * J) % d)) {
+            const cplx c = L.pt[((2 * I) / d) * LDs + ((2 * J) / d)];
+            r.re[0] -= c.re / d; r.im[0] -= c.im / d;
+            r.re[3] -= c.re / d; r.im[3] -= c.im / d;
+        }
+    } else if (lane < NB * NB) {
         const int I = lane / NB, J = lane % NB;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -176,9 +210,13 @@ __device__ __forceinline__ Blk subtract_kron_pt(const Blk& x, const LdsT& L, int
 template <int NQ, class LdsT>
 __device__ Blk proj_tp_blk(const Blk& x, LdsT& L, int lane) {
     constexpr int d = LdsT::d, LDs = LdsT::LDs;
-    partial_trace_out<NQ>(x, L, lane);
-    if (lane < d) L.pt[lane * LDs + lane].re -= 1.0;       // pt - I
-    FBX_WAVE_SYNC();
+    if constexpr (LdsT::batched) {
+        partial_trace_out<NQ, true>(x, L, lane);           // pt - I
+    } else {
+        partial_trace_out<NQ>(x, L, lane);
+        if (lane < d) L.pt[lane * LDs + lane].re -= 1.0;   // pt - I
+        FBX_WAVE_SYNC();
+    }
     return subtract_kron_pt<NQ>(x, L, lane);
 }
 

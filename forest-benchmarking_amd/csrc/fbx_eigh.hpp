@@ -297,8 +297,7 @@ struct __attribute__((aligned(16))) JRec { double c, sr, si, an, dn, pad; };
 // four ds_read_b128.  A round was 160 cycles of LDS pipe, 104 of them its eight 16-byte stores (13 cycles per wave
 // instruction on MI355X, a third of the read rate), shared by the four or eight wavefronts of a CU.  Measured in isolation
 // (scripts/micro/run_jacobi_vdpp.sh, profiles/r05): 1180 -> 1017 cycles per round at one wavefront per SIMD, 1635 -> 1433 at
-// two, 2595 -> 2096 at four.  The same rotations are applied to the same data: results are bit-identical to the LDS form
-// (-DFBX_JACOBI_V_THROUGH_LDS keeps it for A/Bs).
+// two, 2595 -> 2096 at four.  The same rotations are applied to the same data: results are bit-identical to the LDS form.
 // The solver exists in two forms selected by a TEMPLATE TAG at the call site (fbx_choi.hpp: ChoiLds<..., TWO_WORKERS>), not by a
 // per-file macro: jacobi_eigh_wave<N, true> below (two workers per upper block; only the diagonal of Ms is meaningful on exit) and
 // jacobi_eigh_wave<N, false> (every lane its full block).  Two names for two post-conditions -- no ODR hazard under -fgpu-rdc / LTO.
@@ -720,34 +719,83 @@ __device__ __forceinline__ int jacobi_eigh_lds(cplx* Ms, cplx* Vs, JRec* rec, in
 
 // block (I, J) of sum_k lam[k] v_k v_k^H for the eigenvectors in Vs (element-major layout);
 // terms with lam[k] == 0 are skipped (wave-uniform branch).
-template <int N>
-__device__ __forceinline__ Blk reconstruct_blk(const cplx* Vs, const double* lam, int lane) {
-    constexpr int NB = N / 2, LS = NB * NB, PS = sys_plane<N>();
+//
+// One trip of the loop below: the UU lowest set bits of `todo` are popped, the 4 UU eigenvector loads of those terms are ALL
+// requested before the first multiply -- a scheduling barrier keeps them there -- and the terms are then added to `out` in
+// ascending k under partial waits.  A lone wavefront has nobody to hide an LDS round trip behind: with one term per trip every
+// term pays a full one (s_ff1, two v_readlane, four ds_read_b128, a wait to zero, 28 fp64 instructions).  Each accumulator of
+// `out` receives the terms it received before, written as before, in the order it received them: same bits for any UU.
+template <int N, int UU>
+__device__ __forceinline__ void reconstruct_terms(const cplx* Vs, double mine, unsigned long long& todo, int I, int J, Blk& out) {
+    constexpr int PS = sys_plane<N>();
+    double l[UU];
+    cplx r0[UU], r1[UU], c0[UU], c1[UU];
+#pragma unroll
+    for (int u = 0; u < UU; ++u) {
+        const int k = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        l[u] = readlane_f64(mine, k);
+        const int kb = k >> 1, ke = k & 1;
+        const int rk = sys_pos<N>(I, kb, ke), ck = sys_pos<N>(J, kb, ke);      // column k of the block rows I and J
+        r0[u] = Vs[(0 + ke) * PS + rk]; r1[u] = Vs[(2 + ke) * PS + rk];
+        c0[u] = Vs[(0 + ke) * PS + ck]; c1[u] = Vs[(2 + ke) * PS + ck];
+    }
+    if constexpr (UU > 1) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < UU; ++u) {
+        const double w0r = l[u] * r0[u].re, w0i = l[u] * r0[u].im, w1r = l[u] * r1[u].re, w1i = l[u] * r1[u].im;
+        // w * conj(c)
+        out.re[0] += w0r * c0[u].re + w0i * c0[u].im; out.im[0] += w0i * c0[u].re - w0r * c0[u].im;
+        out.re[1] += w0r * c1[u].re + w0i * c1[u].im; out.im[1] += w0i * c1[u].re - w0r * c1[u].im;
+        out.re[2] += w1r * c0[u].re + w1i * c0[u].im; out.im[2] += w1i * c0[u].re - w1r * c0[u].im;
+        out.re[3] += w1r * c1[u].re + w1i * c1[u].im; out.im[3] += w1i * c1[u].re - w1r * c1[u].im;
+    }
+}
+// `mine`: lane k (of every wavefront) holds lam[k], lanes from N on hold 0; the non-zero ones are walked through a ballot mask
+// and v_readlane, so the loop has no LDS load + branch on its critical path.  U = terms per trip; what is left over when fewer
+// than U remain runs as a pair, then a single term (never padded with zero-weight terms: 0 * inf would be a NaN the plain loop
+// does not produce).  U = 1 is the plain loop.
+template <int N, int U = 1>
+__device__ __forceinline__ Blk reconstruct_blk(const cplx* Vs, double mine, int lane) {
+    constexpr int NB = N / 2, LS = NB * NB;
+    static_assert(U >= 1 && U <= 4, "one to four terms per trip");
     Blk out = blk_zero();
     const bool act = lane < LS;
     const int I = act ? lane / NB : 0, J = act ? lane % NB : 0;
-    // lane k of every wavefront keeps lam[k]; the non-zero ones are walked through a ballot mask and
-    // v_readlane, so the loop has no LDS load + branch on its critical path
-    const int wl = lane & 63;
-    const double mine = wl < N ? lam[wl] : 0.0;
     unsigned long long todo = __ballot(mine != 0.0);
-    while (todo) {
-        const int k = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const double l = readlane_f64(mine, k);
-        const int kb = k >> 1, ke = k & 1;
-        const int rk = sys_pos<N>(I, kb, ke), ck = sys_pos<N>(J, kb, ke);      // column k of the block rows I and J
-        const cplx r0 = Vs[(0 + ke) * PS + rk], r1 = Vs[(2 + ke) * PS + rk];
-        const cplx c0 = Vs[(0 + ke) * PS + ck], c1 = Vs[(2 + ke) * PS + ck];
-        const double w0r = l * r0.re, w0i = l * r0.im, w1r = l * r1.re, w1i = l * r1.im;
-        // w * conj(c)
-        out.re[0] += w0r * c0.re + w0i * c0.im; out.im[0] += w0i * c0.re - w0r * c0.im;
-        out.re[1] += w0r * c1.re + w0i * c1.im; out.im[1] += w0i * c1.re - w0r * c1.im;
-        out.re[2] += w1r * c0.re + w1i * c0.im; out.im[2] += w1i * c0.re - w1r * c0.im;
-        out.re[3] += w1r * c1.re + w1i * c1.im; out.im[3] += w1i * c1.re - w1r * c1.im;
+    if constexpr (U > 1) {
+        while (__popcll(todo) >= U) reconstruct_terms<N, U>(Vs, mine, todo, I, J, out);
+        if constexpr (U > 2) {
+            if (__popcll(todo) >= 2) reconstruct_terms<N, 2>(Vs, mine, todo, I, J, out);
+        }
+        if (todo) reconstruct_terms<N, 1>(Vs, mine, todo, I, J, out);
+    } else {
+        // (spelled out, not reconstruct_terms<N, 1>: through the helper the register-capped two-waves kernel allocates its
+        // registers differently, and its code is kept as it is)
+        constexpr int PS = sys_plane<N>();
+        while (todo) {
+            const int k = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const double l = readlane_f64(mine, k);
+            const int kb = k >> 1, ke = k & 1;
+            const int rk = sys_pos<N>(I, kb, ke), ck = sys_pos<N>(J, kb, ke);      // column k of the block rows I and J
+            const cplx r0 = Vs[(0 + ke) * PS + rk], r1 = Vs[(2 + ke) * PS + rk];
+            const cplx c0 = Vs[(0 + ke) * PS + ck], c1 = Vs[(2 + ke) * PS + ck];
+            const double w0r = l * r0.re, w0i = l * r0.im, w1r = l * r1.re, w1i = l * r1.im;
+            // w * conj(c)
+            out.re[0] += w0r * c0.re + w0i * c0.im; out.im[0] += w0i * c0.re - w0r * c0.im;
+            out.re[1] += w0r * c1.re + w0i * c1.im; out.im[1] += w0i * c1.re - w0r * c1.im;
+            out.re[2] += w1r * c0.re + w1i * c0.im; out.im[2] += w1i * c0.re - w1r * c0.im;
+            out.re[3] += w1r * c1.re + w1i * c1.im; out.im[3] += w1i * c1.re - w1r * c1.im;
+        }
     }
     if (!act) out = blk_zero();
     return out;
+}
+template <int N>
+__device__ __forceinline__ Blk reconstruct_blk(const cplx* Vs, const double* lam, int lane) {
+    const int wl = lane & 63;
+    return reconstruct_blk<N>(Vs, wl < N ? lam[wl] : 0.0, lane);
 }
 
 }  // namespace fbx

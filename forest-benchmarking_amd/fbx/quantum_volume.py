@@ -6,6 +6,8 @@ What runs where:
     simulation of B circuits of one width in one launch, the state in LDS, widths 2..13 (wider: ``FbxError(FBX_ERR_UNSUPPORTED)``;
     there is no host fallback);
   * ``count_heavy_hitters_sampled[_batch]`` -- ``fbx_qv_count_heavy``: a streaming reduction of the ``qc.run`` bit arrays;
+  * ``simulate_heavy_output_counts_batch`` -- a simulated run resident on the device: ``fbx_qv_heavy_outputs_dev`` ->
+    ``fbx_sample_bitstrings_dev`` (noisy measured bitstrings from the ideal distributions) -> ``fbx_qv_count_heavy_dev``;
   * ``generate_abstract_qv_circuit`` -- host numpy with the reference's draw order (a run seeded with ``np.random.seed`` reproduces
     the reference's circuit); ``generate_abstract_qv_circuits_batch`` -- gates from the device generator;
   * ``calculate_prob_est_and_err``, ``get_prob_sample_heavy_by_depth``, ``extract_quantum_volume_from_results`` -- host arithmetic.
@@ -28,7 +30,8 @@ from .operator_tools.random_operators import _stream_seed, haar_rand_unitary
 __all__ = ["generate_abstract_qv_circuit", "generate_abstract_qv_circuits_batch", "collect_heavy_outputs",
            "collect_heavy_outputs_batch", "ideal_heavy_output_probability_batch", "count_heavy_hitters_sampled",
            "count_heavy_hitters_sampled_batch", "calculate_prob_est_and_err", "get_prob_sample_heavy_by_depth",
-           "extract_quantum_volume_from_results", "layer_pairs", "pack_heavy_mask", "unpack_heavy_mask", "heavy_outputs_flat"]
+           "extract_quantum_volume_from_results", "layer_pairs", "pack_heavy_mask", "unpack_heavy_mask", "heavy_outputs_flat",
+           "simulate_heavy_output_counts_batch"]
 
 MIN_WIDTH, MAX_WIDTH = 2, 13
 
@@ -250,6 +253,59 @@ def count_heavy_hitters_sampled(qc_results: Iterator[np.ndarray], heavy_hitters:
         for row, i in enumerate(idx):
             counts[i] = int(got[row])
     yield from counts
+
+
+# ------------------------------------------------------------------------------------------------ simulated runs
+def simulate_heavy_output_counts_batch(permutations, gates, shots: int, depolarizing=0.0, readout_flip=None,
+                                       seed: Optional[int] = None, pairing: str = "reference"):
+    """A simulated quantum-volume run of B model circuits of one width, resident on the device: ideal output distributions
+    (``fbx_qv_heavy_outputs_dev``) -> ``shots`` noisy measured bitstrings per circuit (``fbx_sample_bitstrings_dev``: global
+    depolarizing of strength ``depolarizing``, a scalar or ``[B]``, then readout flips ``[n, 2]`` or ``[B, n, 2]``, see
+    ``sampling.sample_bitstrings_batch``) -> heavy-hitter counts (``fbx_qv_count_heavy_dev``).  The distributions and the
+    ``B * shots * n`` bytes of shots never leave the device.
+
+    Returns ``(counts [B] int64, stats)`` with ``stats["heavy_prob"]`` and ``stats["heavy_count"]`` of the ideal circuits: under
+    depolarizing alone a shot of circuit b is heavy with probability ``(1 - lambda) heavy_prob_b + lambda heavy_count_b / 2^n``.
+    Circuit b draws from item b of the Philox stream keyed by ``seed`` (``None``: a fresh key, the rule of ``random_operators``),
+    so the counts equal those of the composed host calls on the same seed."""
+    from . import _lib
+    from .sampling import _noise, _raise_poisoned
+    width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
+    B, L = pairs.shape[:2]
+    if not MIN_WIDTH <= width <= MAX_WIDTH:
+        raise _lib.FbxError(_lib.FBX_ERR_UNSUPPORTED, f"simulate_heavy_output_counts_batch: width must be {MIN_WIDTH}..{MAX_WIDTH} "
+                                                      f"(got {width}); there is no host fallback")
+    N, W = 1 << width, _mask_words(width)
+    shots, lam, flips, _ = _noise(B, width, shots, depolarizing, readout_flip)
+    key = _stream_seed(seed)
+    if B == 0:
+        return np.zeros(0, dtype=np.int64), {"heavy_prob": np.zeros(0), "heavy_count": np.zeros(0, dtype=np.int32)}
+    DB = _lib.DeviceBuffer
+    lib = _lib.lib()
+    bufs = []
+
+    def dev(x):
+        bufs.append(x)
+        return x
+    try:
+        d_pairs, d_gates = dev(DB.from_array(pairs)), dev(DB.from_array(_lib.c128(flat)))
+        d_lam = dev(DB.from_array(lam)) if lam is not None else None
+        d_flips = dev(DB.from_array(flips)) if flips is not None else None
+        d_probs, d_mask, d_hp, d_hc = dev(DB(8 * B * N)), dev(DB(8 * B * W)), dev(DB(8 * B)), dev(DB(4 * B))
+        d_bits, d_status, d_counts = dev(DB(max(B * shots * width, 16))), dev(DB(4 * B)), dev(DB(8 * B))
+        _lib.check(lib.fbx_qv_heavy_outputs_dev(width, B, L, d_pairs.ptr, d_gates.ptr, d_probs.ptr, None, d_mask.ptr, d_hp.ptr,
+                                                d_hc.ptr))
+        _lib.check(lib.fbx_sample_bitstrings_dev(width, B, shots, d_probs.ptr, d_lam.ptr if d_lam else None,
+                                                 d_flips.ptr if d_flips else None, key, 0, d_bits.ptr, d_status.ptr))
+        _lib.check(lib.fbx_qv_count_heavy_dev(width, B, shots, d_bits.ptr, d_mask.ptr, d_counts.ptr))
+        counts = d_counts.to_array(np.int64, (B,))
+        stats = {"heavy_prob": d_hp.to_array(np.float64, (B,)), "heavy_count": d_hc.to_array(np.int32, (B,))}
+        if shots:
+            _raise_poisoned(d_status.to_array(np.int32, (B,)), 0)
+    finally:
+        for b in bufs:
+            b.free()
+    return counts, stats
 
 
 # ------------------------------------------------------------------------------------------------ statistics (host)

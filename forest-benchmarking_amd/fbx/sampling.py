@@ -1,0 +1,76 @@
+"""Measured bitstrings drawn on the device from outcome distributions (``fbx_sample_bitstrings``): the step between an ideal
+distribution -- ``quantum_volume.collect_heavy_outputs_batch(..., return_probabilities=True)``, a row of a confusion matrix, the
+diagonal of a state -- and the ``[shots, n]`` bit arrays that ``qc.run`` returns and every ``*_from_shots`` function of this
+package consumes.  The reference gets such arrays from a QVM; nothing of it is mirrored here.
+
+The stream is part of the C contract (include/fbx.h): a record depends on ``(seed, first_item + b, shot)`` and its item's inputs
+only, so a batch may be drawn in pieces, on any number of calls, and checked shot by shot on the host."""
+import ctypes as C
+
+import numpy as np
+
+from .operator_tools.random_operators import _stream_seed
+
+__all__ = ["sample_bitstrings_batch"]
+
+MIN_WIDTH, MAX_WIDTH = 1, 13
+
+
+def _noise(B, n, shots, depolarizing, readout_flip, first_item=0):
+    """The broadcasting of one call: (shots, lam [B] or None, flips [B, n, 2] or None, first_item)."""
+    shots, first_item = int(shots), int(first_item)
+    if shots < 0 or first_item < 0:
+        raise ValueError("need shots >= 0 and first_item >= 0")
+    lam = None
+    if depolarizing is not None:
+        lam = np.asarray(depolarizing, dtype=np.float64)
+        if lam.shape not in ((), (B,)):
+            raise ValueError(f"depolarizing must be a scalar or [B] = {(B,)}, not {lam.shape}")
+        lam = np.ascontiguousarray(np.broadcast_to(lam, (B,)))
+    flips = None
+    if readout_flip is not None:
+        flips = np.asarray(readout_flip, dtype=np.float64)
+        if flips.shape not in ((n, 2), (B, n, 2)):
+            raise ValueError(f"readout_flip must be [n, 2] = {(n, 2)} or [B, n, 2] = {(B, n, 2)}, not {flips.shape}")
+        flips = np.ascontiguousarray(np.broadcast_to(flips, (B, n, 2)))
+    return shots, lam, flips, first_item
+
+
+def _raise_poisoned(status, first_item):
+    bad = np.flatnonzero(status)
+    if bad.size:
+        b = int(bad[0])
+        raise ValueError(f"sample_bitstrings_batch: item {b} (global id {first_item + b}) cannot be sampled: a weight that is "
+                         f"negative or not finite, weights without a positive finite sum, or a depolarizing / readout_flip "
+                         f"value outside [0, 1] ({bad.size} such item(s) in the batch)")
+
+
+def sample_bitstrings_batch(probabilities, shots, depolarizing=None, readout_flip=None, seed=None, first_item=0,
+                            return_status=False):
+    """``probabilities [B, 2^n]`` (non-negative weights, not necessarily normalised; outcome index i has qubit 0 as its most
+    significant bit), n = 1..13 -> ``[B, shots, n]`` uint8 bit arrays, first column = qubit 0.
+
+    ``depolarizing`` (a scalar or ``[B]``): item b is drawn from ``(1 - lambda_b) p + lambda_b sum(p) / 2^n``.  ``readout_flip``
+    (``[n, 2]`` for the whole batch or ``[B, n, 2]``): after the draw, column j flips with probability ``[j, 0]`` when the drawn bit
+    is 0 (P(read 1 | 0)) and ``[j, 1]`` when it is 1 (P(read 0 | 1)), independently per bit.  ``seed=None`` takes a fresh key from
+    numpy's global stream (the rule of ``random_operators``); item b is global item ``first_item + b`` of the stream.
+
+    An item that cannot be sampled (a negative or non-finite weight, no positive finite sum, a probability outside [0, 1]) raises
+    ``ValueError`` naming the first one; with ``return_status=True`` nothing is raised and ``(bits, status [B] int32)`` comes back,
+    status 1 and a record of zeros for such an item, its neighbours untouched."""
+    from . import _lib
+    p = np.ascontiguousarray(probabilities, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] < 2 or p.shape[1] & (p.shape[1] - 1):
+        raise ValueError("probabilities must be [B, 2^n] with n >= 1")
+    B, N = p.shape
+    n = N.bit_length() - 1
+    shots, lam, flips, first_item = _noise(B, n, shots, depolarizing, readout_flip, first_item)
+    ok = MIN_WIDTH <= n <= MAX_WIDTH                     # (outside, the library refuses before it touches a buffer)
+    bits = np.zeros((B, shots, n) if ok else (0, 0, n), dtype=np.uint8)
+    status = np.zeros(B, dtype=np.int32)
+    _lib.check(_lib.lib().fbx_sample_bitstrings(n, B, shots, _lib.dptr(p), _lib.dptr(lam), _lib.dptr(flips), _stream_seed(seed),
+                                                first_item, bits.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.iptr(status)))
+    if return_status:
+        return bits, status
+    _raise_poisoned(status, first_item)
+    return bits

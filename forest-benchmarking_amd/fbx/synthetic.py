@@ -149,6 +149,15 @@ def qv_shots(probabilities, shots, depolarizing=0.0, seed=3000):
     return out
 
 
+def qv_shots_batch(probabilities, shots, depolarizing=0.0, readout_flip=None, seed=3000):
+    """``qv_shots`` drawn on the device (``sampling.sample_bitstrings_batch``): the same shapes and the same distribution, one launch
+    for the batch instead of one ``choice`` per circuit; optionally with readout flips (``[n, 2]`` or ``[B, n, 2]``).  The stream is
+    the device's (include/fbx.h), not numpy's: circuit b is item b of the Philox stream keyed by ``seed``, and the records differ
+    from those of ``qv_shots`` shot by shot."""
+    from .sampling import sample_bitstrings_batch
+    return sample_bitstrings_batch(probabilities, shots, depolarizing=depolarizing, readout_flip=readout_flip, seed=int(seed))
+
+
 def rb_data(n_qubits, depths, decay=0.97, shots=500, batch=1, seed=4000):
     """Synthetic randomized-benchmarking statistics in the shapes ``randomized_benchmarking.fit_rb_results_batch`` takes:
     ``(z_expectations, z_std_errs)``, both [batch, len(depths), 2^n - 1].  A sequence of depth m leaves the depolarised state
@@ -225,6 +234,22 @@ def readout_shots(confusion, shots, seed=6000):
         for r in range(N):
             idx = np.random.default_rng([int(seed), grp, r]).choice(N, size=int(shots), p=c[grp, r] / c[grp, r].sum())
             out[grp, r] = (idx[:, None] >> shifts) & 1
+    return out[0] if single else out
+
+
+def readout_shots_batch(confusion, shots, seed=6000):
+    """``readout_shots`` drawn on the device: every row of every confusion matrix is one item of ``sample_bitstrings_batch`` (row r
+    of group G is item ``G 2^g + r`` of the Philox stream keyed by ``seed``); the output has the shape of ``readout_shots``."""
+    from .sampling import sample_bitstrings_batch
+    c = np.asarray(confusion, dtype=np.float64)
+    single = c.ndim == 2
+    c = c[None] if single else c
+    if c.ndim != 3 or c.shape[1] != c.shape[2] or c.shape[1] < 2 or c.shape[1] & (c.shape[1] - 1):
+        raise ValueError("confusion must be [G, 2^g, 2^g]")
+    if int(shots) < 0 or c.min() < 0.0 or not np.allclose(c.sum(axis=2), 1.0):
+        raise ValueError("need shots >= 0 and rows that are probability distributions")
+    G, N = c.shape[:2]
+    out = sample_bitstrings_batch(c.reshape(G * N, N), shots, seed=int(seed)).reshape(G, N, int(shots), N.bit_length() - 1)
     return out[0] if single else out
 
 

@@ -500,6 +500,37 @@ int fbx_qv_count_heavy(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* 
 int fbx_qv_count_heavy_dev(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* d_bits, const uint64_t* d_heavy_mask,
                            int64_t* d_counts_out);
 
+/* ---------------------------------------------------------------- measured bitstrings from outcome distributions
+ * The step between a distribution and a bit record (what a QVM's run-and-measure does for the reference): B items of one width,
+ * n_shots shots each.  probs [B][2^n] outcome weights, non-negative and finite, not necessarily normalised; outcome index i has
+ * qubit 0 as its MOST significant bit (as fbx_qv_heavy_outputs).  depolarizing [B] or NULL (= 0): with T = sum_i p_i and lambda
+ * the item's value the sampled weights are w_i = p_i for lambda == 0, else (1 - lambda) p_i + lambda T / 2^n.  readout_flip
+ * [B][n][2] or NULL (= no flips): [j][0] = P(read 1 | drawn 0), [j][1] = P(read 0 | drawn 1) of column j, applied independently
+ * per bit after the draw.  bits_out [B][n_shots][n] uint8 0 / 1, first column = qubit 0: the records fbx_shots_to_moments,
+ * fbx_qv_count_heavy and fbx_bit_histogram read.  status_out [B] or NULL: 0 for a good item, 1 for a poisoned one.
+ *
+ * n_qubits 1..13 (the table of prefix sums lives in the LDS of one CU; others FBX_ERR_UNSUPPORTED, before any buffer is touched).
+ * B == 0 or n_shots == 0: nothing is done.  n_shots >= 2^32, a negative size, first_item < 0, NULL probs / bits_out: FBX_ERR_BAD_ARG.
+ *
+ * A poisoned item -- a weight that is negative or not finite, T not positive and finite, lambda outside [0, 1] or NaN, a flip
+ * probability outside [0, 1] or NaN -- gets status 1 and a record of zeros; its neighbours are untouched.
+ *
+ * THE STREAM (part of the contract: it is what a host check restates).  Shot s of the item with the global id g = first_item + b
+ * owns the Philox4x32-10 blocks with counter (g low, g high, s, t), t = 0, 1, 2, 3, and key (seed low, seed high); their words, in
+ * order, are x_0 .. x_15 (only the blocks that are needed are computed).  The draw is u = k * 2^-53, k = ((x_0 >> 5) << 26) |
+ * (x_1 >> 6): exact, in [0, 1).  With C the inclusive prefix sums of w, the outcome is the smallest i with C_i > u * C_{N-1}; if
+ * rounding leaves none, the last i with w_i > 0.  C is non-decreasing in i and repeats its predecessor exactly where w_i == 0 (the
+ * order in which it is summed is otherwise not specified), so an outcome of weight zero is never produced.  Column j, whose
+ * drawn bit is d, flips iff (double) x_{2 + j} * 2^-32 < readout_flip[j][d].  A record depends on (seed, g, s) and its item's
+ * inputs only: not on B, n_shots, the launch shape or the workgroup that drew it -- a call of B' items from first_item + k repeats
+ * items k .. k + B' - 1, and a call of fewer shots repeats the first shots.
+ * The _dev form enqueues on the calling thread's stream and does not synchronise. */
+int fbx_sample_bitstrings(int n_qubits, int64_t B, int64_t n_shots, const double* probs, const double* depolarizing,
+                          const double* readout_flip, uint64_t seed, int64_t first_item, uint8_t* bits_out, int32_t* status_out);
+int fbx_sample_bitstrings_dev(int n_qubits, int64_t B, int64_t n_shots, const double* d_probs, const double* d_depolarizing,
+                              const double* d_readout_flip, uint64_t seed, int64_t first_item, uint8_t* d_bits_out,
+                              int32_t* d_status_out);
+
 /* ---------------------------------------------------------------- curve fits (analysis/fitting.py, randomized_benchmarking.py,
  * qubit_spectroscopy.py)
  * fbx_curve_fit: B independent weighted non-linear least-squares fits, one per GPU lane, of the four models of

@@ -83,6 +83,15 @@ void pool_give(void* p);
 
 #define FBX_TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 
+// One kernel launch on the calling thread's stream with `lds_bytes` of dynamic LDS (past 64 KB that needs the attribute).
+template <class... P, class... A>
+inline int launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, A... args) {
+    if (lds_bytes > 0) FBX_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream(), static_cast<P>(args)...);
+    FBX_HIP(hipGetLastError());
+    return FBX_OK;
+}
+
 // Device block from the calling thread's pool (no hipMalloc / hipFree per call once the pool is warm); it goes back when the
 // DevBuf goes out of scope, whatever is still queued on it.  Whoever holds one waits for that work first: HostIO below does
 // so on every path, fbx_pgdb_process_ex drains its streams by hand, and the asynchronous `_dev` launchers that keep one as

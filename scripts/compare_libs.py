@@ -1,6 +1,8 @@
 """Bit-for-bit comparison of two builds of the library on the same inputs: PGDB (2 qubits on both kernels, 1 and 3 qubits), the
-state estimators and measures for 1-4 qubits incl. designs of more than 64 settings, Choi projections, conversions, the Kraus
-sweeps, and fbx_eigh / fbx_matmul / fbx_choi2kraus at every size class.
+state estimators and measures for 1-4 qubits incl. designs of more than 64 settings, Choi projections, every conversion route and
+Kraus sweep kernel (both forms of the 3-qubit ones, batches past the persistent grid, Kraus counts on either side of each kernel
+switch), the Kraus-pair / twirl / partial-trace / apply / fidelity / linear-inversion entry points, and fbx_eigh / fbx_matmul /
+fbx_choi2kraus at every size class.
 usage: python scripts/compare_libs.py libA.so libB.so      (names inside forest-benchmarking_amd/; FBX_LIBRARY selects each build)"""
 import os, subprocess, sys, hashlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,6 +101,56 @@ for N in (5, 33):
 for n in (1, 2):
     choi = st_.convert_batch("kraus", "choi", synthetic.kraus_batch(n, 3, 8, seed=7))
     out.append(H(*st_.choi2kraus_batch(choi)))
+# csrc/fbx_convert.hip, fbx_sweep.hip, fbx_superop.hip route by route: arbitrary complex matrices where the route is linear,
+# Hermitian non-PSD ones into chi (the |C| step)
+from fbx.operator_tools import compose_superoperators as cs, channel_approximation as ca, calculational as calc, apply_superoperator as ap
+REPS = ("choi", "superop", "pauli_liouville", "chi")
+PL_ROUTES = (("choi", "pauli_liouville"), ("superop", "pauli_liouville"), ("pauli_liouville", "choi"), ("pauli_liouville", "superop"))
+def mats(B, D, seed):
+    r = np.random.RandomState(seed)
+    x = r.randn(B, D, D) + 1j * r.randn(B, D, D)
+    return x, x + x.conj().transpose(0, 2, 1)
+def sweep(n, K, B, seed):
+    D = 4 ** n
+    k = np.ascontiguousarray(synthetic.kraus_batch(n, K, min(B, 8), seed=seed)[np.arange(B) % min(B, 8)])
+    ref = np.ascontiguousarray(st_.convert_batch("kraus", "pauli_liouville", synthetic.kraus_batch(n, 1, 1, seed=99))[0])
+    choi, ptm, chi = (np.empty((B, D, D), dtype=np.complex128) for _ in range(3))
+    fid = np.empty(B)
+    _lib.check(lib.fbx_kraus_sweep(n, B, K, _lib.dptr(k.view(np.float64)), _lib.dptr(ref.view(np.float64)), _lib.dptr(choi.view(np.float64)),
+                                   _lib.dptr(ptm.view(np.float64)), _lib.dptr(chi.view(np.float64)), _lib.dptr(fid)))
+    out.append(H(choi, ptm, chi, fid))
+for n in (1, 2, 3):
+    x, h = mats(5, 4 ** n, 50 + n)
+    k = synthetic.kraus_batch(n, 3, 5, seed=6)
+    out.append(H(*[st_.convert_batch("kraus", dst, k) for dst in ("superop",) + REPS]))
+    for src in REPS:
+        out.append(H(*[st_.convert_batch(src, dst, h if dst == "chi" else x) for dst in REPS if dst != src]))
+x, h = mats(2049, 64, 54)                                  # past the persistent grid of the 3-qubit register kernels
+out.append(H(*[st_.convert_batch(src, dst, x) for src, dst in PL_ROUTES]))
+sweep(3, 4, 2049, 8)
+os.environ["FBX_CONVERT3_V1"] = os.environ["FBX_SWEEP3_V1"] = "1"      # the first forms of the 3-qubit kernels
+out.append(H(*[st_.convert_batch(src, dst, x[:5]) for src, dst in PL_ROUTES]))
+out.append(H(*[st_.convert_batch("kraus", dst, synthetic.kraus_batch(3, 3, 5, seed=6)) for dst in REPS]))
+sweep(3, 4, 33, 9)
+del os.environ["FBX_CONVERT3_V1"], os.environ["FBX_SWEEP3_V1"]
+x, h = mats(2, 256, 55)
+k = synthetic.kraus_batch(4, 3, 2, seed=6)
+out.append(H(*[st_.convert_batch("kraus", dst, k) for dst in REPS]))
+out.append(H(*[st_.convert_batch(src, dst, x) for src in REPS for dst in REPS[:3] if dst != src], st_.convert_batch("choi", "chi", h)))
+k = rs.randn(5, 3, 3, 3) + 1j * rs.randn(5, 3, 3, 3)     # qutrits: the basis-free kernel
+sup = st_.convert_batch("kraus", "superop", k)
+out.append(H(sup, st_.convert_batch("kraus", "choi", k), st_.convert_batch("superop", "choi", sup), st_.convert_batch("choi", "superop", sup)))
+for n, K in ((2, 16), (2, 17), (3, 15), (3, 16)):           # either side of the pair kernel / of the composed form
+    sweep(n, K, 3, 100 * n + K)
+out.append(H(*[st_.convert_batch("kraus", dst, synthetic.kraus_batch(3, 40, 2, seed=340)) for dst in REPS[:1] + REPS[2:]]))   # past every LDS staging
+k2, k1 = rs.randn(4, 3, 4, 4) + 1j * rs.randn(4, 3, 4, 4), rs.randn(4, 2, 4, 4) + 1j * rs.randn(4, 2, 4, 4)
+x, h = mats(6, 16, 56)
+out.append(H(cs.tensor_channel_kraus_batch(k2, k1), cs.compose_channel_kraus_batch(k2, k1), ca.pauli_twirl_chi_matrix_batch(x),
+             calc.partial_trace_bipartite_batch(x, 2, 8, 0), calc.partial_trace_bipartite_batch(x, 2, 8, 1),
+             ap.apply_choi_matrix_2_state_batch(x, rand_states(6, 4, 57)), dm.process_fidelity_batch(x[:1], h), dm.process_fidelity_batch(x, h, entanglement=True)))
+for n in (1, 2):
+    design, _, e, c = synthetic.process_batch(n, "pauli", 9)
+    out.append(H(tomography.linear_inv_process_estimate_batch(design, e)))
 print(" ".join(out))
 '''
 res = []

@@ -45,7 +45,7 @@ def test_pairwise_conversions(gpu, n):
 
 def test_pairwise_conversions_3q_register_passes_against_the_first_form(gpu):
     """The 3-qubit routes between Choi / superoperator / Pauli-Liouville run two butterfly stages per pass in registers
-    (convert3_regs_kernel, csrc/fbx_superop.hip); the one-stage-per-pass kernels stay behind FBX_CONVERT3_V1=1.  Arbitrary
+    (convert3_regs_kernel, csrc/fbx_convert.hip); the one-stage-per-pass kernels stay behind FBX_CONVERT3_V1=1.  Arbitrary
     complex matrices (the conversions are linear maps: no structure of the input may be assumed), a batch larger than the
     persistent grid: both forms agree to rounding, the reshuffle routes bit for bit where no arithmetic is involved, and
     every route followed by its inverse returns the input."""
@@ -146,7 +146,7 @@ def test_kraus_sweep_fused(gpu, n):
 
 
 def test_kraus_sweep_3q_fused_kernel_against_reference_fixtures(gpu):
-    """The fused 3-qubit sweep (csrc/fbx_superop.hip sweep3_regs_kernel: kraus -> superoperator -> Pauli-Liouville + fidelity,
+    """The fused 3-qubit sweep (csrc/fbx_sweep.hip sweep3_regs_kernel: kraus -> superoperator -> Pauli-Liouville + fidelity,
     kraus -> Choi -> chi through one 64 x 64 LDS matrix) on six random CPTP Kraus sets against what the reference's
     kraus2choi / kraus2pauli_liouville / kraus2chi / process_fidelity returned (tests/golden/make_goldens.py --sweep3q);
     every subset of outputs gives the same numbers, and a batch larger than the persistent grid (2048 workgroups) repeats
@@ -266,6 +266,56 @@ def test_fused_sweep_odd_batches_and_kraus_counts(gpu, B, K):
     assert np.abs(fid - dm.process_fidelity_batch(ref, ptm)).max() < 1e-13
 
 
+def _sweep_against_the_oracle(n, K, B):
+    """fbx_kraus_sweep with all four outputs on B random CPTP sets of K operators, each output against the oracle."""
+    from fbx import _lib, synthetic
+    from fbx_oracle import measures as om, superops as so
+    D = 4 ** n
+    ks = np.ascontiguousarray(synthetic.kraus_batch(n, K, B, seed=100 * n + K))
+    ref = np.ascontiguousarray(so.kraus2pauli_liouville(list(synthetic.kraus_batch(n, 1, 1, seed=99)[0])), dtype=np.complex128)
+    choi = np.empty((B, D, D), complex); ptm = np.empty_like(choi); chi = np.empty_like(choi); fid = np.empty(B)
+    _lib.check(_lib.lib().fbx_kraus_sweep(n, B, K, _lib.dptr(ks.view(np.float64)), _lib.dptr(ref.view(np.float64)),
+                                          _lib.dptr(choi.view(np.float64)), _lib.dptr(ptm.view(np.float64)),
+                                          _lib.dptr(chi.view(np.float64)), _lib.dptr(fid)))
+    for b in range(B):
+        ops = list(ks[b])
+        want_ptm = so.kraus2pauli_liouville(ops)
+        assert np.abs(choi[b] - so.kraus2choi(ops)).max() < TOL, (n, K, b)
+        assert np.abs(ptm[b] - want_ptm).max() < TOL, (n, K, b)
+        assert np.abs(chi[b] - so.kraus2chi(ops)).max() < TOL, (n, K, b)
+        assert abs(fid[b] - om.process_fidelity(ref, want_ptm)) < TOL, (n, K, b)
+    return ks, choi
+
+
+@pytest.mark.parametrize("K", [16, 17])
+def test_kraus_sweep_2q_either_side_of_the_pair_kernel(gpu, K):
+    """Two qubits: up to 16 Kraus operators take sweep2q_pair_kernel, 17 are the only way into sweep_kernel<2>
+    (csrc/fbx_sweep.hip).  Both sides of that switch against the oracle.  (Not bit for bit against convert_batch: the pair
+    kernel and kraus_to fuse different products of the imaginary part, 2.8e-17 apart at K = 16.)"""
+    _sweep_against_the_oracle(2, K, 3)
+
+
+@pytest.mark.parametrize("K", [15, 16])
+def test_kraus_sweep_3q_either_side_of_the_composed_form(gpu, K):
+    """Three qubits: 15 Kraus operators are the last that fit the 80 KB of sweep3_regs_kernel, 16 the first that go through
+    the composed form (the pairwise conversions and process_fidelity_kernel, csrc/fbx_sweep.hip)."""
+    _sweep_against_the_oracle(3, K, 3)
+
+
+def test_three_qubit_conversions_from_more_kraus_operators_than_lds_stages(gpu):
+    """40 three-qubit Kraus operators are past the LDS staging of every fused kernel: fbx_convert answers from the basis-free
+    kernel and walks on from its (PSD) Choi matrix, and the refusal of the fused path is not left behind as the call's error."""
+    from fbx import _lib, synthetic
+    from fbx.operator_tools import convert_batch
+    from fbx_oracle import superops as so
+    ks = synthetic.kraus_batch(3, 40, 2, seed=340)
+    for dst, f in (("choi", so.kraus2choi), ("pauli_liouville", so.kraus2pauli_liouville), ("chi", so.kraus2chi)):
+        got = convert_batch("kraus", dst, ks)
+        assert _lib.lib().fbx_last_error() == b"", dst
+        for b in range(2):
+            assert np.abs(got[b] - f(list(ks[b]))).max() < TOL, (dst, b)
+
+
 def test_full_size_sweep_properties(gpu):
     """BASELINE config 3 size (1e6 two-qubit Kraus sets, K = 4), device-resident: size-independent checks --
     tiled inputs give bit-identical outputs, a sample of items matches the pairwise conversions, every
@@ -314,7 +364,7 @@ def test_full_size_sweep_properties(gpu):
 
 # ------------------------------------------------------------------ beyond three qubits / beyond qubits
 def test_four_qubit_conversions_match_the_oracle(gpu):
-    """256 x 256 superoperators (work matrices in HBM, csrc/fbx_superop.hip convert_big_kernel): every pairwise
+    """256 x 256 superoperators (work matrices in HBM, csrc/fbx_convert.hip convert_big_kernel): every pairwise
     conversion that does not need the 256 x 256 eigendecomposition of choi2kraus, against the oracle's dense
     basis-change matrices."""
     from fbx.operator_tools import superoperator_transformations as st

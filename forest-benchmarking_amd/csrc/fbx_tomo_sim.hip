@@ -1,0 +1,253 @@
+// fbx_tomo_sim.hip -- simulated tomography experiments (fbx_tomo_simulate): from true channels / states to the noisy
+// (expectations, total_counts) that the tomography estimators read -- the acquisition half the reference gets from a QVM.
+//
+// Two kernels.  tomo_poison_kernel (a wavefront per item) looks at every truth entry and flip probability of an item once and
+// writes its status.  tomo_sim_kernel takes a unit = (item b, grouped setting g): it computes the mean of the measured +-1
+// product from the design's own tables -- tr[P Lambda(rho_s)] = sum_j R[P][j] c_j(s), a row of the item's transfer matrix against
+// a row of DesignDev::Ct; for a state design the trace against the density matrix itself -- with the readout flips folded in
+// exactly (include/fbx.h), and then counts the shots whose Philox word falls below the threshold.  The truth is read from L2:
+// per setting the mean costs D fused multiply-adds per term, the counting n_shots / 4 Philox blocks of about a hundred
+// instructions each, so the counting is the cost from a few dozen shots on.
+//
+// The work split is chosen by the number of units alone: from TOMO_LANE_MIN_UNITS on a LANE takes a unit and counts all its
+// shots (the chip is full without cutting a setting); below, a WAVEFRONT takes a unit, lane l counts the Philox blocks l, l + 64,
+// ... and the 64 partial counts are summed (integers, exactly, in double).  A value depends on (seed, item id, setting, mean, shots)
+// only: both splits evaluate the mean with the same code in the same order and count the same words.
+#include "fbx_common.hpp"
+
+namespace fbx {
+
+constexpr int TOMO_THREADS = 256;
+#ifndef FBX_TOMO_LANE_MIN_UNITS
+#define FBX_TOMO_LANE_MIN_UNITS 131072           // 256 CUs x 4 SIMDs x 64 lanes x 2 wavefronts: a lane per setting fills the chip
+#endif
+constexpr uint32_t TOMO_KEY_TAG = 0x544F4D4Fu;   // "TOMO": keeps the stream apart from fbx_sample_bitstrings under one seed
+
+__device__ __forceinline__ bool tomo_bad_probability(double v) { return !(v >= 0.0 && v <= 1.0); }      // NaN included
+
+// status[b] = 1 when item b has a non-finite truth entry or a flip probability outside [0, 1] (NaN included), else 0
+__global__ void __launch_bounds__(TOMO_THREADS)
+tomo_poison_kernel(long long B, int truth_len, int flip_len, const double* __restrict__ truth, const double* __restrict__ flips,
+                   int* __restrict__ status) {
+    const long long b = (long long)blockIdx.x * (TOMO_THREADS / 64) + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const double* t = truth + b * truth_len;
+    bool bad = false;
+    for (int i = lane; i < truth_len; i += 64) {
+        const double v = t[i];
+        if (!(fabs(v) < __builtin_inf())) bad = true;
+    }
+    if (flips && lane < flip_len && tomo_bad_probability(flips[b * flip_len + lane])) bad = true;
+    const unsigned long long any = __ballot(bad);
+    if (lane == 0) status[b] = any ? 1 : 0;
+}
+
+// tr[P rho] of the Pauli with index `pidx` (base-4 digits, qubit 0 most significant): P = i^ny X^x Z^z, P |c> = i^ny (-1)^{|c & z|} |c ^ x>
+__device__ __forceinline__ double tomo_trace_state(const cplx* __restrict__ rho, int n, int pidx) {
+    int x = 0, z = 0, ny = 0;
+    for (int t = 0; t < n; ++t) {
+        const int code = (pidx >> (2 * t)) & 3;
+        x |= ((code == 1) | (code == 2)) << t; z |= ((code == 2) | (code == 3)) << t; ny += code == 2;
+    }
+    const int d = 1 << n;
+    double acc = 0.0;
+    for (int c = 0; c < d; ++c) {
+        const cplx v = rho[c * d + (c ^ x)];
+        double term = (ny & 1) ? v.im : v.re;               // Re(i^ny v): re, -im, -re, im
+        if (((ny + 1) >> 1) & 1) term = -term;
+        acc += (__popc(c & z) & 1) ? -term : term;
+    }
+    return acc;
+}
+
+// tr[P Lambda(rho_s)] = sum_j R[P][j] c_j(s): row `pidx` of the transfer matrix against the state's Bloch coefficients
+__device__ __forceinline__ double tomo_trace_process(const double* __restrict__ R, const double* __restrict__ ct, int D, int pidx) {
+    const double* row = R + (size_t)pidx * D;
+    double acc = 0.0;
+    for (int j = 0; j < D; ++j) acc = fma(row[j], ct[j], acc);
+    return acc;
+}
+
+// The mean of the measured +-1 product of the setting with the packed (state, Pauli) `sp` (include/fbx.h): over the subsets T
+// of the Pauli's support, prod_{S \ T} a_j prod_T b_j tr[P_T .]; without flips a = 0 and b = 1, and only T = S is left.
+__device__ double tomo_mean(const DesignDev& des, const double* __restrict__ truth, const double* __restrict__ flip, uint32_t sp) {
+    const int n = des.n, pidx = (int)(sp & 0xFFFFu), s = (int)(sp >> 16);
+    int support = 0;
+    double a[5], bb[5];
+#pragma unroll
+    for (int t = 0; t < 5; ++t) {                             // (fixed bounds: a and bb stay in registers)
+        if (t >= n) { a[t] = 0.0; bb[t] = 1.0; continue; }
+        if ((pidx >> (2 * t)) & 3) support |= 1 << t;
+        const int q = n - 1 - t;                              // digit t belongs to qubit n - 1 - t
+        const double f0 = flip ? flip[2 * q] : 0.0, f1 = flip ? flip[2 * q + 1] : 0.0;
+        a[t] = f1 - f0; bb[t] = 1.0 - f0 - f1;
+    }
+    if (support == 0) return 1.0;
+    const double* ct = des.Ct + (size_t)s * des.D;
+    double mu = 0.0;
+    for (int T = support;; T = (T - 1) & support) {
+        double w = 1.0;
+        int keep = 0;
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            if (!((support >> t) & 1)) continue;
+            if ((T >> t) & 1) { w *= bb[t]; keep |= 3 << (2 * t); } else { w *= a[t]; }
+        }
+        if (w != 0.0) {
+            const double tr = T == 0 ? 1.0
+                            : des.kind == FBX_KIND_PROCESS ? tomo_trace_process(truth, ct, des.D, pidx & keep)
+                                                           : tomo_trace_state(reinterpret_cast<const cplx*>(truth), n, pidx & keep);
+            mu = fma(w, tr, mu);
+        }
+        if (T == 0) break;
+    }
+    return mu;
+}
+
+// How many of the Philox blocks first, first + step, ... of the setting (g, k) hold words below t (< 2^32); the last block of a
+// shot count that is no multiple of 4 counts its first n_shots & 3 words only.
+__device__ __forceinline__ uint32_t tomo_count(uint32_t t, uint32_t g0, uint32_t g1, uint32_t k, uint32_t k0, uint32_t k1,
+                                               uint32_t first, uint32_t step, uint32_t n_shots) {
+    const uint32_t full = n_shots >> 2, tail = n_shots & 3u;
+    uint32_t cnt = 0;
+    for (uint32_t j = first; j < full; j += step) {
+        uint32_t c[4] = {g0, g1, k, j};
+        philox4x32_10(c, k0, k1);
+        cnt += (uint32_t)(c[0] < t) + (uint32_t)(c[1] < t) + (uint32_t)(c[2] < t) + (uint32_t)(c[3] < t);
+    }
+    if (tail && full % step == first) {
+        uint32_t c[4] = {g0, g1, k, full};
+        philox4x32_10(c, k0, k1);
+        cnt += (uint32_t)(c[0] < t) + (uint32_t)(tail > 1 && c[1] < t) + (uint32_t)(tail > 2 && c[2] < t);
+    }
+    return cnt;
+}
+
+// unit u = (item u / m, grouped setting u % m); LANE: a lane per unit, else a wavefront per unit
+template <bool LANE>
+__global__ void __launch_bounds__(TOMO_THREADS)
+tomo_sim_kernel(DesignDev des, long long B, const double* __restrict__ truth, int truth_len, const double* __restrict__ flips,
+                unsigned n_shots, unsigned long long seed, long long first_item, const int* __restrict__ status,
+                double* __restrict__ expect_out, double* __restrict__ counts_out, double* __restrict__ std_err_out,
+                double* __restrict__ exact_out) {
+    const long long units = B * des.m;
+    const int lane = threadIdx.x & 63;
+    const long long u = LANE ? (long long)blockIdx.x * TOMO_THREADS + threadIdx.x
+                             : (long long)blockIdx.x * (TOMO_THREADS / 64) + uniform((int)(threadIdx.x >> 6));
+    if (u >= units) return;
+    const long long b = u / des.m;
+    const int g = (int)(u - b * des.m), k = des.order[g];
+    const double coef = des.coef[g];
+    const long long out = b * des.m + k;
+    const double nd = (double)n_shots;
+    if (status[b]) {
+        if (!LANE && lane != 0) return;
+        const double nan = __builtin_nan("");
+        if (expect_out) expect_out[out] = nan;
+        if (std_err_out) std_err_out[out] = nan;
+        if (exact_out) exact_out[out] = nan;
+        if (counts_out) counts_out[out] = nd;
+        return;
+    }
+    const double mu = tomo_mean(des, truth + b * truth_len, flips ? flips + b * 2 * des.n : nullptr, des.sp[g]);
+    if (exact_out && (LANE || lane == 0)) exact_out[out] = coef * mu;
+    if (n_shots == 0) return;
+    double q = 0.5 * mu + 0.5;
+    q = fmin(fmax(q, 0.0), 1.0);
+    const unsigned long long t = (unsigned long long)(q * 0x1p32);
+    unsigned long long k_plus;
+    if (t >> 32) {
+        k_plus = n_shots;                                       // every word is below 2^32: no draws
+    } else if (t == 0) {
+        k_plus = 0;
+    } else {
+        const unsigned long long gid = (unsigned long long)(first_item + b);
+        const uint32_t k0 = (uint32_t)seed ^ TOMO_KEY_TAG, k1 = (uint32_t)(seed >> 32);
+        if constexpr (LANE) {
+            k_plus = tomo_count((uint32_t)t, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)k, k0, k1, 0u, 1u, n_shots);
+        } else {
+            const uint32_t part = tomo_count((uint32_t)t, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)k, k0, k1, (uint32_t)lane,
+                                             64u, n_shots);
+            k_plus = (unsigned long long)wave_sum((double)part);    // integers below 2^32: the sum is exact
+        }
+    }
+    if (!LANE && lane != 0) return;
+    const unsigned long long k_minus = n_shots - k_plus;
+    if (expect_out) expect_out[out] = coef * ((double)((long long)k_plus - (long long)k_minus) / nd);
+    if (counts_out) counts_out[out] = nd;
+    if (std_err_out) std_err_out[out] = fabs(coef) * sqrt((double)(k_plus * k_minus) * 4.0 / nd) / nd;
+}
+
+static int tomo_check(const fbx_design* design, int64_t B, const void* truth, int64_t n_shots, int64_t first_item,
+                      const void* expect, const void* counts, const void* std_err, const void* exact) {
+    FBX_REQUIRE(B >= 0 && n_shots >= 0 && first_item >= 0, "fbx_tomo_simulate: need B >= 0, n_shots >= 0 and first_item >= 0");
+    FBX_REQUIRE(n_shots < ((int64_t)1 << 32), "fbx_tomo_simulate: n_shots must be below 2^32");
+    FBX_REQUIRE(truth != nullptr, "fbx_tomo_simulate: NULL truth");
+    FBX_REQUIRE(expect || counts || std_err || exact, "fbx_tomo_simulate: every output is NULL");
+    FBX_REQUIRE(n_shots > 0 || !(expect || counts || std_err),
+                "fbx_tomo_simulate: n_shots == 0 gives exact_out only (expect_out, counts_out and std_err_out must be NULL)");
+    FBX_TRY(check_design(design, "fbx_tomo_simulate"));
+    FBX_REQUIRE(B <= INT64_MAX / 65536 / 4096, "fbx_tomo_simulate: B * m overflows");
+    return FBX_OK;
+}
+
+static int tomo_truth_len(const DesignDev& d) { return d.kind == FBX_KIND_PROCESS ? d.D * d.D : 2 * d.D; }
+
+}  // namespace fbx
+
+using namespace fbx;
+
+extern "C" {
+
+int fbx_tomo_simulate_dev(const fbx_design* design, int64_t B, const double* d_truth, int64_t n_shots, const double* d_readout_flip,
+                          uint64_t seed, int64_t first_item, double* d_expect_out, double* d_counts_out, double* d_std_err_out,
+                          double* d_exact_out, int32_t* d_status_out) {
+    FBX_TRY(tomo_check(design, B, d_truth, n_shots, first_item, d_expect_out, d_counts_out, d_std_err_out, d_exact_out));
+    FBX_TRY(ensure_device());
+    if (B == 0) return FBX_OK;
+    const DesignDev& des = design->dev;
+    const int truth_len = tomo_truth_len(des);
+    DevBuf scratch;                                  // the status when the caller does not want it (stream order protects it)
+    int32_t* status = d_status_out;
+    if (!status) { FBX_TRY(scratch.alloc(sizeof(int32_t) * (size_t)B)); status = scratch.as<int32_t>(); }
+    constexpr int WAVES = TOMO_THREADS / 64;
+    hipLaunchKernelGGL(tomo_poison_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(TOMO_THREADS), 0, stream(), (long long)B,
+                       truth_len, 2 * des.n, d_truth, d_readout_flip, status);
+    FBX_HIP(hipGetLastError());
+    const int64_t units = B * des.m;
+    if (units >= FBX_TOMO_LANE_MIN_UNITS) {
+        const int64_t blocks = (units + TOMO_THREADS - 1) / TOMO_THREADS;
+        FBX_REQUIRE(blocks < ((int64_t)1 << 31), "fbx_tomo_simulate: B * m is beyond one launch; cut the batch with first_item");
+        hipLaunchKernelGGL(tomo_sim_kernel<true>, dim3((unsigned)blocks), dim3(TOMO_THREADS), 0, stream(), des, (long long)B, d_truth,
+                           truth_len, d_readout_flip, (unsigned)n_shots, (unsigned long long)seed, (long long)first_item,
+                           (const int*)status, d_expect_out, d_counts_out, d_std_err_out, d_exact_out);
+    } else {
+        hipLaunchKernelGGL(tomo_sim_kernel<false>, dim3((unsigned)((units + WAVES - 1) / WAVES)), dim3(TOMO_THREADS), 0, stream(), des,
+                           (long long)B, d_truth, truth_len, d_readout_flip, (unsigned)n_shots, (unsigned long long)seed,
+                           (long long)first_item, (const int*)status, d_expect_out, d_counts_out, d_std_err_out, d_exact_out);
+    }
+    FBX_HIP(hipGetLastError());
+    return FBX_OK;
+}
+
+int fbx_tomo_simulate(const fbx_design* design, int64_t B, const double* truth, int64_t n_shots, const double* readout_flip,
+                      uint64_t seed, int64_t first_item, double* expect_out, double* counts_out, double* std_err_out,
+                      double* exact_out, int32_t* status_out) {
+    FBX_TRY(tomo_check(design, B, truth, n_shots, first_item, expect_out, counts_out, std_err_out, exact_out));
+    FBX_TRY(ensure_device());
+    if (B == 0) return FBX_OK;
+    const size_t n = (size_t)B, m = (size_t)design->dev.m;
+    HostIO io; double *dt, *df = nullptr, *de, *dc, *ds, *dx; int32_t* dst;
+    FBX_TRY(io.in(truth, n * (size_t)tomo_truth_len(design->dev), &dt));
+    if (readout_flip) FBX_TRY(io.in(readout_flip, n * 2 * (size_t)design->dev.n, &df));
+    FBX_TRY(io.out_opt(expect_out, n * m, &de));
+    FBX_TRY(io.out_opt(counts_out, n * m, &dc));
+    FBX_TRY(io.out_opt(std_err_out, n * m, &ds));
+    FBX_TRY(io.out_opt(exact_out, n * m, &dx));
+    FBX_TRY(io.out_opt(status_out, n, &dst));
+    FBX_TRY(fbx_tomo_simulate_dev(design, B, dt, n_shots, df, seed, first_item, de, dc, ds, dx, dst));
+    return io.finish();
+}
+
+}  // fbx C ABI

@@ -277,3 +277,62 @@ def ghz_shots(n, flip_probability, shots, seed=8000):
     side = rng.integers(0, 2, size=(int(shots), 1), dtype=np.uint8)
     flips = rng.random((int(shots), int(n))) < flip_probability
     return (side ^ flips).astype(np.uint8)
+
+
+# --------------------------------------------------------------------------------------------------
+# The stream of fbx_tomo_simulate (include/fbx.h), restated in numpy from the contract: what a host program checks the
+# device's simulated tomography counts against.
+# --------------------------------------------------------------------------------------------------
+TOMO_KEY_TAG = 0x544F4D4F
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """One Philox4x32-10 block per element (Salmon et al., SC'11): counter words and key words as uint64 arrays or scalars
+    holding 32-bit values -> the four output words (uint64 arrays holding 32-bit values)."""
+    mask = np.uint64(0xFFFFFFFF)
+    m0, m1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) for c in (c0, c1, c2, c3))
+    k0, k1 = np.uint64(k0), np.uint64(k1)
+    for _ in range(10):
+        p0, p1 = m0 * c0, m1 * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & mask, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & mask, (k1 + np.uint64(0xBB67AE85)) & mask
+    return c0, c1, c2, c3
+
+
+def restate_tomography_counts(exact, coefs, shots, seed, first_item=0):
+    """The counts ``tomography.simulate_*_tomography_batch`` draws, restated on the host from the contract of
+    ``fbx_tomo_simulate`` (include/fbx.h): ``exact [B, m]`` = coefficient times the mean of the measured product (the
+    ``return_exact`` output), ``coefs [m]`` the non-zero observable coefficients, ``shots`` = N >= 1, ``seed`` the 64-bit key and
+    item b the global item ``first_item + b``.  Per setting: mu = exact / coef, q = 0.5 mu + 0.5 clamped to [0, 1], t =
+    floor(q 2^32); shot s counts +1 iff word ``s & 3`` of the Philox4x32-10 block with counter (g low, g high, k, s >> 2) and
+    key (seed low ^ 0x544F4D4F, seed high) is below t.  Returns ``(expectations, total_counts, std_errs, k_plus)``, all [B, m],
+    ``k_plus`` int64: expectation = coef (k+ - k-) / N, std_err = |coef| sqrt(4 k+ k- / N) / N."""
+    exact = np.atleast_2d(np.asarray(exact, dtype=np.float64))
+    B, m = exact.shape
+    coefs = np.broadcast_to(np.asarray(coefs, dtype=np.float64), (m,))
+    N, seed, first_item = int(shots), int(seed) & (2 ** 64 - 1), int(first_item)
+    if not 1 <= N < 2 ** 32 or first_item < 0 or not np.all(coefs != 0.0):
+        raise ValueError("need 1 <= shots < 2^32, first_item >= 0 and non-zero coefficients")
+    mu = exact / coefs[None, :]
+    q = np.clip(0.5 * mu + 0.5, 0.0, 1.0)
+    t = np.floor(q * 2.0 ** 32).astype(np.uint64)                       # in [0, 2^32]
+    k0, k1 = (seed & 0xFFFFFFFF) ^ TOMO_KEY_TAG, seed >> 32
+    n_blocks = (N + 3) // 4
+    blocks = np.arange(n_blocks, dtype=np.uint64)
+    valid = [4 * blocks + np.uint64(w) < np.uint64(N) for w in range(4)]  # the last block of a count that is no multiple of 4
+    k_plus = np.zeros((B, m), dtype=np.int64)
+    rows = max(1, (1 << 21) // n_blocks)                                 # settings per pass: about 2^21 blocks at a time
+    ks = np.arange(m, dtype=np.uint64)
+    for b in range(B):
+        g = first_item + b
+        for lo in range(0, m, rows):
+            k = ks[lo:lo + rows, None]
+            words = _philox4x32_10(np.uint64(g & 0xFFFFFFFF), np.uint64(g >> 32), k, blocks[None, :], k0, k1)
+            tt = t[b, lo:lo + rows, None]
+            k_plus[b, lo:lo + rows] = sum(((w < tt) & v[None, :]).sum(axis=1) for w, v in zip(words, valid))
+    k_minus = N - k_plus
+    e = coefs[None, :] * ((k_plus - k_minus).astype(np.float64) / float(N))
+    prod = np.array([[int(p) * int(q_) * 4 for p, q_ in zip(rp, rm)] for rp, rm in zip(k_plus, k_minus)], dtype=object)
+    s = np.abs(coefs)[None, :] * np.sqrt(prod.astype(np.float64) / float(N)) / float(N)
+    return e, np.full((B, m), float(N)), s, k_plus

@@ -647,3 +647,205 @@ def estimate_by_qubit_groups(results, qubit_groups, kind="process", estimator="p
         for g, x in zip(groups, est):
             out[g] = x
     return out
+
+
+# ==================================================================================================
+# SIMULATED experiments (fbx_tomo_simulate): truth -> the noisy (expectations, total_counts) the estimators above read.  The
+# acquisition half of do_tomography (observable_estimation.py:856-920, a QVM in the reference) as one device call.
+# ==================================================================================================
+_SIM_REPS = ("pauli_liouville", "unitary", "kraus", "choi")
+_SIM_ESTIMATORS = ("pgdb", "linear_inv")
+MAX_SHOTS = 2 ** 32 - 1
+
+
+def _sim_process_truth(design: Design, channels, rep):
+    """The real Pauli transfer matrices [B, D, D] of ``channels`` given in ``rep``; shape errors are raised before the library
+    is touched, the conversion itself runs on the device (``convert_batch``)."""
+    if rep not in _SIM_REPS:
+        raise ValueError(f"rep must be one of {_SIM_REPS}, not {rep!r}")
+    if design.kind != "process":
+        raise ValueError("simulate_process_tomography_batch needs a process design")
+    d, D = design.dim, design.dim ** 2
+    x = np.asarray(channels)
+    if rep == "pauli_liouville":
+        if x.ndim == 2:
+            x = x[None]
+        if x.ndim != 3 or x.shape[1:] != (D, D):
+            raise ValueError(f"pauli_liouville channels must be [B, {D}, {D}]")
+        if np.iscomplexobj(x):
+            if np.any(x.imag != 0.0):
+                raise ValueError("pauli_liouville channels must be real")
+            x = x.real
+        return np.ascontiguousarray(x, dtype=np.float64)
+    if rep == "unitary":
+        if x.ndim == 2:
+            x = x[None]
+        if x.ndim != 3 or x.shape[1:] != (d, d):
+            raise ValueError(f"unitary channels must be [B, {d}, {d}]")
+        x, src = x[:, None], "kraus"
+    elif rep == "kraus":
+        if x.ndim == 3:
+            x = x[None]
+        if x.ndim != 4 or x.shape[1] < 1 or x.shape[2:] != (d, d):
+            raise ValueError(f"kraus channels must be [B, K, {d}, {d}]")
+        src = "kraus"
+    else:
+        if x.ndim == 2:
+            x = x[None]
+        if x.ndim != 3 or x.shape[1:] != (D, D):
+            raise ValueError(f"choi channels must be [B, {D}, {D}]")
+        src = "choi"
+    from .operator_tools.superoperator_transformations import convert_batch
+    return np.ascontiguousarray(convert_batch(src, "pauli_liouville", x).real)
+
+
+def _sim_state_truth(design: Design, states):
+    if design.kind != "state":
+        raise ValueError("simulate_state_tomography_batch needs a state design")
+    d = design.dim
+    x = np.asarray(states)
+    if x.ndim == 2:
+        x = x[None]
+    if x.ndim != 3 or x.shape[1:] != (d, d):
+        raise ValueError(f"states must be [B, {d}, {d}]")
+    return _lib.c128(x)
+
+
+def _sim_noise(B, n, shots, readout_flip, seed, first_item):
+    shots, first_item = int(shots), int(first_item)
+    if not 1 <= shots <= MAX_SHOTS or first_item < 0:
+        raise ValueError("need 1 <= shots < 2^32 and first_item >= 0")
+    flips = None
+    if readout_flip is not None:
+        flips = np.asarray(readout_flip, dtype=np.float64)
+        if flips.shape not in ((n, 2), (B, n, 2)):
+            raise ValueError(f"readout_flip must be [n, 2] = {(n, 2)} or [B, n, 2] = {(B, n, 2)}, not {flips.shape}")
+        flips = np.ascontiguousarray(np.broadcast_to(flips, (B, n, 2)))
+    from .operator_tools.random_operators import _stream_seed
+    return shots, flips, _stream_seed(seed), first_item
+
+
+def _simulate_batch(who, design, truth, shots, readout_flip, seed, first_item, return_std_errs, return_exact, return_status):
+    B, m = truth.shape[0], design.m
+    shots, flips, seed, first_item = _sim_noise(B, design.n_qubits, shots, readout_flip, seed, first_item)
+    e, c = np.empty((B, m)), np.empty((B, m))
+    se = np.empty((B, m)) if return_std_errs else None
+    ex = np.empty((B, m)) if return_exact else None
+    status = np.zeros(B, dtype=np.int32)
+    _lib.check(_lib.lib().fbx_tomo_simulate(design.handle, B, _lib.dptr(truth.view(np.float64)), shots, _lib.dptr(flips), seed,
+                                            first_item, _lib.dptr(e), _lib.dptr(c), _lib.dptr(se), _lib.dptr(ex),
+                                            _lib.iptr(status)))
+    if not return_status:
+        bad = np.flatnonzero(status)
+        if bad.size:
+            b = int(bad[0])
+            raise ValueError(f"{who}: item {b} (global id {first_item + b}) cannot be simulated: a truth entry that is not finite "
+                             f"or a readout_flip value outside [0, 1] ({bad.size} such item(s) in the batch)")
+    out = (e, c) + ((se,) if return_std_errs else ()) + ((ex,) if return_exact else ())
+    return out + ((status,) if return_status else ())
+
+
+def simulate_process_tomography_batch(design: Design, channels, shots, rep="pauli_liouville", readout_flip=None, seed=None,
+                                      first_item=0, return_std_errs=False, return_exact=False, return_status=False):
+    """B true channels measured with the settings of a process design (1..3 qubits), ``shots`` shots per setting, on the device:
+    ``(expectations [B, m], total_counts [B, m][, std_errs][, exact])`` -- what ``pgdb_process_estimate_batch`` and
+    ``linear_inv_process_estimate_batch`` take.
+
+    ``channels``: Pauli transfer matrices [B, D, D] (``rep="pauli_liouville"``, the reference's convention), or ``"unitary"``
+    [B, d, d], ``"kraus"`` [B, K, d, d], ``"choi"`` [B, D, D], converted by the package's conversion kernels.  ``readout_flip``
+    ([n, 2] for the batch or [B, n, 2]): ``[j, 0]`` = P(read 1 | drawn 0), ``[j, 1]`` = P(read 0 | drawn 1) of qubit j,
+    independent per bit; the means take them in exactly.  ``seed=None`` takes a fresh key from numpy's global stream; item b is
+    global item ``first_item + b`` of the stream, which is part of the C contract (include/fbx.h) and restated on the host by
+    ``synthetic.restate_tomography_counts``.  ``exact`` is the coefficient times the mean of the measured product (flips
+    included), ``std_errs`` the reference's ``sqrt(var / N)``.  An item with a non-finite truth entry or a flip probability
+    outside [0, 1] raises ``ValueError``; with ``return_status=True`` nothing is raised and ``status [B]`` is appended: 1 and NaN
+    values for such an item, its neighbours untouched."""
+    truth = _sim_process_truth(design, channels, rep)
+    return _simulate_batch("simulate_process_tomography_batch", design, truth, shots, readout_flip, seed, first_item,
+                           return_std_errs, return_exact, return_status)
+
+
+def simulate_state_tomography_batch(design: Design, states, shots, readout_flip=None, seed=None, first_item=0,
+                                    return_std_errs=False, return_exact=False, return_status=False):
+    """B true density matrices [B, d, d] measured with the settings of a state design (1..5 qubits): the options and returns of
+    ``simulate_process_tomography_batch``; the result is what the state estimators take."""
+    truth = _sim_state_truth(design, states)
+    return _simulate_batch("simulate_state_tomography_batch", design, truth, shots, readout_flip, seed, first_item,
+                           return_std_errs, return_exact, return_status)
+
+
+def simulate_tomography_results(qubits, kind, truth, shots, in_basis="pauli", **kw) -> List[ExperimentResult]:
+    """One simulated experiment as the ``List[ExperimentResult]`` the reference-signature estimators and ``estimate_dfe`` read:
+    the stand-in for the acquisition half of ``do_tomography``.  ``kind`` "process" (``truth`` a channel, ``rep`` and the other
+    options of ``simulate_process_tomography_batch`` by keyword; settings of ``generate_process_tomography_settings(qubits,
+    in_basis)``) or "state" (``truth`` a density matrix; ``generate_state_tomography_settings(qubits)``)."""
+    qubits = list(qubits)
+    if kind not in ("process", "state"):
+        raise ValueError("kind must be 'process' or 'state'")
+    for name in ("return_std_errs", "return_exact", "return_status", "first_item"):
+        if name in kw:
+            raise ValueError(f"simulate_tomography_results does not take {name}")
+    if kind == "process":
+        design = process_design(len(qubits), in_basis)
+        e, c, se = simulate_process_tomography_batch(design, truth, shots, return_std_errs=True, **kw)
+    else:
+        design = state_design(len(qubits))
+        e, c, se = simulate_state_tomography_batch(design, truth, shots, return_std_errs=True, **kw)
+    if e.shape[0] != 1:
+        raise ValueError("simulate_tomography_results covers one experiment: pass one channel or state")
+    return [ExperimentResult(setting=s, expectation=float(x), total_counts=int(n), std_err=float(v))
+            for s, x, n, v in zip(_settings_of(design, qubits), e[0], c[0], se[0])]
+
+
+def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pauli_liouville", readout_flip=None, seed=None,
+                                        first_item=0, estimator="pgdb", **estimator_kw):
+    """The resident loop truth -> shots -> estimate -> fidelity to truth: the truth's transfer matrices are uploaded once,
+    ``fbx_tomo_simulate_dev`` writes (expectations, counts) into HBM, the estimator's ``_dev`` form (``estimator`` "pgdb":
+    ``trace_preserving``, ``mode``, ``max_iters`` by keyword as in ``pgdb_process_estimate_batch``; "linear_inv": no options)
+    reconstructs from them, and the Choi matrices go through Choi -> Pauli-Liouville into ``fbx_process_fidelity_dev`` against
+    the truth.  Returns ``(chois [B, D, D], fidelity_to_truth [B])`` -- all that leaves the device; bit for bit what
+    ``simulate_process_tomography_batch``, the batched estimator and ``distance_measures.process_fidelity_batch`` give when
+    composed through the host."""
+    if estimator not in _SIM_ESTIMATORS:
+        raise ValueError(f"estimator must be one of {_SIM_ESTIMATORS}, not {estimator!r}")
+    allowed = {"trace_preserving", "mode", "max_iters"} if estimator == "pgdb" else set()
+    if set(estimator_kw) - allowed:
+        raise ValueError(f"estimator {estimator!r} does not take {sorted(set(estimator_kw) - allowed)}")
+    mode = estimator_kw.get("mode", "converge")
+    if mode not in ("converge", "fixed"):
+        raise ValueError("mode must be 'converge' or 'fixed'")
+    truth = _sim_process_truth(design, channels, rep)
+    B, m, n, D = truth.shape[0], design.m, design.n_qubits, design.dim ** 2
+    shots, flips, seed, first_item = _sim_noise(B, n, shots, readout_flip, seed, first_item)
+    if B == 0:
+        raise ValueError("need a non-empty batch")
+    lib, DB = _lib.lib(), _lib.DeviceBuffer
+    d_truth, d_truth_c = DB.from_array(truth), DB.from_array(truth.astype(np.complex128))
+    d_flips = DB.from_array(flips) if flips is not None else None
+    d_e, d_c, d_status = DB(B * m * 8), DB(B * m * 8), DB(B * 4)
+    d_choi, d_ptm, d_f = DB(B * D * D * 16), DB(B * D * D * 16), DB(B * 8)
+    bufs = [b for b in (d_truth, d_truth_c, d_flips, d_e, d_c, d_status, d_choi, d_ptm, d_f) if b is not None]
+    try:
+        _lib.check(lib.fbx_tomo_simulate_dev(design.handle, B, d_truth.ptr, shots, d_flips.ptr if d_flips else None, seed,
+                                             first_item, d_e.ptr, d_c.ptr, None, None, d_status.ptr))
+        if estimator == "pgdb":
+            _lib.check(lib.fbx_pgdb_process_dev(design.handle, B, d_e.ptr, d_c.ptr,
+                                                int(bool(estimator_kw.get("trace_preserving", True))),
+                                                _lib.MODE_FIXED if mode == "fixed" else _lib.MODE_CONVERGE,
+                                                int(estimator_kw.get("max_iters", 0)), d_choi.ptr, None, None, None, None, None))
+        else:
+            _lib.check(lib.fbx_linv_process_dev(design.handle, B, d_e.ptr, d_choi.ptr))
+        _lib.check(lib.fbx_convert_dev(_lib.REP_CHOI, _lib.REP_PAULI_LIOUVILLE, n, B, d_choi.ptr, 0, d_ptm.ptr))
+        _lib.check(lib.fbx_process_fidelity_dev(n, B, d_truth_c.ptr, d_ptm.ptr, None, d_f.ptr))
+        _lib.synchronize()
+        status = d_status.to_array(np.int32, (B,))
+        choi = d_choi.to_array(np.complex128, (B, D, D))
+        fid = d_f.to_array(np.float64, (B,))
+    finally:
+        for buf in bufs:
+            buf.free()
+    bad = np.flatnonzero(status)
+    if bad.size:
+        raise ValueError(f"simulate_and_estimate_process_batch: item {int(bad[0])} cannot be simulated: a truth entry that is not "
+                         f"finite or a readout_flip value outside [0, 1] ({bad.size} such item(s) in the batch)")
+    return choi, fid

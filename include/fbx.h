@@ -531,6 +531,53 @@ int fbx_sample_bitstrings_dev(int n_qubits, int64_t B, int64_t n_shots, const do
                               const double* d_readout_flip, uint64_t seed, int64_t first_item, uint8_t* d_bits_out,
                               int32_t* d_status_out);
 
+/* ---------------------------------------------------------------- simulated tomography experiments: truth to noisy expectations
+ * The acquisition half of a tomography experiment (what do_tomography / estimate_observables, observable_estimation.py:856-920,
+ * get from a QVM): B true channels or states measured with the settings of `design`, n_shots shots per setting, as the
+ * (expectations, total_counts) every estimator here reads.
+ *
+ * truth: for a process design (1..3 qubits) the Pauli transfer matrices [B][D][D], real, row-major, in the reference's
+ * pauli-liouville convention and Pauli order (what fbx_convert(..., FBX_REP_PAULI_LIOUVILLE) writes); for a state design (1..5
+ * qubits) the density matrices [B][d][d] complex128 (interleaved re, im), as the other state entry points take them.
+ * readout_flip [B][n][2] or NULL (= no flips), with the meaning of fbx_sample_bitstrings: [j][0] = P(read 1 | drawn 0), [j][1] =
+ * P(read 0 | drawn 1) of qubit j, independent per bit.
+ *
+ * Outputs: expect_out, counts_out, std_err_out, exact_out [B][m] in the CALLER's setting order (the order of
+ * fbx_design_create), status_out [B].  Each may be NULL, not all of them.  n_shots == 0 is the exact-expectations-only mode: it
+ * is allowed only when expect_out, counts_out and std_err_out are NULL.
+ *
+ * THE MEAN.  Setting k of item b has the input state s_k, the Pauli P_k, the coefficient c_k and the set S of qubits on which
+ * P_k is not the identity.  Without flips mu = tr[P_k Lambda_b(rho_{s_k})] (process) or tr[P_k rho_b] (state).  With flips, a_j =
+ * f1_j - f0_j and b_j = 1 - f0_j - f1_j (f0 = [j][0], f1 = [j][1]), the mean of the MEASURED +-1 product is
+ *     mu = sum_{T subset of S} prod_{j in S \ T} a_j prod_{j in T} b_j tr[P_T .],
+ * P_T = P_k with the factors outside T replaced by I and the term of the empty T equal to 1: exact for independent per-bit flips
+ * (E[z' | z] = a + b z), at most 2^w terms for a Pauli of weight w <= 5.  An all-identity observable has mu = 1 and uses no
+ * draws.  exact_out = c_k mu.
+ *
+ * THE STREAM (part of the contract: it is what a host check restates).  q = 0.5 mu + 0.5 clamped to [0, 1] (an unphysical truth
+ * is clamped, not refused); t = floor(q 2^32), a 64-bit integer in [0, 2^32].  Shot s of setting k (the caller's index) of the
+ * global item g = first_item + b reads word s & 3 of the Philox4x32-10 block with counter (g low, g high, k, s >> 2) and key
+ * (seed low ^ 0x544F4D4F, seed high); the tag keeps a caller who reuses a seed away from the stream of fbx_sample_bitstrings.
+ * The shot counts +1 iff word < t; k_plus = the number of such shots, k_minus = N - k_plus (N = n_shots), and
+ *     expect_out  = c_k * ((double) (k_plus - k_minus) / (double) N)
+ *     counts_out  = N
+ *     std_err_out = |c_k| * sqrt((double) (4 k_plus k_minus) / N) / N
+ * (the reference's sqrt(np.var(vals) / N), observable_estimation.py:849-851, written so that nothing cancels).  A value depends
+ * on (seed, g, k), mu and N only: not on B, the launch shape or which lanes counted which shots -- a call of B' items from
+ * first_item + i repeats items i .. i + B' - 1.
+ *
+ * n_shots >= 2^32, a negative size, first_item < 0, NULL truth, every output NULL, n_shots == 0 with a sampled output requested:
+ * FBX_ERR_BAD_ARG before any buffer is touched; a NULL design or one of another device likewise.  B == 0: nothing is done.
+ * A poisoned item -- a non-finite truth entry, a flip probability outside [0, 1] or NaN -- gets status 1, NaN in expect_out /
+ * std_err_out / exact_out and N in counts_out; its neighbours are untouched.
+ * The _dev form enqueues on the calling thread's stream and does not synchronise. */
+int fbx_tomo_simulate(const fbx_design* design, int64_t B, const double* truth, int64_t n_shots, const double* readout_flip,
+                      uint64_t seed, int64_t first_item, double* expect_out, double* counts_out, double* std_err_out,
+                      double* exact_out, int32_t* status_out);
+int fbx_tomo_simulate_dev(const fbx_design* design, int64_t B, const double* d_truth, int64_t n_shots, const double* d_readout_flip,
+                          uint64_t seed, int64_t first_item, double* d_expect_out, double* d_counts_out, double* d_std_err_out,
+                          double* d_exact_out, int32_t* d_status_out);
+
 /* ---------------------------------------------------------------- curve fits (analysis/fitting.py, randomized_benchmarking.py,
  * qubit_spectroscopy.py)
  * fbx_curve_fit: B independent weighted non-linear least-squares fits, one per GPU lane, of the four models of

@@ -5,7 +5,7 @@
 // while a setting's record is short (the usual 1000 shots x 2 qubits = 2 KB: four settings in flight per
 // workgroup and no barrier -- a workgroup per setting ran at 1.0 TB/s there), one 256-thread workgroup per
 // setting for long records.  HBM-bound integer work: n_qubits bytes per shot in, 16 bytes per setting out.
-#include "fbx_common.hpp"
+#include "fbx_sim_shared.hpp"      // dfe_item, shared with fbx_dfe.hip
 
 namespace fbx {
 
@@ -311,28 +311,9 @@ shots_kernel(int n, long long n_settings, long long n_shots, const uint8_t* __re
 __global__ void __launch_bounds__(64)
 dfe_kernel(int n_qubits, int process, long long B, long long m, const double* __restrict__ expect,
            const double* __restrict__ std_err, double* __restrict__ mean_out, double* __restrict__ err_out) {
-    const int lane = threadIdx.x;
     const double d = (double)(1 << n_qubits);
-    for (long long item = blockIdx.x; item < B; item += gridDim.x) {
-        const double* e = expect + item * m;
-        const double* se = std_err + item * m;
-        double s = 0.0, v = 0.0;
-        for (long long k = lane; k < m; k += 64) { s += e[k]; const double x = se[k]; v += x * x; }
-        s = wave_sum(s); v = wave_sum(v);
-        if (lane == 0) {
-            const double mean = s / (double)m;
-            const double var_mean = v / ((double)m * (double)m);
-            if (!process) {
-                mean_out[item] = (d - 1.0) / d * mean + 1.0 / d;
-                err_out[item] = sqrt((d - 1.0) * (d - 1.0) / (d * d) * var_mean);
-            } else {
-                const double d2 = d * d;
-                const double p_mean = (d2 - 1.0) / d2 * mean + 1.0 / d2;
-                mean_out[item] = (d2 * p_mean + d) / (d2 + d);
-                err_out[item] = sqrt(d2 / ((d + 1.0) * (d + 1.0)) * (d2 - 1.0) * (d2 - 1.0) / (d2 * d2) * var_mean);
-            }
-        }
-    }
+    for (long long item = blockIdx.x; item < B; item += gridDim.x)
+        dfe_item(d, process, m, expect + item * m, std_err + item * m, (int)threadIdx.x, mean_out + item, err_out + item);
 }
 
 

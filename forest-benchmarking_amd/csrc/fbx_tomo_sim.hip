@@ -13,14 +13,11 @@
 // shots (the chip is full without cutting a setting); below, a WAVEFRONT takes a unit, lane l counts the Philox blocks l, l + 64,
 // ... and the 64 partial counts are summed (integers, exactly, in double).  A value depends on (seed, item id, setting, mean, shots)
 // only: both splits evaluate the mean with the same code in the same order and count the same words.
-#include "fbx_common.hpp"
+#include "fbx_sim_shared.hpp"      // tomo_count and the unit threshold, shared with fbx_dfe.hip
 
 namespace fbx {
 
 constexpr int TOMO_THREADS = 256;
-#ifndef FBX_TOMO_LANE_MIN_UNITS
-#define FBX_TOMO_LANE_MIN_UNITS 131072           // 256 CUs x 4 SIMDs x 64 lanes x 2 wavefronts: a lane per setting fills the chip
-#endif
 constexpr uint32_t TOMO_KEY_TAG = 0x544F4D4Fu;   // "TOMO": keeps the stream apart from fbx_sample_bitstrings under one seed
 
 __device__ __forceinline__ bool tomo_bad_probability(double v) { return !(v >= 0.0 && v <= 1.0); }      // NaN included
@@ -103,25 +100,6 @@ __device__ double tomo_mean(const DesignDev& des, const double* __restrict__ tru
         if (T == 0) break;
     }
     return mu;
-}
-
-// How many of the Philox blocks first, first + step, ... of the setting (g, k) hold words below t (< 2^32); the last block of a
-// shot count that is no multiple of 4 counts its first n_shots & 3 words only.
-__device__ __forceinline__ uint32_t tomo_count(uint32_t t, uint32_t g0, uint32_t g1, uint32_t k, uint32_t k0, uint32_t k1,
-                                               uint32_t first, uint32_t step, uint32_t n_shots) {
-    const uint32_t full = n_shots >> 2, tail = n_shots & 3u;
-    uint32_t cnt = 0;
-    for (uint32_t j = first; j < full; j += step) {
-        uint32_t c[4] = {g0, g1, k, j};
-        philox4x32_10(c, k0, k1);
-        cnt += (uint32_t)(c[0] < t) + (uint32_t)(c[1] < t) + (uint32_t)(c[2] < t) + (uint32_t)(c[3] < t);
-    }
-    if (tail && full % step == first) {
-        uint32_t c[4] = {g0, g1, k, full};
-        philox4x32_10(c, k0, k1);
-        cnt += (uint32_t)(c[0] < t) + (uint32_t)(tail > 1 && c[1] < t) + (uint32_t)(tail > 2 && c[2] < t);
-    }
-    return cnt;
 }
 
 // unit u = (item u / m, grouped setting u % m); LANE: a lane per unit, else a wavefront per unit

@@ -28,6 +28,8 @@ HIST_MAX_SHOTS = 2 ** 31 - 1
 HIST_WAVE_BYTES = 16384         # records below this many bytes get a wavefront each (csrc/fbx_histogram.hip)
 CLIFFORD_NONE = 0xFFFFFFFF      # no element: "no interleaved gate" / "no such index" (include/fbx.h)
 RB_MAX_NOISE_PTMS = 16
+DFE_MAX_CLASSES = 16
+DFE_NOISELESS = 255             # noise class of a gate without noise (include/fbx.h)
 
 
 class FbxError(RuntimeError):
@@ -49,6 +51,8 @@ _ip = C.POINTER(C.c_int32)
 _u8p = C.POINTER(C.c_uint8)
 _u32p = C.POINTER(C.c_uint32)
 _i64p = C.POINTER(C.c_int64)
+_u64p = C.POINTER(C.c_uint64)
+_i8p = C.POINTER(C.c_int8)
 _vp = C.c_void_p
 _i64 = C.c_int64
 
@@ -185,6 +189,20 @@ PROTOTYPES = {
     "fbx_rb_sequences_dev": [C.c_int, _i64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp],
     "fbx_rb_simulate": [C.c_int, _i64, _i64p, _u32p, _u8p, C.c_int, _dp, _dp, _dp],
     "fbx_rb_simulate_dev": [C.c_int, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
+    "fbx_clifford_conjugate": [C.c_int, _i64, _u32p, C.c_int, _i64, _u64p, _u64p, _u8p, _u64p, _u64p, _u8p],
+    "fbx_clifford_conjugate_dev": [C.c_int, _i64, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "fbx_dfe_settings": [C.c_int, C.c_int, _i64, C.c_uint64, _i64, _u32p, _i64, _u64p, _u64p, _u64p, _u64p, _u64p, _u8p],
+    "fbx_dfe_settings_dev": [C.c_int, C.c_int, _i64, C.c_uint64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "fbx_dfe_propagate": [C.c_int, _i64, _u32p, _u8p, C.c_int, _i64, _u64p, _u64p, _u64p, _u64p, _u64p, _u8p, _i8p, _u32p],
+    "fbx_dfe_propagate_dev": [C.c_int, _i64, _vp, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "fbx_dfe_simulate": [C.c_int, _i64, C.c_int, _i8p, _u32p, _u64p, _u64p, _u8p, _i64, _dp, _dp, C.c_int, _i64, C.c_uint64, _i64,
+                         _dp, _dp, _dp, _dp, _ip],
+    "fbx_dfe_simulate_dev": [C.c_int, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, C.c_int, _i64, C.c_uint64, _i64,
+                             _vp, _vp, _vp, _vp, _vp],
+    "fbx_dfe_simulate_fidelity": [C.c_int, _i64, C.c_int, _i8p, _u32p, _u64p, _u64p, _u8p, _i64, _dp, _dp, _i64, C.c_uint64, _i64,
+                                  C.c_int, C.c_int, _dp, _dp, _ip],
+    "fbx_dfe_simulate_fidelity_dev": [C.c_int, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, C.c_uint64, _i64,
+                                      C.c_int, C.c_int, _vp, _vp, _vp],
 }
 
 
@@ -330,6 +348,11 @@ def dptr(a):
 
 def iptr(a):
     return None if a is None else a.ctypes.data_as(_ip)
+
+
+def ptr(a, ctype):
+    """Pointer to a contiguous array as ``POINTER(ctype)`` (None stays None)."""
+    return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
 
 
 def eigh_batch(a, eigenvectors=True):

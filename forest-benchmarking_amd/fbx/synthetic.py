@@ -300,13 +300,25 @@ def _philox4x32_10(c0, c1, c2, c3, k0, k1):
     return c0, c1, c2, c3
 
 
+DFE_KEY_TAG = 0x44464530                 # the shots of fbx_dfe_simulate
+DFE_CALIBRATION_KEY_TAG = 0x44464543     # ... of its calibration mode
+
+
 def restate_tomography_counts(exact, coefs, shots, seed, first_item=0):
-    """The counts ``tomography.simulate_*_tomography_batch`` draws, restated on the host from the contract of
-    ``fbx_tomo_simulate`` (include/fbx.h): ``exact [B, m]`` = coefficient times the mean of the measured product (the
+    """``restate_dfe_counts`` under the key tag of ``fbx_tomo_simulate``: the counts ``tomography.simulate_*_tomography_batch``
+    draws, restated on the host (the stream is described there)."""
+    return restate_dfe_counts(exact, coefs, shots, seed, first_item, key_tag=TOMO_KEY_TAG)
+
+
+def restate_dfe_counts(exact, coefs, shots, seed, first_item=0, key_tag=DFE_KEY_TAG):
+    """The counts a simulated experiment draws, restated on the host from the contract of ``fbx_tomo_simulate`` and
+    ``fbx_dfe_simulate`` (include/fbx.h): ``exact [B, m]`` = coefficient times the mean of the measured product (the
     ``return_exact`` output), ``coefs [m]`` the non-zero observable coefficients, ``shots`` = N >= 1, ``seed`` the 64-bit key and
     item b the global item ``first_item + b``.  Per setting: mu = exact / coef, q = 0.5 mu + 0.5 clamped to [0, 1], t =
     floor(q 2^32); shot s counts +1 iff word ``s & 3`` of the Philox4x32-10 block with counter (g low, g high, k, s >> 2) and
-    key (seed low ^ 0x544F4D4F, seed high) is below t.  Returns ``(expectations, total_counts, std_errs, k_plus)``, all [B, m],
+    key (seed low ^ key_tag, seed high) is below t: ``key_tag`` is 0x544F4D4F for ``fbx_tomo_simulate``
+    (``restate_tomography_counts``), 0x44464530 for ``fbx_dfe_simulate`` and 0x44464543 for its calibration mode, where
+    ``coefs`` are the signs c_k.  Returns ``(expectations, total_counts, std_errs, k_plus)``, all [B, m],
     ``k_plus`` int64: expectation = coef (k+ - k-) / N, std_err = |coef| sqrt(4 k+ k- / N) / N."""
     exact = np.atleast_2d(np.asarray(exact, dtype=np.float64))
     B, m = exact.shape
@@ -317,7 +329,7 @@ def restate_tomography_counts(exact, coefs, shots, seed, first_item=0):
     mu = exact / coefs[None, :]
     q = np.clip(0.5 * mu + 0.5, 0.0, 1.0)
     t = np.floor(q * 2.0 ** 32).astype(np.uint64)                       # in [0, 2^32]
-    k0, k1 = (seed & 0xFFFFFFFF) ^ TOMO_KEY_TAG, seed >> 32
+    k0, k1 = (seed & 0xFFFFFFFF) ^ (int(key_tag) & 0xFFFFFFFF), seed >> 32
     n_blocks = (N + 3) // 4
     blocks = np.arange(n_blocks, dtype=np.uint64)
     valid = [4 * blocks + np.uint64(w) < np.uint64(N) for w in range(4)]  # the last block of a count that is no multiple of 4

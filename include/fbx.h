@@ -823,6 +823,154 @@ int fbx_rb_simulate(int n_qubits, int64_t B, const int64_t* offsets, const uint3
 int fbx_rb_simulate_dev(int n_qubits, int64_t B, const int64_t* d_offsets, const uint32_t* d_elems, const uint8_t* d_noise_ids, int G,
                         const double* d_noise_ptms, const double* d_prep, double* d_out);
 
+/* ---------------------------------------------------------------- Clifford circuits and direct fidelity estimation, 1..64 qubits
+ * The experiment generators of direct_fidelity_estimation.py:15-182 and the noisy expectations of their settings for a Clifford
+ * circuit with Pauli noise, exact in the Heisenberg picture: the observable walks backwards through the circuit as a signed Pauli
+ * and picks up a factor 1 - p at every noisy gate it touches.  n_qubits outside 1..64: FBX_ERR_BAD_ARG.
+ *
+ * Pauli.  (x, z, sign): two uint64 masks and a uint8.  Bit q of a mask belongs to qubit q, which is index q of a label string (as
+ * in str_to_pauli_term, utils.py:127-143).  Per qubit (x, z) = 00 I, 10 X, 11 Y, 01 Z, Y being the Hermitian Y; the operator is
+ * (-1)^sign times the tensor product.  Bits from n_qubits on are ignored on the way in and zero on the way out; only bit 0 of a
+ * sign byte is read.
+ *
+ * Gate word.  uint32: opcode in bits 0..7, q0 in bits 8..15, q1 in bits 16..23, the rest zero (q1 is zero for a one-qubit gate).
+ * The one-qubit gates act on q0; CNOT has q0 as control and q1 as target; CZ and SWAP need q0 != q1.  A circuit is gates[G],
+ * applied in index order, G >= 0.  fbx/clifford_circuit.py is the host mirror and encodes the (name, qubits) tuples that
+ * fbx.clifford.to_gates emits. */
+#define FBX_GATE_H 0
+#define FBX_GATE_S 1
+#define FBX_GATE_SDG 2
+#define FBX_GATE_X 3
+#define FBX_GATE_Y 4
+#define FBX_GATE_Z 5
+#define FBX_GATE_RX_PLUS 6   /* RX(pi/2)  */
+#define FBX_GATE_RX_MINUS 7  /* RX(-pi/2) */
+#define FBX_GATE_RY_PLUS 8   /* RY(pi/2)  */
+#define FBX_GATE_RY_MINUS 9  /* RY(-pi/2) */
+#define FBX_GATE_RZ_PLUS 10  /* RZ(pi/2)  */
+#define FBX_GATE_RZ_MINUS 11 /* RZ(-pi/2) */
+#define FBX_GATE_CNOT 12
+#define FBX_GATE_CZ 13
+#define FBX_GATE_SWAP 14
+#define FBX_DFE_NOISELESS 255 /* noise class of a gate without noise */
+/* Conjugation U P U^+ by one gate; s is the sign flip, evaluated on the values BEFORE the update (a = q0, b = q1):
+ *     H                  s = x&z               swap x, z
+ *     S,   RZ(pi/2)      s = x&z               z ^= x
+ *     SDG, RZ(-pi/2)     s = x&~z              z ^= x
+ *     X                  s = z
+ *     Y                  s = x^z
+ *     Z                  s = x
+ *     RX(pi/2)           s = z&~x              x ^= z
+ *     RX(-pi/2)          s = z&x               x ^= z
+ *     RY(pi/2)           s = x&~z              swap x, z
+ *     RY(-pi/2)          s = z&~x              swap x, z
+ *     CNOT(a, b)         s = xa&zb&~(xb^za)    xb ^= xa; za ^= zb
+ *     CZ(a, b)           s = xa&xb&(za^zb)     za ^= xb; zb ^= xa
+ *     SWAP                                     swap both pairs
+ * The inverse direction U^+ P U walks the list backwards with every gate's inverse (S <-> SDG, RX / RY / RZ(+) <-> (-), the rest
+ * are their own inverses).
+ *
+ * GATE WORDS ARE VALIDATED BY WHOEVER CAN READ THEM.  The host-pointer forms refuse (FBX_ERR_BAD_ARG, before any buffer is
+ * touched) an unknown opcode, a qubit index >= n_qubits, q0 == q1 on a two-qubit gate and a word with other bits set.  The _dev
+ * forms cannot read their words and take them as validated by the caller (run them through the host form or through
+ * clifford_circuit.encode_gates once).  A word that was not is harmless but meaningless: qubit indices are reduced mod 64, an
+ * unknown opcode does nothing, an unknown noise class is not counted -- no access depends on a word's content.
+ *
+ * fbx_clifford_conjugate: M Paulis, one per lane, through the circuit: inverse == 0 gives U P U^+, otherwise U^+ P U.  It stands in
+ * for BenchmarkConnection.apply_clifford_to_pauli.  M == 0: nothing is done. */
+int fbx_clifford_conjugate(int n_qubits, int64_t G, const uint32_t* gates, int inverse, int64_t M, const uint64_t* x_in,
+                           const uint64_t* z_in, const uint8_t* sign_in, uint64_t* x_out, uint64_t* z_out, uint8_t* sign_out);
+int fbx_clifford_conjugate_dev(int n_qubits, int64_t G, const uint32_t* d_gates, int inverse, int64_t M, const uint64_t* d_x_in,
+                               const uint64_t* d_z_in, const uint8_t* d_sign_in, uint64_t* d_x_out, uint64_t* d_z_out,
+                               uint8_t* d_sign_out);
+
+/* Setting.  in_x, in_z, in_minus, obs_x, obs_z (uint64) and obs_sign (uint8), one entry per setting.  The in-state is a product of
+ * one-qubit Pauli eigenstates: (in_x, in_z) bit q is the label of qubit q (X, Y or Z, never I), in_minus bit q is set for the -1
+ * eigenstate; |0..0> is Z everywhere with in_minus = 0.  The observable is (-1)^obs_sign times the Pauli (obs_x, obs_z).
+ *
+ * fbx_dfe_settings writes the m settings of one of the reference's four generators for the circuit, conjugation included.
+ * n_terms == 0 is exhaustive (m >= 2^31 is refused):
+ *   FBX_KIND_STATE    m = 2^n - 1.  Setting k is string k + 1 (counting from 0: the all-identity string is skipped) of
+ *                     itertools.product('IZ', repeat=n), qubit 0 the most significant digit; the in-state is |0..0>, the observable
+ *                     U Z-string U^+ (direct_fidelity_estimation.py:91-94).
+ *   FBX_KIND_PROCESS  m = (4^n - 1) 2^n.  Setting k = (j - 1) 2^n + e has string j of product('IXYZ', repeat=n) as its Pauli P; the
+ *                     in-state labels are P with I replaced by Z, the eigenvalue bits are e (qubit 0 most significant), and the
+ *                     observable is U P U^+ times (-1)^(minus bits on the qubits where P is not I) (:46-66).
+ * n_terms > 0 is Monte Carlo with m = n_terms (:117-129, :153-182), from a documented stream in place of np.random.  With
+ * valid = the mask of the n low bits: attempt a = 0, 1, ... of setting k reads the words w0..w3 of the Philox4x32-10 block with
+ * counter (k low, k high, a, 0) and key (seed low ^ 0x44464553, seed high).  State: the Z mask is (w0 | w1 << 32) & valid.
+ * Process: x = (w0 | w1 << 32) & valid, z = (w2 | w3 << 32) & valid.  The first attempt that is not the identity is kept (the
+ * reference's resampling loop); the process kind then reads the block (k low, k high, a, 1) of that attempt for the eigenvalue
+ * bits (w0 | w1 << 32) & valid.  After 256 rejected attempts z = valid (and x = valid for a process) is taken with a = 256, so the
+ * loop is finite.  A setting depends on (seed, k) only.  A wrong m, a negative size, an unknown kind: FBX_ERR_BAD_ARG. */
+int fbx_dfe_settings(int n_qubits, int kind, int64_t n_terms, uint64_t seed, int64_t G, const uint32_t* gates, int64_t m,
+                     uint64_t* in_x, uint64_t* in_z, uint64_t* in_minus, uint64_t* obs_x, uint64_t* obs_z, uint8_t* obs_sign);
+int fbx_dfe_settings_dev(int n_qubits, int kind, int64_t n_terms, uint64_t seed, int64_t G, const uint32_t* d_gates, int64_t m,
+                         uint64_t* d_in_x, uint64_t* d_in_z, uint64_t* d_in_minus, uint64_t* d_obs_x, uint64_t* d_obs_z,
+                         uint8_t* d_obs_sign);
+
+/* fbx_dfe_propagate: one lane per setting walks the UNSIGNED observable (obs_x, obs_z) backwards through the circuit (obs_sign is
+ * not read and may be NULL).  noise_class[G] is uint8: a class < K, 1 <= K <= 16, or FBX_DFE_NOISELESS; NULL means every gate is
+ * class 0.  touches_out [m][K] uint32: touches[k][c] = the number of gates of class c on whose qubits the walking Pauli is not the
+ * identity.  A gate maps Paulis that are the identity on its qubits to themselves and no others, so whether this is looked at
+ * before or after passing the gate makes no difference.  sigma_out [m] int8 = the ideal expectation of the unsigned observable in
+ * the in-state: with O_0 the Pauli that arrives at the start of the circuit, 0 if O_0 differs from the in-state's label on any
+ * qubit where O_0 is not I, otherwise (-1)^(sign of O_0 + popcount(in_minus & support of O_0)).
+ * The host form also refuses a class that is neither below K nor 255 and an in-state label of I. */
+int fbx_dfe_propagate(int n_qubits, int64_t G, const uint32_t* gates, const uint8_t* noise_class, int K, int64_t m,
+                      const uint64_t* in_x, const uint64_t* in_z, const uint64_t* in_minus, const uint64_t* obs_x,
+                      const uint64_t* obs_z, const uint8_t* obs_sign, int8_t* sigma_out, uint32_t* touches_out);
+int fbx_dfe_propagate_dev(int n_qubits, int64_t G, const uint32_t* d_gates, const uint8_t* d_noise_class, int K, int64_t m,
+                          const uint64_t* d_in_x, const uint64_t* d_in_z, const uint64_t* d_in_minus, const uint64_t* d_obs_x,
+                          const uint64_t* d_obs_z, const uint8_t* d_obs_sign, int8_t* d_sigma_out, uint32_t* d_touches_out);
+
+/* fbx_dfe_simulate: B items share the m settings (sigma, touches of fbx_dfe_propagate and the observables) and differ in noise.
+ * class_error [B][K]: the depolarizing probability of every gate of class c; readout_flip [B][n]: a symmetric flip probability per
+ * qubit.  Either may be NULL (= 0).  Outputs [B][m] and status_out [B] as those of fbx_tomo_simulate; each may be NULL, not all.
+ *
+ * THE MEAN.  mu = sigma_k prod_c (1 - p_{b,c})^touches[k][c] prod_{q in S_k} (1 - 2 f_{b,q}), S_k = the support obs_x | obs_z.
+ * A depolarizing channel rho -> (1 - p) rho + p tr_g(rho) (x) I / d_g on the qubits of gate g, applied after the gate, scales
+ * every Pauli that is not the identity there by 1 - p and leaves the others alone; symmetric flips scale a product of bits by
+ * 1 - 2 f each.  Only symmetric flips are modelled: the reference's default for DFE is exhaustive symmetrization, which makes the
+ * effective readout error symmetric.  The powers are formed by repeated squaring and the factors multiplied in ascending class
+ * and qubit order: at most one rounding per factor.  calibration != 0: mu is the readout product alone and c_k = 1 -- the
+ * observable with coefficient 1 measured on its own +1 eigenstate, what calibrate_observable_estimates acquires
+ * (observable_estimation.py:1005-1020) -- under a key tag of its own.  exact_out = c_k mu, c_k = (-1)^obs_sign.
+ *
+ * THE STREAM and the three sampled outputs are, word for word, those of fbx_tomo_simulate -- t = floor((0.5 mu + 0.5) 2^32) after
+ * clamping, shot s of setting k of the global item g = first_item + b reads word s & 3 of the block with counter (g low, g high, k,
+ * s >> 2), expect_out = c_k (k_plus - k_minus) / N, counts_out = N, std_err_out = sqrt(4 k_plus k_minus / N) / N, n_shots == 0 the
+ * exact-only mode -- with the key (seed low ^ 0x44464530, seed high), or (seed low ^ 0x44464543, seed high) when calibrating.
+ * From B m = 131072 units on a lane takes a unit, below a wavefront does; both give the same bits.
+ * A poisoned item -- a class error or a flip outside [0, 1], or NaN -- gets status 1, NaN in expect_out / std_err_out / exact_out
+ * and N in counts_out; its neighbours are untouched.  n_shots >= 2^32, m >= 2^32, a negative size, first_item < 0, K outside
+ * 1..16, a NULL settings buffer, every output NULL, n_shots == 0 with a sampled output requested: FBX_ERR_BAD_ARG before any
+ * buffer is touched.  B == 0 or m == 0: nothing is done.  The _dev forms enqueue on the calling thread's stream. */
+int fbx_dfe_simulate(int n_qubits, int64_t m, int K, const int8_t* sigma, const uint32_t* touches, const uint64_t* obs_x,
+                     const uint64_t* obs_z, const uint8_t* obs_sign, int64_t B, const double* class_error, const double* readout_flip,
+                     int calibration, int64_t n_shots, uint64_t seed, int64_t first_item, double* expect_out, double* counts_out,
+                     double* std_err_out, double* exact_out, int32_t* status_out);
+int fbx_dfe_simulate_dev(int n_qubits, int64_t m, int K, const int8_t* d_sigma, const uint32_t* d_touches, const uint64_t* d_obs_x,
+                         const uint64_t* d_obs_z, const uint8_t* d_obs_sign, int64_t B, const double* d_class_error,
+                         const double* d_readout_flip, int calibration, int64_t n_shots, uint64_t seed, int64_t first_item,
+                         double* d_expect_out, double* d_counts_out, double* d_std_err_out, double* d_exact_out,
+                         int32_t* d_status_out);
+
+/* The resident chain: the simulation above (expectations and standard errors), with calibrate != 0 a second one in calibration
+ * mode whose (expectation, standard error^2) of item b and setting k are the calibration of that result
+ * (fbx_calibrate_expectations' arithmetic), then estimate_dfe (direct_fidelity_estimation.py:291-307) with d = 2^n as a double,
+ * for any n up to 64: fidelity_out [B], err_out [B], status_out [B] or NULL.  Nothing of size [B][m] leaves the device.  m >= 1
+ * and n_shots >= 1 are required; a poisoned item comes out as NaN. */
+int fbx_dfe_simulate_fidelity(int n_qubits, int64_t m, int K, const int8_t* sigma, const uint32_t* touches, const uint64_t* obs_x,
+                              const uint64_t* obs_z, const uint8_t* obs_sign, int64_t B, const double* class_error,
+                              const double* readout_flip, int64_t n_shots, uint64_t seed, int64_t first_item, int kind, int calibrate,
+                              double* fidelity_out, double* err_out, int32_t* status_out);
+int fbx_dfe_simulate_fidelity_dev(int n_qubits, int64_t m, int K, const int8_t* d_sigma, const uint32_t* d_touches,
+                                  const uint64_t* d_obs_x, const uint64_t* d_obs_z, const uint8_t* d_obs_sign, int64_t B,
+                                  const double* d_class_error, const double* d_readout_flip, int64_t n_shots, uint64_t seed,
+                                  int64_t first_item, int kind, int calibrate, double* d_fidelity_out, double* d_err_out,
+                                  int32_t* d_status_out);
+
 /* out[b] = op(a[b]) diag(scale[b]) op(b[b]) for stacks of N x N complex matrices, N in 1..1024: op = the matrix itself
  * (conj_t = 0) or its conjugate transpose (conj_t = 1); scale is [B][N] real or NULL.  The products around fbx_eigh:
  * V f(lambda) V^H (sqrtm_psd, calculational.py:77-91), sqrt(rho) sigma sqrt(rho) (fidelity, distance_measures.py:64-84). */

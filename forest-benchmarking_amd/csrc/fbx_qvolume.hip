@@ -25,6 +25,7 @@
 //
 // fbx_qv_count_heavy: a byte-stream reduction in the style of fbx_shots.hip (16-byte loads, runs of 16 shots per lane).
 #include "fbx_common.hpp"
+#include "fbx_qv_gate.hpp"
 
 namespace fbx {
 
@@ -35,21 +36,9 @@ struct QvScratch {
     double red[16];
 };
 
-__device__ __forceinline__ int qv_slot(int i) { return i ^ (((i >> 3) & 1) * 7) ^ ((i >> 1) & 8) ^ ((i >> 5) & 3); }
-
 template <bool WAVE>
 __device__ __forceinline__ void qv_sync() {
     if constexpr (WAVE) FBX_WAVE_SYNC(); else __syncthreads();
-}
-
-// inclusive prefix sum over the 64 lanes of a wavefront (all lanes active)
-__device__ __forceinline__ unsigned wave_scan_u32(unsigned v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned o = (unsigned)__shfl_up((int)v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
 }
 
 // the k-th smallest (k from 0) of the N bit patterns in S[.].re, all of them between mn and mx
@@ -106,33 +95,7 @@ __device__ void qv_circuit(int n, long long item, int L, const uint8_t* __restri
         const int q0 = uniform((int)pr[0]), q1 = uniform((int)pr[1]);
         if (q0 >= n || q1 >= n || q0 == q1) { bad_pair = 1; continue; }               // wave-uniform; never index outside the state
         const int p0 = n - 1 - q0, p1 = n - 1 - q1;                                   // qubit 0 = most significant bit
-        const int lo = p0 < p1 ? p0 : p1, hi = p0 < p1 ? p1 : p0;
-        const int m0 = 1 << p0, m1 = 1 << p1, lomask = (1 << lo) - 1, himask = (1 << hi) - 1;
-        const int t0 = qv_slot(m0), t1 = qv_slot(m1);                                 // the swizzle is linear
-        const double* __restrict__ U = gates + ((size_t)item * L + l) * 32;
-        double ur[16], ui[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { ur[e] = U[2 * e]; ui[e] = U[2 * e + 1]; }
-        for (int g = tid; g < groups; g += nth) {
-            int base = ((g & ~lomask) << 1) | (g & lomask);
-            base = ((base & ~himask) << 1) | (base & himask);
-            const int s0 = qv_slot(base), s1 = s0 ^ t1, s2 = s0 ^ t0, s3 = s2 ^ t1;
-            const cplx a0 = S[s0], a1 = S[s1], a2 = S[s2], a3 = S[s3];                 // (bit of q0, bit of q1) = 00, 01, 10, 11
-            cplx o[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                double re = ur[4 * r] * a0.re - ui[4 * r] * a0.im;
-                double im = ur[4 * r] * a0.im + ui[4 * r] * a0.re;
-                re += ur[4 * r + 1] * a1.re - ui[4 * r + 1] * a1.im;
-                im += ur[4 * r + 1] * a1.im + ui[4 * r + 1] * a1.re;
-                re += ur[4 * r + 2] * a2.re - ui[4 * r + 2] * a2.im;
-                im += ur[4 * r + 2] * a2.im + ui[4 * r + 2] * a2.re;
-                re += ur[4 * r + 3] * a3.re - ui[4 * r + 3] * a3.im;
-                im += ur[4 * r + 3] * a3.im + ui[4 * r + 3] * a3.re;
-                o[r] = cplx{re, im};
-            }
-            S[s0] = o[0]; S[s1] = o[1]; S[s2] = o[2]; S[s3] = o[3];
-        }
+        qv_apply_gate(S, groups, p0, p1, gates + ((size_t)item * L + l) * 32, tid, nth);               // fbx_qv_gate.hpp
         qv_sync<WAVE>();
     }
     // amplitudes -> probabilities (in the real part of the slot), smallest / largest pattern, non-finite check

@@ -158,6 +158,11 @@ PROTOTYPES = {
     "fbx_qv_heavy_outputs_dev": [C.c_int, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fbx_qv_count_heavy": [C.c_int, _i64, _i64, _u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
     "fbx_qv_count_heavy_dev": [C.c_int, _i64, _i64, _vp, _vp, _vp],
+    "fbx_qv_heavy_outputs_wide": [C.c_int, _i64, C.c_int, _u8p, _dp, C.c_int, _dp, _dp, C.POINTER(C.c_uint64), _dp, _ip],
+    "fbx_qv_heavy_outputs_wide_dev": [C.c_int, _i64, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp],
+    "fbx_qv_count_heavy_wide": [C.c_int, _i64, _i64, _u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
+    "fbx_qv_count_heavy_wide_dev": [C.c_int, _i64, _i64, _vp, _vp, _vp],
+    "fbx_qv_wide_plan": [C.c_int, _i64, C.c_int, _u8p, C.c_int, _ip, _ip, _u32p],
     "fbx_sample_bitstrings": [C.c_int, _i64, _i64, _dp, _dp, _dp, C.c_uint64, _i64, _u8p, _ip],
     "fbx_sample_bitstrings_dev": [C.c_int, _i64, _i64, _vp, _vp, _vp, C.c_uint64, _i64, _vp, _vp],
     "fbx_tomo_simulate": [_vp, _i64, _dp, _i64, _dp, C.c_uint64, _i64, _dp, _dp, _dp, _dp, _ip],

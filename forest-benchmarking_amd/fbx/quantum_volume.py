@@ -5,6 +5,11 @@ What runs where:
   * ``collect_heavy_outputs[_batch]`` / ``ideal_heavy_output_probability_batch`` -- ``fbx_qv_heavy_outputs``: a state-vector
     simulation of B circuits of one width in one launch, the state in LDS, widths 2..13 (wider: ``FbxError(FBX_ERR_UNSUPPORTED)``;
     there is no host fallback);
+  * ``heavy_outputs_flat_wide`` / ``collect_heavy_outputs_wide_batch`` / ``ideal_heavy_output_probability_wide_batch`` /
+    ``count_heavy_hitters_sampled_wide_batch`` -- the same results for widths 2..26 through one call: widths up to 13 go to the
+    entry points above unchanged, widths 14..26 to ``fbx_qv_heavy_outputs_wide`` / ``fbx_qv_count_heavy_wide`` (the state in device
+    memory, a tile of ``2^tile_bits`` amplitudes at a time in LDS).  ``plan_wide_passes`` is the numpy mirror
+    of the device planner that cuts a circuit into passes (``fbx_qv_wide_plan`` returns the device's decisions);
   * ``count_heavy_hitters_sampled[_batch]`` -- ``fbx_qv_count_heavy``: a streaming reduction of the ``qc.run`` bit arrays;
   * ``simulate_heavy_output_counts_batch`` -- a simulated run resident on the device: ``fbx_qv_heavy_outputs_dev`` ->
     ``fbx_sample_bitstrings_dev`` (noisy measured bitstrings from the ideal distributions) -> ``fbx_qv_count_heavy_dev``;
@@ -31,9 +36,12 @@ __all__ = ["generate_abstract_qv_circuit", "generate_abstract_qv_circuits_batch"
            "collect_heavy_outputs_batch", "ideal_heavy_output_probability_batch", "count_heavy_hitters_sampled",
            "count_heavy_hitters_sampled_batch", "calculate_prob_est_and_err", "get_prob_sample_heavy_by_depth",
            "extract_quantum_volume_from_results", "layer_pairs", "pack_heavy_mask", "unpack_heavy_mask", "heavy_outputs_flat",
-           "simulate_heavy_output_counts_batch"]
+           "simulate_heavy_output_counts_batch", "heavy_outputs_flat_wide", "collect_heavy_outputs_wide_batch",
+           "ideal_heavy_output_probability_wide_batch", "count_heavy_hitters_sampled_wide_batch", "plan_wide_passes"]
 
 MIN_WIDTH, MAX_WIDTH = 2, 13
+MIN_WIDE_WIDTH, MAX_WIDE_WIDTH = 14, 26                  # fbx_qv_*_wide
+WIDE_DEFAULT_TILE_BITS, WIDE_LOW_BITS = 13, 3
 
 
 # ------------------------------------------------------------------------------------------------ circuits
@@ -253,6 +261,163 @@ def count_heavy_hitters_sampled(qc_results: Iterator[np.ndarray], heavy_hitters:
         for row, i in enumerate(idx):
             counts[i] = int(got[row])
     yield from counts
+
+
+# ------------------------------------------------------------------------------------------------ widths 14..26
+def _check_wide(n: int, tile_bits: int, who: str) -> int:
+    from . import _lib
+    if not MIN_WIDTH <= n <= MAX_WIDE_WIDTH:
+        raise _lib.FbxError(_lib.FBX_ERR_UNSUPPORTED, f"{who}: width must be {MIN_WIDTH}..{MAX_WIDE_WIDTH} (got {n}); there is no "
+                                                      f"host fallback")
+    tile_bits = int(tile_bits)
+    if tile_bits != 0 and not 8 <= tile_bits <= 13:
+        raise ValueError(f"{who}: tile_bits must be 0 (the default) or 8..13")
+    return tile_bits
+
+
+def plan_wide_passes(n_qubits: int, pairs, tile_bits: int = 0):
+    """The pass plan of ``fbx_qv_heavy_outputs_wide``, restated in numpy (``fbx_qv_wide_plan`` must agree integer for integer).
+    ``pairs [L, 2]`` or ``[B, L, 2]`` -> ``(n_passes, first_gate, local_mask)``: int32 ``[B]``, int32 ``[B, L + 1]`` and uint32
+    ``[B, L]`` (without the leading axis for one circuit).  Pass k applies gates ``first_gate[k] .. first_gate[k + 1] - 1`` with the
+    index bits of ``local_mask[k]`` local (bit p = index bit p = qubit ``n - 1 - p``); entries past the last pass are L and 0.
+
+    The rule: index bits 0..2 are always local (8 amplitudes = 128 B contiguous in device memory).  A pass takes gates in order
+    while their targets that are not yet local still fit into the ``tile_bits - 3`` free places, and stops at the first gate
+    that does not (no reordering).  Places still free are filled with the lowest index bits not yet local."""
+    n = int(n_qubits)
+    T = int(tile_bits) or WIDE_DEFAULT_TILE_BITS
+    if not MIN_WIDE_WIDTH <= n <= MAX_WIDE_WIDTH:
+        raise ValueError(f"plan_wide_passes: n_qubits must be {MIN_WIDE_WIDTH}..{MAX_WIDE_WIDTH}")
+    if not 8 <= T <= 13:
+        raise ValueError("plan_wide_passes: tile_bits must be 0 (the default) or 8..13")
+    pairs = np.asarray(pairs, dtype=np.int64)
+    single = pairs.ndim == 2
+    if single:
+        pairs = pairs[None]
+    if pairs.ndim != 3 or pairs.shape[2] != 2:
+        raise ValueError("pairs must be [L, 2] or [B, L, 2]")
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= n or np.any(pairs[..., 0] == pairs[..., 1])):
+        raise ValueError("a gate needs two different qubits below n_qubits")
+    B, L = pairs.shape[:2]
+    n_passes = np.zeros(B, dtype=np.int32)
+    first = np.full((B, L + 1), L, dtype=np.int32)
+    masks = np.zeros((B, L), dtype=np.uint32)
+    low = (1 << WIDE_LOW_BITS) - 1
+    for b in range(B):
+        bits = [(1 << (n - 1 - int(q0)), 1 << (n - 1 - int(q1))) for q0, q1 in pairs[b]]
+        k = l = 0
+        while l < L:
+            m, first[b, k] = low, l
+            while l < L:
+                grown = m | bits[l][0] | bits[l][1]
+                if bin(grown).count("1") > T:
+                    break
+                m, l = grown, l + 1
+            p = WIDE_LOW_BITS
+            while bin(m).count("1") < T:
+                m, p = m | (1 << p), p + 1
+            masks[b, k] = m
+            k += 1
+        n_passes[b] = k
+    return (n_passes[0], first[0], masks[0]) if single else (n_passes, first, masks)
+
+
+def heavy_outputs_flat_wide(n_qubits: int, pairs, gates, probabilities=True, median=True, mask=True, heavy_prob=True,
+                            heavy_count=True, tile_bits: int = 0):
+    """``heavy_outputs_flat`` for widths 2..26: up to 13 it IS ``heavy_outputs_flat`` (``tile_bits`` is checked and unused); from 14
+    on ``fbx_qv_heavy_outputs_wide`` with ``tile_bits`` (0 = the library's default, else 8..13; no result depends on it)."""
+    n = int(n_qubits)
+    tile_bits = _check_wide(n, tile_bits, "heavy_outputs_flat_wide")
+    if n <= MAX_WIDTH:
+        return heavy_outputs_flat(n, pairs, gates, probabilities, median, mask, heavy_prob, heavy_count)
+    pairs = np.asarray(pairs)
+    gates = np.asarray(gates)
+    if pairs.ndim != 3 or pairs.shape[2] != 2:
+        raise ValueError("pairs must be [B, L, 2]")
+    B, L = pairs.shape[:2]
+    if gates.shape != (B, L, 4, 4):
+        raise ValueError(f"gates must be [B, L, 4, 4] = {(B, L, 4, 4)}, not {gates.shape}")
+    if not (probabilities or median or mask or heavy_prob or heavy_count):
+        raise ValueError("no output asked for")
+    if pairs.size:
+        if pairs.min() < 0 or pairs.max() >= n:
+            raise ValueError(f"a qubit index is out of range for {n} qubits")
+        if np.any(pairs[..., 0] == pairs[..., 1]):
+            raise ValueError("a gate needs two different qubits")
+    pairs = np.ascontiguousarray(pairs, dtype=np.uint8)
+    from . import _lib
+    import ctypes as C
+    gates = _lib.c128(gates)
+    N, W = 1 << n, _mask_words(n)
+    out = {}
+    if probabilities:
+        out["probabilities"] = np.empty((B, N))
+    if median:
+        out["median"] = np.empty(B)
+    if mask:
+        out["mask"] = np.zeros((B, W), dtype=np.uint64)
+    if heavy_prob:
+        out["heavy_prob"] = np.empty(B)
+    if heavy_count:
+        out["heavy_count"] = np.empty(B, dtype=np.int32)
+    _lib.check(_lib.lib().fbx_qv_heavy_outputs_wide(
+        n, B, L, pairs.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(gates.view(np.float64)), tile_bits,
+        _lib.dptr(out.get("probabilities")), _lib.dptr(out.get("median")),
+        out["mask"].ctypes.data_as(C.POINTER(C.c_uint64)) if mask else None,
+        _lib.dptr(out.get("heavy_prob")), _lib.iptr(out.get("heavy_count"))))
+    return out
+
+
+def collect_heavy_outputs_wide_batch(permutations, gates, pairing: str = "reference", return_probabilities: bool = False,
+                                     return_stats: bool = False, tile_bits: int = 0):
+    """``collect_heavy_outputs_batch`` for widths 2..26 (``heavy_outputs_flat_wide``): the same arguments and return values."""
+    width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
+    r = heavy_outputs_flat_wide(width, pairs, flat, probabilities=return_probabilities, median=return_stats, mask=True,
+                                heavy_prob=return_stats, heavy_count=return_stats, tile_bits=tile_bits)
+    res = [unpack_heavy_mask(r["mask"], width)]
+    if return_probabilities:
+        res.append(r["probabilities"])
+    if return_stats:
+        res.append({k: r[k] for k in ("median", "heavy_prob", "heavy_count")})
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def ideal_heavy_output_probability_wide_batch(permutations, gates, pairing: str = "reference", tile_bits: int = 0) -> np.ndarray:
+    """``ideal_heavy_output_probability_batch`` for widths 2..26; from 14 on the probabilities stay in the device workspace."""
+    width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
+    return heavy_outputs_flat_wide(width, pairs, flat, probabilities=False, median=False, mask=False, heavy_prob=True,
+                                   heavy_count=False, tile_bits=tile_bits)["heavy_prob"]
+
+
+def count_heavy_hitters_sampled_wide_batch(bitarrays, heavy, tile_bits: int = 0) -> np.ndarray:
+    """``count_heavy_hitters_sampled_batch`` for widths 2..26 (from 14 on ``fbx_qv_count_heavy_wide``; ``tile_bits`` is accepted
+    for symmetry with the other ``_wide`` functions and does not enter the count)."""
+    bits = np.asarray(bitarrays)
+    if bits.ndim != 3:
+        raise ValueError("bitarrays must be [B, shots, n_qubits]")
+    B, shots, n = bits.shape
+    _check_wide(n, tile_bits, "count_heavy_hitters_sampled_wide_batch")
+    if n <= MAX_WIDTH:
+        return count_heavy_hitters_sampled_batch(bits, heavy)
+    heavy = np.asarray(heavy)
+    if heavy.dtype == np.uint64:
+        mask = np.ascontiguousarray(heavy)
+        if mask.shape != (B, _mask_words(n)):
+            raise ValueError(f"masks must be [B, W] = {(B, _mask_words(n))}, not {mask.shape}")
+    else:
+        if heavy.shape != (B, 1 << n):
+            raise ValueError(f"heavy must be a boolean table [B, 2^n] = {(B, 1 << n)}, not {heavy.shape}")
+        mask = pack_heavy_mask(heavy)
+    if bits.size and (bits.min() < 0 or bits.max() > 1):
+        raise ValueError("bitarrays must hold 0 / 1")
+    bits = np.ascontiguousarray(bits, dtype=np.uint8)
+    from . import _lib
+    import ctypes as C
+    counts = np.zeros(B, dtype=np.int64)
+    _lib.check(_lib.lib().fbx_qv_count_heavy_wide(n, B, shots, bits.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                  mask.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                  counts.ctypes.data_as(C.POINTER(C.c_int64))))
+    return counts
 
 
 # ------------------------------------------------------------------------------------------------ simulated runs

@@ -132,7 +132,9 @@ int         fbx_release_workspace(void);
  *   "pgdb1_binned" (default 1): the lane-per-reconstruction single-qubit kernel runs one launch per outer iteration with the
  *   reconstructions re-binned by Dykstra count in between from 2^20 experiments to convergence (2^19 for at most 12 settings;
  *   2^17 for a fixed iteration count); 2 = always, 0 = never (one persistent launch).  Results do not depend on it; the binned
- *   form holds 3.5 KB + 16 m bytes of device workspace per reconstruction and synchronises the calling thread's stream. */
+ *   form holds 3.5 KB + 16 m bytes of device workspace per reconstruction and synchronises the calling thread's stream.
+ *   "qv_wide_workspace_mib" (default 128, range [1, 65536]): fbx_qv_heavy_outputs_wide[_dev] runs its batch in chunks of as many
+ *   circuits as fit this many MiB of device workspace (always at least one circuit).  Results do not depend on it. */
 int         fbx_set_option(const char* name, double value);
 int         fbx_get_option(const char* name, double* value);
 
@@ -499,6 +501,32 @@ int fbx_qv_count_heavy(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* 
                        int64_t* counts_out);
 int fbx_qv_count_heavy_dev(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* d_bits, const uint64_t* d_heavy_mask,
                            int64_t* d_counts_out);
+
+/* The same two computations for n_qubits 14..26 (others FBX_ERR_UNSUPPORTED; widths up to 13 belong to the functions above): the
+ * state of a circuit is 16 B x 2^n in device memory and is worked on in LDS a tile of 2^tile_bits amplitudes at a time
+ * (csrc/fbx_qvolume_wide.hip).  Layouts, conventions, the exact median, the tie rule and the poisoned-item rule are
+ * those of fbx_qv_heavy_outputs; W = 2^n / 64.  tile_bits: 0 = the library's default (13), else 8..13 (FBX_ERR_BAD_ARG otherwise).
+ * No result depends on tile_bits, on B or on how the batch was cut into chunks; the probabilities are bitwise the same for every
+ * tile_bits.  heavy_prob_out is summed in one fixed order: blocks of 4096 outputs, the blocks in order.  The batch runs in chunks of
+ * as many circuits as fbx_set_option "qv_wide_workspace_mib" (default 128, range [1, 65536]; at least one circuit) admits at
+ * 16 B x 2^n per circuit, plus 8 B x 2^n when probs_out is NULL.  The _dev form enqueues on the calling thread's stream and does
+ * not synchronise (growing the workspace does, as everywhere). */
+int fbx_qv_heavy_outputs_wide(int n_qubits, int64_t B, int L, const uint8_t* pairs, const double* gates, int tile_bits,
+                              double* probs_out, double* median_out, uint64_t* heavy_mask_out, double* heavy_prob_out,
+                              int32_t* heavy_count_out);
+int fbx_qv_heavy_outputs_wide_dev(int n_qubits, int64_t B, int L, const uint8_t* d_pairs, const double* d_gates, int tile_bits,
+                                  double* d_probs_out, double* d_median_out, uint64_t* d_heavy_mask_out, double* d_heavy_prob_out,
+                                  int32_t* d_heavy_count_out);
+int fbx_qv_count_heavy_wide(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* bits, const uint64_t* heavy_mask,
+                            int64_t* counts_out);
+int fbx_qv_count_heavy_wide_dev(int n_qubits, int64_t B, int64_t n_shots, const uint8_t* d_bits, const uint64_t* d_heavy_mask,
+                                int64_t* d_counts_out);
+/* What the planner of fbx_qv_heavy_outputs_wide decided (host pointers; the planner itself runs on the device): circuit b runs
+ * n_passes_out[b] passes; pass k applies the gates pass_first_gate_out[b][k] .. pass_first_gate_out[b][k + 1] - 1 with the index bits
+ * of pass_local_mask_out[b][k] local (bit p of the mask = index bit p = qubit n - 1 - p; exactly tile_bits bits, always bits 0..2).
+ * Entries past the last pass: first gate L, mask 0.  Bad pairs: FBX_ERR_BAD_ARG. */
+int fbx_qv_wide_plan(int n_qubits, int64_t B, int L, const uint8_t* pairs, int tile_bits, int32_t* n_passes_out /* [B] */,
+                     int32_t* pass_first_gate_out /* [B][L + 1] */, uint32_t* pass_local_mask_out /* [B][L] */);
 
 /* ---------------------------------------------------------------- measured bitstrings from outcome distributions
  * The step between a distribution and a bit record (what a QVM's run-and-measure does for the reference): B items of one width,

@@ -294,6 +294,8 @@ std::atomic<int> g_pieces{8};                         // 2-qubit two-waves kerne
 std::atomic<int> g_binned_1q{1};                      // single-qubit lane-per-item kernel: binned relaunch 0 never / 1 large batches / 2 always
 std::atomic<double> g_qv_wide_ws_mib{128.0};           // fbx_qv_heavy_outputs_wide: cap of the chunk's workspace
 double option_qv_wide_workspace_mib() { return g_qv_wide_ws_mib.load(); }
+std::atomic<double> g_sample_wide_ws_mib{128.0};       // fbx_sample_bitstrings_wide: cap of the chunk's workspace
+double option_sample_wide_workspace_mib() { return g_sample_wide_ws_mib.load(); }
 int option_pgdb_pieces() { return g_pieces.load(); }
 int option_pgdb1_binned() { return g_binned_1q.load(); }
 }  // namespace fbx
@@ -420,6 +422,10 @@ int fbx_set_option(const char* name, double value) {
         FBX_REQUIRE(value >= 1.0 && value <= 65536.0, "fbx_set_option: qv_wide_workspace_mib must be in [1, 65536]");
         fbx::g_qv_wide_ws_mib.store(value); return FBX_OK;
     }
+    if (n == "sample_wide_workspace_mib") {
+        FBX_REQUIRE(value >= 1.0 && value <= 65536.0, "fbx_set_option: sample_wide_workspace_mib must be in [1, 65536]");
+        fbx::g_sample_wide_ws_mib.store(value); return FBX_OK;
+    }
     set_error("fbx_set_option: unknown option '" + n + "'");
     return FBX_ERR_BAD_ARG;
 }
@@ -435,6 +441,7 @@ int fbx_get_option(const char* name, double* value) {
     if (n == "pgdb_pieces") { *value = fbx::g_pieces.load(); return FBX_OK; }
     if (n == "pgdb1_binned") { *value = fbx::g_binned_1q.load(); return FBX_OK; }
     if (n == "qv_wide_workspace_mib") { *value = fbx::g_qv_wide_ws_mib.load(); return FBX_OK; }
+    if (n == "sample_wide_workspace_mib") { *value = fbx::g_sample_wide_ws_mib.load(); return FBX_OK; }
     set_error("fbx_get_option: unknown option '" + n + "'");
     return FBX_ERR_BAD_ARG;
 }

@@ -20,7 +20,7 @@
 // lane draws a run of 16 shots -- 16 bits of outcome each, shifted through four 64-bit registers -- expands them into 16 n bytes and
 // writes them as n 16-byte vectors; the shots in front of the first 16-byte boundary of a range and behind its last full run go
 // byte-wise.
-#include "fbx_common.hpp"
+#include "fbx_sample_common.hpp"
 
 namespace fbx {
 
@@ -57,8 +57,6 @@ template <bool WAVE>
 __device__ __forceinline__ void sample_sync() {
     if constexpr (WAVE) FBX_WAVE_SYNC(); else __syncthreads();
 }
-
-__device__ __forceinline__ bool sample_bad_probability(double v) { return !(v >= 0.0 && v <= 1.0); }      // NaN included
 
 // how many of the N entries are <= t (0..N) = the smallest i with C_i > t: log2(N) dependent reads, no branch
 template <int NQ>
@@ -302,16 +300,8 @@ static int launch_sample(int64_t B, int64_t n_shots, const double* probs, const 
 }
 
 static int sample_check(int n_qubits, int64_t B, int64_t n_shots, const void* probs, int64_t first_item, const void* bits) {
-    FBX_REQUIRE(B >= 0 && n_shots >= 0 && first_item >= 0, "fbx_sample_bitstrings: need B >= 0, n_shots >= 0 and first_item >= 0");
-    FBX_REQUIRE(n_shots < ((int64_t)1 << 32), "fbx_sample_bitstrings: n_shots must be below 2^32 (the shot is one word of the Philox counter)");
-    if (n_qubits < 1 || n_qubits > SAMPLE_MAX_WIDTH) {
-        set_error("fbx_sample_bitstrings: n_qubits must be 1..13 (a wider table does not fit the LDS of one CU; got " +
-                  std::to_string(n_qubits) + ")");
-        return FBX_ERR_UNSUPPORTED;
-    }
-    FBX_REQUIRE(B == 0 || n_shots == 0 || (probs && bits), "fbx_sample_bitstrings: NULL probs / bits_out");
-    FBX_REQUIRE(B <= INT64_MAX / (n_shots ? n_shots : 1) / n_qubits, "fbx_sample_bitstrings: B * n_shots * n_qubits overflows");
-    return FBX_OK;
+    return sample_check("fbx_sample_bitstrings", 1, SAMPLE_MAX_WIDTH, "a wider table does not fit the LDS of one CU", n_qubits, B, n_shots,
+                        probs, first_item, bits);
 }
 
 }  // namespace fbx

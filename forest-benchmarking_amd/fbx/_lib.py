@@ -165,6 +165,8 @@ PROTOTYPES = {
     "fbx_qv_wide_plan": [C.c_int, _i64, C.c_int, _u8p, C.c_int, _ip, _ip, _u32p],
     "fbx_sample_bitstrings": [C.c_int, _i64, _i64, _dp, _dp, _dp, C.c_uint64, _i64, _u8p, _ip],
     "fbx_sample_bitstrings_dev": [C.c_int, _i64, _i64, _vp, _vp, _vp, C.c_uint64, _i64, _vp, _vp],
+    "fbx_sample_bitstrings_wide": [C.c_int, _i64, _i64, _dp, _dp, _dp, C.c_uint64, _i64, _u8p, _ip],
+    "fbx_sample_bitstrings_wide_dev": [C.c_int, _i64, _i64, _vp, _vp, _vp, C.c_uint64, _i64, _vp, _vp],
     "fbx_tomo_simulate": [_vp, _i64, _dp, _i64, _dp, C.c_uint64, _i64, _dp, _dp, _dp, _dp, _ip],
     "fbx_tomo_simulate_dev": [_vp, _i64, _vp, _i64, _vp, C.c_uint64, _i64, _vp, _vp, _vp, _vp, _vp],
     "fbx_curve_fit": [C.c_int, _i64, C.c_int, _dp, _i64, _dp, _dp, _dp, C.c_uint, C.c_double, C.c_double, C.c_int,

@@ -13,6 +13,9 @@ What runs where:
   * ``count_heavy_hitters_sampled[_batch]`` -- ``fbx_qv_count_heavy``: a streaming reduction of the ``qc.run`` bit arrays;
   * ``simulate_heavy_output_counts_batch`` -- a simulated run resident on the device: ``fbx_qv_heavy_outputs_dev`` ->
     ``fbx_sample_bitstrings_dev`` (noisy measured bitstrings from the ideal distributions) -> ``fbx_qv_count_heavy_dev``;
+  * ``simulate_heavy_output_counts_wide_batch`` -- the same run for widths 2..26: up to 13 it IS the function above, from 14 on
+    ``fbx_qv_heavy_outputs_wide_dev`` -> ``fbx_sample_bitstrings_wide_dev`` -> ``fbx_qv_count_heavy_wide_dev`` on slices of circuits
+    that keep the resident probabilities and shots under a cap (DESIGN.md section 4.17);
   * ``generate_abstract_qv_circuit`` -- host numpy with the reference's draw order (a run seeded with ``np.random.seed`` reproduces
     the reference's circuit); ``generate_abstract_qv_circuits_batch`` -- gates from the device generator;
   * ``calculate_prob_est_and_err``, ``get_prob_sample_heavy_by_depth``, ``extract_quantum_volume_from_results`` -- host arithmetic.
@@ -37,7 +40,8 @@ __all__ = ["generate_abstract_qv_circuit", "generate_abstract_qv_circuits_batch"
            "count_heavy_hitters_sampled_batch", "calculate_prob_est_and_err", "get_prob_sample_heavy_by_depth",
            "extract_quantum_volume_from_results", "layer_pairs", "pack_heavy_mask", "unpack_heavy_mask", "heavy_outputs_flat",
            "simulate_heavy_output_counts_batch", "heavy_outputs_flat_wide", "collect_heavy_outputs_wide_batch",
-           "ideal_heavy_output_probability_wide_batch", "count_heavy_hitters_sampled_wide_batch", "plan_wide_passes"]
+           "ideal_heavy_output_probability_wide_batch", "count_heavy_hitters_sampled_wide_batch", "plan_wide_passes",
+           "simulate_heavy_output_counts_wide_batch"]
 
 MIN_WIDTH, MAX_WIDTH = 2, 13
 MIN_WIDE_WIDTH, MAX_WIDE_WIDTH = 14, 26                  # fbx_qv_*_wide
@@ -467,6 +471,69 @@ def simulate_heavy_output_counts_batch(permutations, gates, shots: int, depolari
         stats = {"heavy_prob": d_hp.to_array(np.float64, (B,)), "heavy_count": d_hc.to_array(np.int32, (B,))}
         if shots:
             _raise_poisoned(d_status.to_array(np.int32, (B,)), 0)
+    finally:
+        for b in bufs:
+            b.free()
+    return counts, stats
+
+
+def simulate_heavy_output_counts_wide_batch(permutations, gates, shots: int, depolarizing=0.0, readout_flip=None,
+                                            seed: Optional[int] = None, pairing: str = "reference", tile_bits: int = 0,
+                                            max_resident_mib: float = 1024):
+    """``simulate_heavy_output_counts_batch`` for widths 2..26: up to 13 it IS that function (``tile_bits`` and ``max_resident_mib``
+    are checked and unused); from 14 on ``fbx_qv_heavy_outputs_wide_dev`` -> ``fbx_sample_bitstrings_wide_dev`` ->
+    ``fbx_qv_count_heavy_wide_dev`` on device buffers.  The circuits run in slices, so that the probabilities (8 B x 2^n per
+    circuit) plus the shot bytes of a slice stay under ``max_resident_mib`` (a slice holds at least one circuit); the slice that
+    starts at circuit k is sampled with ``first_item = k``, so circuit b is item b of the stream whatever the cap, and the counts
+    depend neither on the cap nor on ``tile_bits``: they equal the composed host calls (``heavy_outputs_flat_wide`` ->
+    ``sampling.sample_bitstrings_wide_batch`` -> ``count_heavy_hitters_sampled_wide_batch``) on the same seed.
+
+    Returns ``(counts [B] int64, stats)`` as the narrow function does."""
+    import ctypes as C
+    from . import _lib
+    from .sampling import _noise, _raise_poisoned
+    width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
+    tile_bits = _check_wide(width, tile_bits, "simulate_heavy_output_counts_wide_batch")
+    if not float(max_resident_mib) > 0.0:
+        raise ValueError("simulate_heavy_output_counts_wide_batch: max_resident_mib must be positive")
+    if width <= MAX_WIDTH:
+        return simulate_heavy_output_counts_batch(permutations, gates, shots, depolarizing, readout_flip, seed, pairing)
+    B, L = pairs.shape[:2]
+    N, W = 1 << width, _mask_words(width)
+    shots, lam, flips, _ = _noise(B, width, shots, depolarizing, readout_flip)
+    key = _stream_seed(seed)
+    if B == 0:
+        return np.zeros(0, dtype=np.int64), {"heavy_prob": np.zeros(0), "heavy_count": np.zeros(0, dtype=np.int32)}
+    per = 8 * N + shots * width
+    cut = int(max(1, min(B, float(max_resident_mib) * 1048576.0 // per)))
+    DB = _lib.DeviceBuffer
+    lib = _lib.lib()
+    bufs = []
+
+    def dev(x):
+        bufs.append(x)
+        return x
+
+    def at(buf, offset):
+        return None if buf is None else C.c_void_p(buf.ptr.value + offset)
+    try:
+        d_pairs, d_gates = dev(DB.from_array(pairs)), dev(DB.from_array(_lib.c128(flat)))
+        d_lam = dev(DB.from_array(lam)) if lam is not None else None
+        d_flips = dev(DB.from_array(flips)) if flips is not None else None
+        d_probs, d_mask = dev(DB(8 * cut * N)), dev(DB(8 * cut * W))
+        d_bits = dev(DB(max(cut * shots * width, 16)))
+        d_hp, d_hc, d_status, d_counts = dev(DB(8 * B)), dev(DB(4 * B)), dev(DB(4 * B)), dev(DB(8 * B))
+        for k in range(0, B, cut):
+            cb = min(cut, B - k)
+            _lib.check(lib.fbx_qv_heavy_outputs_wide_dev(width, cb, L, at(d_pairs, 2 * L * k), at(d_gates, 256 * L * k), tile_bits,
+                                                         d_probs.ptr, None, d_mask.ptr, at(d_hp, 8 * k), at(d_hc, 4 * k)))
+            _lib.check(lib.fbx_sample_bitstrings_wide_dev(width, cb, shots, d_probs.ptr, at(d_lam, 8 * k),
+                                                          at(d_flips, 16 * width * k), key, k, d_bits.ptr, at(d_status, 4 * k)))
+            _lib.check(lib.fbx_qv_count_heavy_wide_dev(width, cb, shots, d_bits.ptr, d_mask.ptr, at(d_counts, 8 * k)))
+        counts = d_counts.to_array(np.int64, (B,))
+        stats = {"heavy_prob": d_hp.to_array(np.float64, (B,)), "heavy_count": d_hc.to_array(np.int32, (B,))}
+        if shots:
+            _raise_poisoned(d_status.to_array(np.int32, (B,)), 0, "simulate_heavy_output_counts_wide_batch")
     finally:
         for b in bufs:
             b.free()

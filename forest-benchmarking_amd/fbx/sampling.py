@@ -11,9 +11,10 @@ import numpy as np
 
 from .operator_tools.random_operators import _stream_seed
 
-__all__ = ["sample_bitstrings_batch"]
+__all__ = ["sample_bitstrings_batch", "sample_bitstrings_wide_batch"]
 
 MIN_WIDTH, MAX_WIDTH = 1, 13
+MIN_WIDE_WIDTH, MAX_WIDE_WIDTH = 14, 26                  # fbx_sample_bitstrings_wide
 
 
 def _noise(B, n, shots, depolarizing, readout_flip, first_item=0):
@@ -36,11 +37,11 @@ def _noise(B, n, shots, depolarizing, readout_flip, first_item=0):
     return shots, lam, flips, first_item
 
 
-def _raise_poisoned(status, first_item):
+def _raise_poisoned(status, first_item, who="sample_bitstrings_batch"):
     bad = np.flatnonzero(status)
     if bad.size:
         b = int(bad[0])
-        raise ValueError(f"sample_bitstrings_batch: item {b} (global id {first_item + b}) cannot be sampled: a weight that is "
+        raise ValueError(f"{who}: item {b} (global id {first_item + b}) cannot be sampled: a weight that is "
                          f"negative or not finite, weights without a positive finite sum, or a depolarizing / readout_flip "
                          f"value outside [0, 1] ({bad.size} such item(s) in the batch)")
 
@@ -73,4 +74,34 @@ def sample_bitstrings_batch(probabilities, shots, depolarizing=None, readout_fli
     if return_status:
         return bits, status
     _raise_poisoned(status, first_item)
+    return bits
+
+
+def sample_bitstrings_wide_batch(probabilities, shots, depolarizing=None, readout_flip=None, seed=None, first_item=0,
+                                 return_status=False):
+    """``sample_bitstrings_batch`` for widths 1..26 through one call: up to 13 qubits it IS ``sample_bitstrings_batch``; from 14 on
+    ``fbx_sample_bitstrings_wide`` draws from a table of prefix sums in device memory.  Arguments,
+    broadcasting, the stream (column j of a shot reads word ``2 + j`` of its Philox blocks, now up to seven of them), the
+    ``ValueError`` for an item that cannot be sampled and ``return_status`` are those of ``sample_bitstrings_batch``.  Wider than 26:
+    ``FbxError(FBX_ERR_UNSUPPORTED)``; there is no host sampler behind it."""
+    from . import _lib
+    p = np.asarray(probabilities)
+    if p.ndim != 2 or p.shape[1] < 2 or p.shape[1] & (p.shape[1] - 1):
+        raise ValueError("probabilities must be [B, 2^n] with n >= 1")
+    n = p.shape[1].bit_length() - 1
+    if n <= MAX_WIDTH:
+        return sample_bitstrings_batch(p, shots, depolarizing, readout_flip, seed, first_item, return_status)
+    if n > MAX_WIDE_WIDTH:
+        raise _lib.FbxError(_lib.FBX_ERR_UNSUPPORTED, f"sample_bitstrings_wide_batch: width must be {MIN_WIDTH}..{MAX_WIDE_WIDTH} "
+                                                      f"(got {n}); there is no host fallback")
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    B = p.shape[0]
+    shots, lam, flips, first_item = _noise(B, n, shots, depolarizing, readout_flip, first_item)
+    bits = np.zeros((B, shots, n), dtype=np.uint8)
+    status = np.zeros(B, dtype=np.int32)
+    _lib.check(_lib.lib().fbx_sample_bitstrings_wide(n, B, shots, _lib.dptr(p), _lib.dptr(lam), _lib.dptr(flips), _stream_seed(seed),
+                                                     first_item, bits.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.iptr(status)))
+    if return_status:
+        return bits, status
+    _raise_poisoned(status, first_item, "sample_bitstrings_wide_batch")
     return bits

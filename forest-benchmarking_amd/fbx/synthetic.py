@@ -158,6 +158,12 @@ def qv_shots_batch(probabilities, shots, depolarizing=0.0, readout_flip=None, se
     return sample_bitstrings_batch(probabilities, shots, depolarizing=depolarizing, readout_flip=readout_flip, seed=int(seed))
 
 
+def qv_shots_wide_batch(probabilities, shots, depolarizing=0.0, readout_flip=None, seed=3000):
+    """``qv_shots_batch`` for widths 1..26 (``sampling.sample_bitstrings_wide_batch``): up to 13 qubits it IS ``qv_shots_batch``."""
+    from .sampling import sample_bitstrings_wide_batch
+    return sample_bitstrings_wide_batch(probabilities, shots, depolarizing=depolarizing, readout_flip=readout_flip, seed=int(seed))
+
+
 def rb_data(n_qubits, depths, decay=0.97, shots=500, batch=1, seed=4000):
     """Synthetic randomized-benchmarking statistics in the shapes ``randomized_benchmarking.fit_rb_results_batch`` takes:
     ``(z_expectations, z_std_errs)``, both [batch, len(depths), 2^n - 1].  A sequence of depth m leaves the depolarised state

@@ -134,7 +134,9 @@ int         fbx_release_workspace(void);
  *   2^17 for a fixed iteration count); 2 = always, 0 = never (one persistent launch).  Results do not depend on it; the binned
  *   form holds 3.5 KB + 16 m bytes of device workspace per reconstruction and synchronises the calling thread's stream.
  *   "qv_wide_workspace_mib" (default 128, range [1, 65536]): fbx_qv_heavy_outputs_wide[_dev] runs its batch in chunks of as many
- *   circuits as fit this many MiB of device workspace (always at least one circuit).  Results do not depend on it. */
+ *   circuits as fit this many MiB of device workspace (always at least one circuit).  Results do not depend on it.
+ *   "sample_wide_workspace_mib" (default 128, range [1, 65536]): fbx_sample_bitstrings_wide[_dev] runs its batch in chunks of as
+ *   many items as fit this many MiB of device workspace (always at least one item).  Results do not depend on it. */
 int         fbx_set_option(const char* name, double value);
 int         fbx_get_option(const char* name, double* value);
 
@@ -544,8 +546,9 @@ int fbx_qv_wide_plan(int n_qubits, int64_t B, int L, const uint8_t* pairs, int t
  * probability outside [0, 1] or NaN -- gets status 1 and a record of zeros; its neighbours are untouched.
  *
  * THE STREAM (part of the contract: it is what a host check restates).  Shot s of the item with the global id g = first_item + b
- * owns the Philox4x32-10 blocks with counter (g low, g high, s, t), t = 0, 1, 2, 3, and key (seed low, seed high); their words, in
- * order, are x_0 .. x_15 (only the blocks that are needed are computed).  The draw is u = k * 2^-53, k = ((x_0 >> 5) << 26) |
+ * owns the Philox4x32-10 blocks with counter (g low, g high, s, t) and key (seed low, seed high), t = 0..3 for widths up to 13, up
+ * to 6 for the wide form (fbx_sample_bitstrings_wide below); their words, in order, are x_0 .. x_15 (x_0 .. x_27 for the wide form;
+ * only the blocks that are needed are computed).  The draw is u = k * 2^-53, k = ((x_0 >> 5) << 26) |
  * (x_1 >> 6): exact, in [0, 1).  With C the inclusive prefix sums of w, the outcome is the smallest i with C_i > u * C_{N-1}; if
  * rounding leaves none, the last i with w_i > 0.  C is non-decreasing in i and repeats its predecessor exactly where w_i == 0 (the
  * order in which it is summed is otherwise not specified), so an outcome of weight zero is never produced.  Column j, whose
@@ -558,6 +561,23 @@ int fbx_sample_bitstrings(int n_qubits, int64_t B, int64_t n_shots, const double
 int fbx_sample_bitstrings_dev(int n_qubits, int64_t B, int64_t n_shots, const double* d_probs, const double* d_depolarizing,
                               const double* d_readout_flip, uint64_t seed, int64_t first_item, uint8_t* d_bits_out,
                               int32_t* d_status_out);
+
+/* The same sampler for n_qubits 14..26 (others FBX_ERR_UNSUPPORTED, before any buffer is touched; widths up to 13 belong to the
+ * functions above): the table of prefix sums of an item is 8 B x 2^n in device memory (csrc/fbx_sample_wide.hip).
+ * Layouts, the meaning of probs, depolarizing, readout_flip, bits_out and status_out, the argument errors, the poisoned-item rule
+ * and THE STREAM are those of fbx_sample_bitstrings, with t = 0..6: column j reads x_{2 + j}, j = 0 .. n - 1, of the words
+ * x_0 .. x_27.  C is summed in one fixed order per width (blocks of 4096 entries, the block offsets chained in order), is
+ * non-decreasing and repeats its predecessor bit for bit where w_i == 0.  The batch runs in chunks of as many items as
+ * fbx_set_option "sample_wide_workspace_mib" (default 128, range [1, 65536]; at least one item) admits at 8 B x 2^n (+ 32 B per
+ * 4096 entries + 456 B) per item.  A record depends on (seed, g, s) and its item's inputs only: not on B, n_shots, the cut into shot
+ * ranges, the chunks or the option.  The _dev form enqueues on the calling thread's stream and does not synchronise (growing the
+ * workspace does, as everywhere). */
+int fbx_sample_bitstrings_wide(int n_qubits, int64_t B, int64_t n_shots, const double* probs, const double* depolarizing,
+                               const double* readout_flip, uint64_t seed, int64_t first_item, uint8_t* bits_out,
+                               int32_t* status_out);
+int fbx_sample_bitstrings_wide_dev(int n_qubits, int64_t B, int64_t n_shots, const double* d_probs, const double* d_depolarizing,
+                                   const double* d_readout_flip, uint64_t seed, int64_t first_item, uint8_t* d_bits_out,
+                                   int32_t* d_status_out);
 
 /* ---------------------------------------------------------------- simulated tomography experiments: truth to noisy expectations
  * The acquisition half of a tomography experiment (what do_tomography / estimate_observables, observable_estimation.py:856-920,

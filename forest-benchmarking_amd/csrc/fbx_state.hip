@@ -636,6 +636,12 @@ proj_state_kernel(long long B, const double* __restrict__ rho_in, double* __rest
     if (act) { v.re = rho_in[(item * D + lane) * 2]; v.im = rho_in[(item * D + lane) * 2 + 1]; }
     double tr_re = (act && lane / d == lane % d) ? v.re : 0.0, tr_im = (act && lane / d == lane % d) ? v.im : 0.0;
     tr_re = wave_sum(tr_re); tr_im = wave_sum(tr_im);
+    // A non-finite item gives NaN in every entry, as proj_state_big_kernel: the minimum below drops a NaN eigenvalue, and such an
+    // item would pass for physical and come back with its finite entries in place.
+    if (!(wave_sum(fabs(v.re) + fabs(v.im)) <= DBL_MAX)) {
+        if (act) { out[(item * D + lane) * 2] = NAN; out[(item * D + lane) * 2 + 1] = NAN; }
+        return;
+    }
     const cplx q = div_by_trace(v, tr_re, tr_im);
     if (act) L.rho[lane] = q;
     FBX_WAVE_SYNC();
@@ -687,6 +693,17 @@ state_measures_kernel(long long B, const double* __restrict__ rho_in, const doub
         a.re = rho_in[(item * D + lane) * 2]; a.im = rho_in[(item * D + lane) * 2 + 1];
         b.re = sig_in[(item * D + lane) * 2]; b.im = sig_in[(item * D + lane) * 2 + 1];
         L.rho[lane] = a; L.U[lane] = b;
+    }
+    // A non-finite pair gives NaN in every output asked for, as state_measures_big_kernel: the column maximum of the trace
+    // distance drops a NaN, and the clipped square roots of the fidelity turn NaN eigenvalues into zeros.
+    if (!(wave_sum(fabs(a.re) + fabs(a.im) + fabs(b.re) + fabs(b.im)) <= DBL_MAX)) {
+        if (lane == 0) {
+            if (purity) purity[item] = NAN;
+            if (fidelity) fidelity[item] = NAN;
+            if (tdist) tdist[item] = NAN;
+            if (hsip) hsip[item] = NAN;
+        }
+        return;
     }
     FBX_WAVE_SYNC();
     if (purity) {                                  // Re tr(rho rho)

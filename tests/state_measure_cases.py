@@ -44,7 +44,10 @@ def orthogonal(d, rng):
 
 
 def rank_deficient(d, rng):
-    """mixed / mixed, ranks 3d/4 with supports that overlap on d/2 directions of a common random basis"""
+    """mixed / mixed, ranks 3d/4 with supports that overlap on d/2 directions of a common random basis; for one qubit (no room
+    for two deficient ranks that overlap) a pure state and a full-rank one in a common basis"""
+    if d == 2:
+        return _commuting(d, rng, np.array([1.0, 0.0]), cc.random_spectrum(d, rng))
     q = d // 4
     a = np.concatenate([cc.random_spectrum(3 * q, rng), np.zeros(q)])
     b = np.concatenate([np.zeros(q), cc.random_spectrum(3 * q, rng)])

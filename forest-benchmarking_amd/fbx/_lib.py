@@ -163,6 +163,9 @@ PROTOTYPES = {
     "fbx_qv_count_heavy_wide": [C.c_int, _i64, _i64, _u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
     "fbx_qv_count_heavy_wide_dev": [C.c_int, _i64, _i64, _vp, _vp, _vp],
     "fbx_qv_wide_plan": [C.c_int, _i64, C.c_int, _u8p, C.c_int, _ip, _ip, _u32p],
+    "fbx_qv_noisy_trajectories": [C.c_int, _i64, C.c_int, _i64, _u8p, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64, _i64,
+                                  _dp, _dp, _ip, _ip],
+    "fbx_qv_noisy_trajectories_dev": [C.c_int, _i64, C.c_int, _i64, _vp, _vp, _vp, _vp, C.c_uint64, _i64, _vp, _vp, _vp, _vp],
     "fbx_sample_bitstrings": [C.c_int, _i64, _i64, _dp, _dp, _dp, C.c_uint64, _i64, _u8p, _ip],
     "fbx_sample_bitstrings_dev": [C.c_int, _i64, _i64, _vp, _vp, _vp, C.c_uint64, _i64, _vp, _vp],
     "fbx_sample_bitstrings_wide": [C.c_int, _i64, _i64, _dp, _dp, _dp, C.c_uint64, _i64, _u8p, _ip],

@@ -16,6 +16,13 @@ What runs where:
   * ``simulate_heavy_output_counts_wide_batch`` -- the same run for widths 2..26: up to 13 it IS the function above, from 14 on
     ``fbx_qv_heavy_outputs_wide_dev`` -> ``fbx_sample_bitstrings_wide_dev`` -> ``fbx_qv_count_heavy_wide_dev`` on slices of circuits
     that keep the resident probabilities and shots under a cap (DESIGN.md section 4.17);
+  * ``noisy_trajectories_flat`` / ``noisy_heavy_output_probability_batch`` -- ``fbx_qv_noisy_trajectories``: the same circuits
+    under gate noise, as stochastic Pauli-error trajectories (after every gate, with that gate's error probability, one of the 15
+    two-qubit Paulis on its pair), widths 2..13, the Pauli folded into the gate's own pass over the state.
+    ``simulate_noisy_heavy_output_counts_batch`` is the resident run under that noise.  ``fold_gate_errors`` multiplies the Paulis
+    of one trajectory (``synthetic.restate_qv_gate_errors`` restates the device's draws) into the gates: the trajectory is then an
+    ordinary circuit for every entry point above, the ``_wide`` ones included -- noisy trajectories of widths 14..26 exist by
+    composition, one circuit per trajectory, without a kernel of their own;
   * ``generate_abstract_qv_circuit`` -- host numpy with the reference's draw order (a run seeded with ``np.random.seed`` reproduces
     the reference's circuit); ``generate_abstract_qv_circuits_batch`` -- gates from the device generator;
   * ``calculate_prob_est_and_err``, ``get_prob_sample_heavy_by_depth``, ``extract_quantum_volume_from_results`` -- host arithmetic.
@@ -41,7 +48,8 @@ __all__ = ["generate_abstract_qv_circuit", "generate_abstract_qv_circuits_batch"
            "extract_quantum_volume_from_results", "layer_pairs", "pack_heavy_mask", "unpack_heavy_mask", "heavy_outputs_flat",
            "simulate_heavy_output_counts_batch", "heavy_outputs_flat_wide", "collect_heavy_outputs_wide_batch",
            "ideal_heavy_output_probability_wide_batch", "count_heavy_hitters_sampled_wide_batch", "plan_wide_passes",
-           "simulate_heavy_output_counts_wide_batch"]
+           "simulate_heavy_output_counts_wide_batch", "noisy_trajectories_flat", "noisy_heavy_output_probability_batch",
+           "fold_gate_errors", "simulate_noisy_heavy_output_counts_batch"]
 
 MIN_WIDTH, MAX_WIDTH = 2, 13
 MIN_WIDE_WIDTH, MAX_WIDE_WIDTH = 14, 26                  # fbx_qv_*_wide
@@ -534,6 +542,199 @@ def simulate_heavy_output_counts_wide_batch(permutations, gates, shots: int, dep
         stats = {"heavy_prob": d_hp.to_array(np.float64, (B,)), "heavy_count": d_hc.to_array(np.int32, (B,))}
         if shots:
             _raise_poisoned(d_status.to_array(np.int32, (B,)), 0, "simulate_heavy_output_counts_wide_batch")
+    finally:
+        for b in bufs:
+            b.free()
+    return counts, stats
+
+
+# ------------------------------------------------------------------------------------------------ gate noise
+# P[k] = (X^xa Z^za) (x) (X^xc Z^zc) for the Pauli index k = 4 a + c (0 = I, 1 = X, 2 = Y, 3 = Z; a on q0, c on q1), with Y
+# written as X Z = -i Y: the form the device applies (only probabilities leave it, so the phase is immaterial).
+_PAULI_1Q = np.array([[[1, 0], [0, 1]], [[0, 1], [1, 0]], [[0, -1], [1, 0]], [[1, 0], [0, -1]]], dtype=np.float64)
+_PAULI_2Q = np.stack([np.kron(_PAULI_1Q[k >> 2], _PAULI_1Q[k & 3]) for k in range(16)])
+
+
+def fold_gate_errors(gates_flat, paulis) -> np.ndarray:
+    """The gates of a trajectory with its Pauli errors folded in: ``gates_flat [..., L, 4, 4]`` and ``paulis [..., L]`` (the index
+    ``k = 4 a + c`` of the Pauli after each gate, 0 = none; what ``synthetic.restate_qv_gate_errors`` returns) ->
+    ``(P_a (x) P_c) U`` for every gate, with Y taken as X Z (a global phase, immaterial to every probability).  The leading axes
+    broadcast; ``gates_flat [B, L, 4, 4]`` with ``paulis [B, T, L]`` gives ``[B, T, L, 4, 4]``.  Folding only permutes and negates
+    rows, so it is exact: a folded trajectory is an ordinary circuit, for ``heavy_outputs_flat`` as for ``heavy_outputs_flat_wide``
+    (widths 14..26), and on widths 2..13 it reproduces the device's trajectory arithmetic term for term."""
+    gates = np.asarray(gates_flat, dtype=np.complex128)
+    k = np.asarray(paulis)
+    if gates.ndim < 3 or gates.shape[-2:] != (4, 4):
+        raise ValueError("gates_flat must be [..., L, 4, 4]")
+    if not np.issubdtype(k.dtype, np.integer) or k.ndim < 1 or k.shape[-1] != gates.shape[-3]:
+        raise ValueError("paulis must be an integer array [..., L] with the L of gates_flat")
+    if k.size and (k.min() < 0 or k.max() > 15):
+        raise ValueError("a Pauli index must be 0..15")
+    if k.ndim == gates.ndim - 1 and k.ndim >= 3:                          # [B, T, L] against [B, L, 4, 4]
+        gates = gates[..., None, :, :, :]
+    return np.matmul(_PAULI_2Q[k], gates)
+
+
+def _gate_error_array(gate_error, B: int, L: int) -> np.ndarray:
+    ge = np.asarray(gate_error, dtype=np.float64)
+    if ge.shape == (B,):
+        ge = ge[:, None]
+    elif ge.shape not in ((), (B, L)):
+        raise ValueError(f"gate_error must be a scalar, [B] = {(B,)} or [B, L] = {(B, L)}, not {ge.shape}")
+    return np.ascontiguousarray(np.broadcast_to(ge, (B, L)))
+
+
+def _heavy_masks(heavy, B: int, n: int) -> np.ndarray:
+    heavy = np.asarray(heavy)
+    if heavy.dtype == np.uint64:
+        if heavy.shape != (B, _mask_words(n)):
+            raise ValueError(f"masks must be [B, W] = {(B, _mask_words(n))}, not {heavy.shape}")
+        return np.ascontiguousarray(heavy)
+    if heavy.shape != (B, 1 << n):
+        raise ValueError(f"heavy must be a boolean table [B, 2^n] = {(B, 1 << n)}, not {heavy.shape}")
+    return pack_heavy_mask(heavy)
+
+
+def noisy_trajectories_flat(n_qubits: int, pairs, gates, gate_error, trajectories: int, heavy=None, seed: Optional[int] = None,
+                            first_item: int = 0, probs_mean: bool = True, hprob_traj: Optional[bool] = None, n_errors: bool = True):
+    """``fbx_qv_noisy_trajectories`` on flat gate lists: ``trajectories`` = T stochastic Pauli-error trajectories of each of the B
+    circuits ``pairs [B, L, 2]``, ``gates [B, L, 4, 4]`` (as ``heavy_outputs_flat`` takes them).  ``gate_error`` -- a scalar, ``[B]``
+    or ``[B, L]`` -- is the probability that a gate is followed by one of the 15 non-identity Paulis on its pair, chosen uniformly.
+    ``heavy``: the heavy sets of the IDEAL circuits, the boolean table ``[B, 2^n]`` or the packed masks ``[B, W]`` (uint64) of
+    ``heavy_outputs_flat``; needed for ``hprob_traj`` (asked for by default exactly when ``heavy`` is given).
+
+    Returns a dict with the outputs asked for: ``probs_mean [B, 2^n]`` (the mean output distribution over the T trajectories),
+    ``hprob_traj [B, T]`` (the weight of every trajectory on the heavy set), ``n_errors [B, T]`` (int32, the Paulis inserted), and
+    always ``status [B]`` (int32): 1 for a poisoned circuit (a non-finite gate entry, a pair that is not two different qubits below
+    ``n_qubits``, a gate error outside [0, 1]), whose float outputs are NaN.  Trajectory t of circuit b depends on
+    ``(seed, first_item + b, t)`` and the circuit alone (``seed=None``: a fresh key, the rule of ``random_operators``); the draws are
+    restated by ``synthetic.restate_qv_gate_errors``.  Widths 2..13; a wider trajectory is a circuit for ``heavy_outputs_flat_wide``
+    after ``fold_gate_errors``."""
+    n, T, first_item = int(n_qubits), int(trajectories), int(first_item)
+    pairs = np.asarray(pairs)
+    gates = np.asarray(gates)
+    if pairs.ndim != 3 or pairs.shape[2] != 2:
+        raise ValueError("pairs must be [B, L, 2]")
+    B, L = pairs.shape[:2]
+    if gates.shape != (B, L, 4, 4):
+        raise ValueError(f"gates must be [B, L, 4, 4] = {(B, L, 4, 4)}, not {gates.shape}")
+    if pairs.size and (pairs.min() < 0 or pairs.max() > 255):
+        raise ValueError("qubit indices must be 0..255")
+    if hprob_traj is None:
+        hprob_traj = heavy is not None
+    if hprob_traj and heavy is None:
+        raise ValueError("hprob_traj needs the heavy sets of the ideal circuits")
+    if not (probs_mean or hprob_traj or n_errors):
+        raise ValueError("no output asked for")
+    from . import _lib
+    import ctypes as C
+    pairs = np.ascontiguousarray(pairs, dtype=np.uint8)
+    gates = _lib.c128(gates)
+    ge = _gate_error_array(gate_error, B, L)
+    ok = MIN_WIDTH <= n <= MAX_WIDTH and T >= 0          # (outside, the library refuses before it touches a buffer)
+    mask = _heavy_masks(heavy, B, n) if heavy is not None and n >= 0 else None
+    out = {"status": np.zeros(B, dtype=np.int32)}
+    if probs_mean:
+        out["probs_mean"] = np.empty((B, 1 << n if ok else 0))
+    if hprob_traj:
+        out["hprob_traj"] = np.empty((B, T if ok else 0))
+    if n_errors:
+        out["n_errors"] = np.zeros((B, T if ok else 0), dtype=np.int32)
+    _lib.check(_lib.lib().fbx_qv_noisy_trajectories(
+        n, B, L, T, pairs.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(gates.view(np.float64)), _lib.dptr(ge),
+        mask.ctypes.data_as(C.POINTER(C.c_uint64)) if mask is not None else None, _stream_seed(seed), first_item,
+        _lib.dptr(out.get("probs_mean")), _lib.dptr(out.get("hprob_traj")), _lib.iptr(out.get("n_errors")), _lib.iptr(out["status"])))
+    return out
+
+
+def _raise_poisoned_circuit(status, first_item: int, who: str):
+    bad = np.flatnonzero(status)
+    if bad.size:
+        b = int(bad[0])
+        raise ValueError(f"{who}: circuit {b} (global id {first_item + b}) cannot be simulated: a gate entry that is not finite or a "
+                         f"gate error outside [0, 1] ({bad.size} such circuit(s) in the batch)")
+
+
+def noisy_heavy_output_probability_batch(permutations, gates, gate_error, trajectories: int, pairing: str = "reference",
+                                         seed: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The heavy-output probability of B model circuits under gate noise, in two device calls: the heavy sets of the ideal
+    circuits (``heavy_outputs_flat``), then ``trajectories`` Pauli-error trajectories of each (``noisy_trajectories_flat``).
+    Returns ``(mean [B], std_err [B])``: the mean over the trajectories of the weight on the IDEAL heavy set -- what the measured
+    heavy fraction of a device with that gate error estimates -- and its standard error, the sample deviation over
+    ``sqrt(trajectories)`` (NaN for fewer than two trajectories)."""
+    width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
+    T = int(trajectories)
+    if T < 1:
+        raise ValueError("noisy_heavy_output_probability_batch: need at least one trajectory")
+    ideal = heavy_outputs_flat(width, pairs, flat, probabilities=False, median=False, mask=True, heavy_prob=False, heavy_count=False)
+    r = noisy_trajectories_flat(width, pairs, flat, gate_error, T, heavy=ideal["mask"], seed=seed, probs_mean=False, n_errors=False)
+    _raise_poisoned_circuit(r["status"], 0, "noisy_heavy_output_probability_batch")
+    hp = r["hprob_traj"]
+    err = hp.std(axis=1, ddof=1) / np.sqrt(T) if T >= 2 else np.full(hp.shape[0], np.nan)
+    return hp.mean(axis=1), err
+
+
+def simulate_noisy_heavy_output_counts_batch(permutations, gates, shots: int, gate_error, trajectories: int, readout_flip=None,
+                                             seed: Optional[int] = None, pairing: str = "reference"):
+    """A simulated quantum-volume run under GATE noise, resident on the device (the ``_dev`` entry points only): heavy sets of the
+    ideal circuits (``fbx_qv_heavy_outputs_dev``) -> the mean output distribution of ``trajectories`` = T Pauli-error trajectories
+    per circuit (``fbx_qv_noisy_trajectories_dev``, ``gate_error`` a scalar, ``[B]`` or ``[B, L]``) -> ``shots`` measured bitstrings
+    per circuit drawn from that mean (``fbx_sample_bitstrings_dev``: no depolarizing, optionally readout flips ``[n, 2]`` or
+    ``[B, n, 2]``) -> heavy-hitter counts against the IDEAL heavy sets (``fbx_qv_count_heavy_dev``).
+
+    The shots are drawn from the MEAN of T trajectories, not each from a trajectory of its own: that is the noisy channel's
+    output distribution only up to the sampling error of the mean, and exact only as T grows (the error of an outcome's
+    probability falls like ``1 / sqrt(T)``; ``stats["noisy_heavy_prob_err"]`` is that error for the heavy set).
+
+    Returns ``(counts [B] int64, stats)``: ``stats["heavy_prob"]`` and ``stats["heavy_count"]`` of the ideal circuits,
+    ``stats["noisy_heavy_prob"]`` = the mean over the trajectories of the weight on the ideal heavy set and
+    ``stats["noisy_heavy_prob_err"]`` its standard error.  The trajectories and the shots both take ``seed`` (their streams carry
+    different key tags) with circuit b as item b, so the counts equal those of the composed host calls (``heavy_outputs_flat`` ->
+    ``noisy_trajectories_flat`` -> ``sampling.sample_bitstrings_batch`` -> ``count_heavy_hitters_sampled_batch``) on the same seed."""
+    from . import _lib
+    from .sampling import _noise, _raise_poisoned
+    width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
+    B, L = pairs.shape[:2]
+    T = int(trajectories)
+    if not MIN_WIDTH <= width <= MAX_WIDTH:
+        raise _lib.FbxError(_lib.FBX_ERR_UNSUPPORTED, f"simulate_noisy_heavy_output_counts_batch: width must be {MIN_WIDTH}..{MAX_WIDTH} "
+                                                      f"(got {width}); there is no host fallback")
+    if not 1 <= T < 2 ** 32:
+        raise ValueError("simulate_noisy_heavy_output_counts_batch: need 1 <= trajectories < 2^32")
+    N, W = 1 << width, _mask_words(width)
+    shots, _, flips, _ = _noise(B, width, shots, None, readout_flip)
+    ge = _gate_error_array(gate_error, B, L)
+    key = _stream_seed(seed)
+    if B == 0:
+        return np.zeros(0, dtype=np.int64), {"heavy_prob": np.zeros(0), "heavy_count": np.zeros(0, dtype=np.int32),
+                                             "noisy_heavy_prob": np.zeros(0), "noisy_heavy_prob_err": np.zeros(0)}
+    DB = _lib.DeviceBuffer
+    lib = _lib.lib()
+    bufs = []
+
+    def dev(x):
+        bufs.append(x)
+        return x
+    try:
+        d_pairs, d_gates, d_ge = dev(DB.from_array(pairs)), dev(DB.from_array(_lib.c128(flat))), dev(DB.from_array(ge))
+        d_flips = dev(DB.from_array(flips)) if flips is not None else None
+        d_probs, d_mask, d_hp, d_hc = dev(DB(8 * B * N)), dev(DB(8 * B * W)), dev(DB(8 * B)), dev(DB(4 * B))
+        d_traj, d_tstatus = dev(DB(8 * B * T)), dev(DB(4 * B))
+        d_bits, d_status, d_counts = dev(DB(max(B * shots * width, 16))), dev(DB(4 * B)), dev(DB(8 * B))
+        _lib.check(lib.fbx_qv_heavy_outputs_dev(width, B, L, d_pairs.ptr, d_gates.ptr, None, None, d_mask.ptr, d_hp.ptr, d_hc.ptr))
+        _lib.check(lib.fbx_qv_noisy_trajectories_dev(width, B, L, T, d_pairs.ptr, d_gates.ptr, d_ge.ptr, d_mask.ptr, key, 0,
+                                                     d_probs.ptr, d_traj.ptr, None, d_tstatus.ptr))
+        _lib.check(lib.fbx_sample_bitstrings_dev(width, B, shots, d_probs.ptr, None, d_flips.ptr if d_flips else None, key, 0,
+                                                 d_bits.ptr, d_status.ptr))
+        _lib.check(lib.fbx_qv_count_heavy_dev(width, B, shots, d_bits.ptr, d_mask.ptr, d_counts.ptr))
+        counts = d_counts.to_array(np.int64, (B,))
+        hp = d_traj.to_array(np.float64, (B, T))
+        stats = {"heavy_prob": d_hp.to_array(np.float64, (B,)), "heavy_count": d_hc.to_array(np.int32, (B,)),
+                 "noisy_heavy_prob": hp.mean(axis=1),
+                 "noisy_heavy_prob_err": hp.std(axis=1, ddof=1) / np.sqrt(T) if T >= 2 else np.full(B, np.nan)}
+        _raise_poisoned_circuit(d_tstatus.to_array(np.int32, (B,)), 0, "simulate_noisy_heavy_output_counts_batch")
+        if shots:
+            _raise_poisoned(d_status.to_array(np.int32, (B,)), 0, "simulate_noisy_heavy_output_counts_batch")
     finally:
         for b in bufs:
             b.free()

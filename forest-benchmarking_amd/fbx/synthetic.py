@@ -354,3 +354,43 @@ def restate_dfe_counts(exact, coefs, shots, seed, first_item=0, key_tag=DFE_KEY_
     prod = np.array([[int(p) * int(q_) * 4 for p, q_ in zip(rp, rm)] for rp, rm in zip(k_plus, k_minus)], dtype=object)
     s = np.abs(coefs)[None, :] * np.sqrt(prod.astype(np.float64) / float(N)) / float(N)
     return e, np.full((B, m), float(N)), s, k_plus
+
+
+QV_GATE_ERROR_KEY_TAG = 0x51564745       # "QVGE": the Pauli errors of fbx_qv_noisy_trajectories
+
+
+def restate_qv_gate_errors(B, trajectories, L, gate_error, seed, first_item=0):
+    """The Pauli errors ``fbx_qv_noisy_trajectories`` inserts, restated on the host from its contract (include/fbx.h): ``uint8
+    [B, T, L]``, entry ``[b, t, l]`` = the Pauli index ``k = 4 a + c`` in 1..15 (a on q0, c on q1 of the gate's pair; 0 = I, 1 = X,
+    2 = Y, 3 = Z) that follows gate l of circuit b in trajectory t, or 0 for none.  ``gate_error``: a scalar, ``[B]`` or ``[B, L]``.
+    Trajectory t of the global circuit ``g = first_item + b`` owns the Philox4x32-10 blocks with counter (g low, g high, t, j) and key
+    (seed low ^ 0x51564745, seed high); block j serves gates 2 j (words x0, x1) and 2 j + 1 (words x2, x3); a gate errs iff
+    ``float(x_first) * 2^-32 < gate_error`` and then ``k = 1 + ((x_second * 15) >> 32)``.  ``quantum_volume.fold_gate_errors``
+    turns the indices of a trajectory into an ordinary circuit."""
+    B, T, L = int(B), int(trajectories), int(L)
+    seed, first_item = int(seed) & (2 ** 64 - 1), int(first_item)
+    if B < 0 or L < 0 or not 0 <= T < 2 ** 32 or first_item < 0:
+        raise ValueError("need B >= 0, L >= 0, 0 <= trajectories < 2^32 and first_item >= 0")
+    ge = np.asarray(gate_error, dtype=np.float64)
+    if ge.shape == (B,):
+        ge = ge[:, None]
+    elif ge.shape not in ((), (B, L)):
+        raise ValueError(f"gate_error must be a scalar, [B] = {(B,)} or [B, L] = {(B, L)}, not {ge.shape}")
+    ge = np.broadcast_to(ge, (B, L))
+    k0, k1 = (seed & 0xFFFFFFFF) ^ QV_GATE_ERROR_KEY_TAG, seed >> 32
+    out = np.zeros((B, T, L), dtype=np.uint8)
+    n_blocks = (L + 1) // 2
+    if not (B and T and L):
+        return out
+    ts = np.arange(T, dtype=np.uint64)[:, None]
+    js = np.arange(n_blocks, dtype=np.uint64)[None, :]
+    for b in range(B):
+        g = first_item + b
+        x0, x1, x2, x3 = (np.broadcast_to(w, (T, n_blocks)) for w in
+                          _philox4x32_10(np.uint64(g & 0xFFFFFFFF), np.uint64(g >> 32), ts, js, k0, k1))
+        first = np.stack([x0, x2], axis=-1).reshape(T, 2 * n_blocks)[:, :L]
+        second = np.stack([x1, x3], axis=-1).reshape(T, 2 * n_blocks)[:, :L]
+        errs = first.astype(np.float64) * 2.0 ** -32 < ge[b][None, :]
+        k = np.uint64(1) + ((second * np.uint64(15)) >> np.uint64(32))
+        out[b] = np.where(errs, k, np.uint64(0)).astype(np.uint8)
+    return out

@@ -136,7 +136,9 @@ int         fbx_release_workspace(void);
  *   "qv_wide_workspace_mib" (default 128, range [1, 65536]): fbx_qv_heavy_outputs_wide[_dev] runs its batch in chunks of as many
  *   circuits as fit this many MiB of device workspace (always at least one circuit).  Results do not depend on it.
  *   "sample_wide_workspace_mib" (default 128, range [1, 65536]): fbx_sample_bitstrings_wide[_dev] runs its batch in chunks of as
- *   many items as fit this many MiB of device workspace (always at least one item).  Results do not depend on it. */
+ *   many items as fit this many MiB of device workspace (always at least one item).  Results do not depend on it.
+ *   "qv_noisy_workspace_mib" (default 128, range [1, 65536]): fbx_qv_noisy_trajectories[_dev] with probs_mean_out runs its batch
+ *   in chunks of as many circuits as fit this many MiB of partial sums (always at least one circuit).  Results do not depend on it. */
 int         fbx_set_option(const char* name, double value);
 int         fbx_get_option(const char* name, double* value);
 
@@ -529,6 +531,45 @@ int fbx_qv_count_heavy_wide_dev(int n_qubits, int64_t B, int64_t n_shots, const 
  * Entries past the last pass: first gate L, mask 0.  Bad pairs: FBX_ERR_BAD_ARG. */
 int fbx_qv_wide_plan(int n_qubits, int64_t B, int L, const uint8_t* pairs, int tile_bits, int32_t* n_passes_out /* [B] */,
                      int32_t* pass_first_gate_out /* [B][L + 1] */, uint32_t* pass_local_mask_out /* [B][L] */);
+
+/* Quantum-volume circuits under gate noise: T stochastic Pauli-error trajectories of each of B circuits of one width
+ * (csrc/fbx_qvolume_noisy.hip).  pairs [B][L][2], gates [B][L][4][4] complex128, the bit order (qubit 0 = most
+ * significant) and W = max(1, 2^n / 64) are those of fbx_qv_heavy_outputs; heavy_mask [B][W] or NULL is that function's
+ * heavy_mask_out for the IDEAL circuits.  gate_error [B][L]: the error probability of every gate.
+ *
+ * THE MODEL.  After gate l of circuit b, in trajectory t, an error happens with probability gate_error[b][l]: one of the 15
+ * non-identity two-qubit Paulis on that gate's pair (q0, q1), chosen uniformly.  Pauli index k = 4 a + c in 1..15, a on q0 and c on
+ * q1, 0 = I, 1 = X, 2 = Y, 3 = Z.  Averaged over trajectories this is the channel rho -> (1 - 16 p / 15) rho + (16 p / 15) I/4 on
+ * the pair.  Only probabilities leave the kernel, so Y is applied as X Z (a global phase).
+ *
+ * THE STREAM (part of the contract: it is what a host check restates; the conventions are those of fbx_sample_bitstrings).
+ * Trajectory t of the circuit with the global id g = first_item + b owns the Philox4x32-10 blocks with counter (g low, g high, t, j)
+ * and key (seed low ^ 0x51564745, seed high).  Block j serves gates 2 j and 2 j + 1: words (x0, x1) for gate 2 j, (x2, x3) for gate
+ * 2 j + 1.  A gate errs iff (double) x_first * 2^-32 < gate_error; if it errs, k = 1 + (uint32)(((uint64) x_second * 15) >> 32).
+ * A trajectory depends on (seed, g, t) and its circuit's inputs only: not on B, T, the launch shape or the workgroup that ran it.
+ *
+ * Outputs, each may be NULL, not all of the first three.  probs_mean_out [B][2^n]: the mean over the T trajectories of the output
+ * distribution, summed in an order that depends on T alone (partial sums over 4 consecutive trajectories in the order of t, the
+ * partial sums in order, one division by T; no floating-point atomics), so an item repeats bit for bit under another B, another
+ * first_item offset, another launch shape or another "qv_noisy_workspace_mib" (fbx_set_option; default 128, range [1, 65536]: the
+ * batch runs in chunks of as many circuits as that many MiB of partial sums admit, at least one).  hprob_traj_out [B][T]: the
+ * weight trajectory t puts on the heavy set of heavy_mask (required for it), summed in one fixed order.  n_errors_out [B][T]: the
+ * number of Paulis inserted.  status_out [B]: 0 for a good item, 1 for a poisoned one.
+ *
+ * n_qubits 2..13 (others FBX_ERR_UNSUPPORTED, before any buffer is touched; a wider trajectory is an ordinary circuit for
+ * fbx_qv_heavy_outputs_wide once its Paulis are multiplied into its gates).  B == 0 or T == 0: nothing is done.  T >= 2^32, a
+ * negative size, first_item < 0, NULL pairs / gates / gate_error, hprob_traj_out without heavy_mask, no result asked for:
+ * FBX_ERR_BAD_ARG.  A poisoned item -- a non-finite gate entry, a pair that is not two different qubits below n_qubits (neither
+ * form checks pairs on the host), a gate_error outside [0, 1] or NaN -- gets status 1, NaN in probs_mean_out and hprob_traj_out
+ * and 0 in n_errors_out; its neighbours are untouched and the kernel never indexes outside the state.
+ * The _dev form enqueues on the calling thread's stream and does not synchronise (growing the workspace does, as everywhere). */
+int fbx_qv_noisy_trajectories(int n_qubits, int64_t B, int L, int64_t T, const uint8_t* pairs, const double* gates,
+                              const double* gate_error, const uint64_t* heavy_mask, uint64_t seed, int64_t first_item,
+                              double* probs_mean_out, double* hprob_traj_out, int32_t* n_errors_out, int32_t* status_out);
+int fbx_qv_noisy_trajectories_dev(int n_qubits, int64_t B, int L, int64_t T, const uint8_t* d_pairs, const double* d_gates,
+                                  const double* d_gate_error, const uint64_t* d_heavy_mask, uint64_t seed, int64_t first_item,
+                                  double* d_probs_mean_out, double* d_hprob_traj_out, int32_t* d_n_errors_out,
+                                  int32_t* d_status_out);
 
 /* ---------------------------------------------------------------- measured bitstrings from outcome distributions
  * The step between a distribution and a bit record (what a QVM's run-and-measure does for the reference): B items of one width,

@@ -435,7 +435,8 @@ int fbx_pauli_vector_dev(int n_qubits, int64_t B, const double* d_rho, double* d
  * on column q, coefs[s] its real coefficient (NULL = 1).  mean_out[s] = coef * mean of the +-1
  * products, var_out[s] = variance of that mean (coef^2 (1 - m^2) / n_shots), or the Beta(n+ + 1,
  * n- + 1) moments when beta_prior != 0 (use_beta_dist_unbiased_prior).  An all-zero mask is the
- * identity term: (coef, 0). */
+ * identity term: (coef, 0).  Only bit 0 of a byte of bits is read; any non-zero byte of obs_mask
+ * selects its column. */
 int fbx_shots_to_moments(int n_qubits, int64_t n_settings, int64_t n_shots, const uint8_t* bits,
                          const uint8_t* obs_mask, const double* coefs, int beta_prior,
                          double* mean_out, double* var_out);

@@ -1,4 +1,6 @@
-"""shots -> moments kernel vs the oracle and the reference's exact test values."""
+"""shots -> moments kernel vs the oracle and the reference's exact test values, on a few shapes.  The launcher's branches (every
+pipelined instantiation, the second trip of the grid-stride loops, misaligned device buffers) are covered by
+tests/test_shots_dispatch_gpu.py, not here."""
 import numpy as np
 import pytest
 
@@ -52,9 +54,12 @@ def test_large_stream_exact_counts(gpu):
 
 @pytest.mark.parametrize("n,shots", [(3, 1000), (3, 1003), (5, 1000), (6, 24), (7, 1048), (2, 1000), (8, 40), (9, 1000), (3, 20000)])
 def test_every_counting_path_is_exact(gpu, n, shots):
-    """The wave-per-setting and workgroup-per-setting forms, the 16-byte path (n | 16), the packed path of
-    n = 3, 5, 6, 7 (runs of 16 shots + byte-wise tail) and the byte-wise fallback (n = 9; records that are not
-    8-byte aligned, shots = 1003): means equal numpy's to the last bit for every setting."""
+    """Some counting paths, not every one: at S = 37 these shapes launch shots_pipe_kernel<2,2> and <8,1>,
+    shots_pipe_packed_kernel<3,1> and <5,1>, the wavefront form with the packed (n = 6, 7; n = 3 at shots = 1003, with the byte-wise
+    fallback on records that are not 8-byte aligned) and byte-wise (n = 9) counts, and the workgroup form's packed count (3 x 20000).
+    Means equal numpy's to the last bit for every setting.  Bits are 0 / 1, masks 0 / 1, every loop makes one trip; the other 16
+    pipelined instantiations, the vector count of the generic forms, second trips and misaligned bases are in
+    tests/test_shots_dispatch_gpu.py."""
     from fbx import _lib
     rs = np.random.RandomState(n * 1000 + shots)
     S = 37

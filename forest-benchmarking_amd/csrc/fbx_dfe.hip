@@ -14,93 +14,20 @@
 //                      FBX_TOMO_LANE_MIN_UNITS units on, a wavefront per unit below, the same bits either way.
 //   dfe_fidelity_kernel  dfe_item (fbx_sim_shared.hpp) with d = 2^n as a double, for the resident chain.
 // The walks cost about twenty integer instructions per gate and lane and read nothing but the gate words (from L2 / the scalar
-// cache); the simulation is bound by the Philox counting from a few dozen shots on, as in fbx_tomo_sim.hip.
+// cache); the simulation is bound by the Philox counting from a few dozen shots on, as in fbx_tomo_sim.hip.  The conjugation by one
+// gate, the walk and the host checks of gate words are in fbx_clifford_gates.hpp, shared with fbx_frames.hip.
 #include "fbx_sim_shared.hpp"
+#include "fbx_clifford_gates.hpp"
 
 namespace fbx {
 
 constexpr int DFE_THREADS = 256;
-constexpr int DFE_MAX_CLASSES = 16;
 constexpr uint32_t DFE_KEY_SETTINGS = 0x44464553u;      // "DFES": the Monte Carlo settings
 constexpr uint32_t DFE_KEY_SHOTS = 0x44464530u;         // "DFE0": the shots of the experiment
 constexpr uint32_t DFE_KEY_CALIBRATION = 0x44464543u;   // "DFEC": the shots of the calibration runs
 constexpr int DFE_MAX_ATTEMPTS = 256;
 
-__host__ __device__ __forceinline__ uint64_t dfe_valid_mask(int n) { return ~(uint64_t)0 >> (64 - n); }    // n in 1..64: no shift by 64
-
-__host__ __device__ __forceinline__ uint32_t dfe_inverse_opcode(uint32_t op) {
-    switch (op) {
-        case FBX_GATE_S: return FBX_GATE_SDG;
-        case FBX_GATE_SDG: return FBX_GATE_S;
-        case FBX_GATE_RX_PLUS: return FBX_GATE_RX_MINUS;
-        case FBX_GATE_RX_MINUS: return FBX_GATE_RX_PLUS;
-        case FBX_GATE_RY_PLUS: return FBX_GATE_RY_MINUS;
-        case FBX_GATE_RY_MINUS: return FBX_GATE_RY_PLUS;
-        case FBX_GATE_RZ_PLUS: return FBX_GATE_RZ_MINUS;
-        case FBX_GATE_RZ_MINUS: return FBX_GATE_RZ_PLUS;
-        default: return op;
-    }
-}
-
 #if defined(__HIPCC__)
-
-// P <- U P U^+ for the gate with opcode `op` on q0 (and q1); the table of include/fbx.h.  The word is wave-uniform.  Qubit indices are
-// reduced mod 64 and an unknown opcode does nothing: a word the caller did not validate gives an unspecified Pauli, nothing else.
-__device__ __forceinline__ void dfe_apply_gate(uint32_t op, uint32_t q0, uint32_t q1, uint64_t& x, uint64_t& z, uint32_t& sign) {
-    q0 &= 63u; q1 &= 63u;
-    const uint64_t xa = (x >> q0) & 1u, za = (z >> q0) & 1u;
-    uint64_t s = 0;
-    switch (op) {
-        case FBX_GATE_H:        s = xa & za;  x ^= (xa ^ za) << q0; z ^= (xa ^ za) << q0; break;
-        case FBX_GATE_S:
-        case FBX_GATE_RZ_PLUS:  s = xa & za;  z ^= xa << q0; break;
-        case FBX_GATE_SDG:
-        case FBX_GATE_RZ_MINUS: s = xa & ~za; z ^= xa << q0; break;
-        case FBX_GATE_X:        s = za; break;
-        case FBX_GATE_Y:        s = xa ^ za; break;
-        case FBX_GATE_Z:        s = xa; break;
-        case FBX_GATE_RX_PLUS:  s = za & ~xa; x ^= za << q0; break;
-        case FBX_GATE_RX_MINUS: s = za & xa;  x ^= za << q0; break;
-        case FBX_GATE_RY_PLUS:  s = xa & ~za; x ^= (xa ^ za) << q0; z ^= (xa ^ za) << q0; break;
-        case FBX_GATE_RY_MINUS: s = za & ~xa; x ^= (xa ^ za) << q0; z ^= (xa ^ za) << q0; break;
-        case FBX_GATE_CNOT: {
-            const uint64_t xb = (x >> q1) & 1u, zb = (z >> q1) & 1u;
-            s = xa & zb & ~(xb ^ za);
-            x ^= xa << q1; z ^= zb << q0;
-            break;
-        }
-        case FBX_GATE_CZ: {
-            const uint64_t xb = (x >> q1) & 1u, zb = (z >> q1) & 1u;
-            s = xa & xb & (za ^ zb);
-            z ^= (xb << q0) ^ (xa << q1);
-            break;
-        }
-        case FBX_GATE_SWAP: {
-            const uint64_t xb = (x >> q1) & 1u, zb = (z >> q1) & 1u;
-            x ^= ((xa ^ xb) << q0) | ((xa ^ xb) << q1);
-            z ^= ((za ^ zb) << q0) | ((za ^ zb) << q1);
-            break;
-        }
-        default: break;
-    }
-    sign ^= (uint32_t)(s & 1u);
-}
-
-// The whole circuit: inverse == 0 gives U P U^+ (gates in index order), 1 gives U^+ P U (backwards, each gate inverted).
-__device__ __forceinline__ void dfe_walk(const uint32_t* __restrict__ gates, long long G, int inverse, uint64_t& x, uint64_t& z,
-                                         uint32_t& sign) {
-    if (!inverse) {
-        for (long long g = 0; g < G; ++g) {
-            const uint32_t w = gates[g];
-            dfe_apply_gate(w & 0xFFu, (w >> 8) & 0xFFu, (w >> 16) & 0xFFu, x, z, sign);
-        }
-    } else {
-        for (long long g = G - 1; g >= 0; --g) {
-            const uint32_t w = gates[g];
-            dfe_apply_gate(dfe_inverse_opcode(w & 0xFFu), (w >> 8) & 0xFFu, (w >> 16) & 0xFFu, x, z, sign);
-        }
-    }
-}
 
 __global__ void __launch_bounds__(DFE_THREADS)
 conjugate_kernel(int n, long long G, const uint32_t* __restrict__ gates, int inverse, long long M, const uint64_t* __restrict__ x_in,
@@ -203,8 +130,6 @@ propagate_kernel(int n, long long G, const uint32_t* __restrict__ gates, const u
     for (int c = 0; c < K; ++c)
         if (c < k_classes) touches_out[i * k_classes + c] = cnt[c];
 }
-
-__device__ __forceinline__ bool dfe_bad_probability(double v) { return !(v >= 0.0 && v <= 1.0); }      // NaN included
 
 // status[b] = 1 when item b has a class error or a flip probability outside [0, 1] (NaN included), else 0; a wavefront per item
 __global__ void __launch_bounds__(DFE_THREADS)
@@ -322,29 +247,6 @@ dfe_fidelity_kernel(double d, int process, long long B, long long m, const doubl
 #endif
 
 // ------------------------------------------------------------------ host: argument checks
-static int dfe_check_width(const char* who, int n) {
-    if (n < 1 || n > 64) { set_error(std::string(who) + ": n_qubits must be 1..64"); return FBX_ERR_BAD_ARG; }
-    return FBX_OK;
-}
-
-// a circuit given by HOST words: every opcode known, every qubit index below n, q0 != q1 on a two-qubit gate, nothing above bit 23
-static int dfe_check_gates(const char* who, int n, int64_t G, const uint32_t* gates) {
-    for (int64_t g = 0; g < G; ++g) {
-        const uint32_t w = gates[g], op = w & 0xFFu, q0 = (w >> 8) & 0xFFu, q1 = (w >> 16) & 0xFFu;
-        const bool two = op >= FBX_GATE_CNOT;
-        const bool ok = op <= FBX_GATE_SWAP && (w >> 24) == 0 && q0 < (uint32_t)n && (two ? (q1 < (uint32_t)n && q1 != q0) : q1 == 0);
-        if (!ok) { set_error(std::string(who) + ": gate " + std::to_string(g) + " is not a valid gate word for this width"); return FBX_ERR_BAD_ARG; }
-    }
-    return FBX_OK;
-}
-
-static int dfe_check_circuit(const char* who, int n, int64_t G, const void* gates) {
-    FBX_TRY(dfe_check_width(who, n));
-    if (G < 0) { set_error(std::string(who) + ": negative gate count"); return FBX_ERR_BAD_ARG; }
-    if (G > 0 && !gates) { set_error(std::string(who) + ": NULL gates"); return FBX_ERR_BAD_ARG; }
-    return FBX_OK;
-}
-
 static int dfe_blocks(const char* who, int64_t items, unsigned* out) {
     const int64_t blocks = (items + DFE_THREADS - 1) / DFE_THREADS;
     if (blocks >= ((int64_t)1 << 31)) { set_error(std::string(who) + ": too many items for one launch"); return FBX_ERR_BAD_ARG; }
@@ -495,9 +397,7 @@ int fbx_dfe_propagate(int n_qubits, int64_t G, const uint32_t* gates, const uint
     (void)obs_sign;
     FBX_TRY(propagate_check(n_qubits, G, gates, K, m, in_x, in_z, in_minus, obs_x, obs_z, sigma_out, touches_out));
     FBX_TRY(dfe_check_gates("fbx_dfe_propagate", n_qubits, G, gates));
-    if (noise_class)
-        for (int64_t g = 0; g < G; ++g)
-            FBX_REQUIRE(noise_class[g] < K || noise_class[g] == FBX_DFE_NOISELESS, "fbx_dfe_propagate: a noise class is neither below K nor 255");
+    FBX_TRY(dfe_check_classes("fbx_dfe_propagate", K, G, noise_class));
     const uint64_t valid = dfe_valid_mask(n_qubits);
     for (int64_t k = 0; k < m; ++k)
         FBX_REQUIRE(((in_x[k] | in_z[k]) & valid) == valid, "fbx_dfe_propagate: an in-state label is I (every qubit is prepared in an X, Y or Z eigenstate)");

@@ -213,6 +213,11 @@ PROTOTYPES = {
                                   C.c_int, C.c_int, _dp, _dp, _ip],
     "fbx_dfe_simulate_fidelity_dev": [C.c_int, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, C.c_uint64, _i64,
                                       C.c_int, C.c_int, _vp, _vp, _vp],
+    "fbx_clifford_reference_sample": [C.c_int, _i64, _u32p, _u64p],
+    "fbx_clifford_reference_sample_dev": [C.c_int, _i64, _vp, _vp],
+    "fbx_clifford_sample_shots": [C.c_int, _i64, _u32p, _u8p, C.c_int, _u64p, _i64, _i64, _dp, _dp, C.c_uint64, _i64, _u8p, _u64p,
+                                  _ip],
+    "fbx_clifford_sample_shots_dev": [C.c_int, _i64, _vp, _vp, C.c_int, _vp, _i64, _i64, _vp, _vp, C.c_uint64, _i64, _vp, _vp, _vp],
 }
 
 

@@ -1,5 +1,5 @@
 """Clifford circuits on up to 64 qubits as lists of gate words, and signed Paulis as (x, z, sign) bit masks: the host mirror of
-csrc/fbx_dfe.hip in pure numpy (``uint64`` arrays, no device), written from the contract in include/fbx.h.
+csrc/fbx_dfe.hip and csrc/fbx_frames.hip in pure numpy (``uint64`` arrays, no device), written from the contract in include/fbx.h.
 
 A Pauli on n <= 64 qubits is two ``uint64`` masks and a sign bit -- bit q belongs to qubit q, per qubit (x, z) = 00 I, 10 X, 11 Y
 (the Hermitian Y), 01 Z, and the operator is (-1)^sign times the tensor product.  A gate is one ``uint32`` word: opcode in bits
@@ -295,3 +295,189 @@ def restate_dfe_settings(n, kind, n_terms, seed, gates):
     sign = (s.astype(np.uint64) + _popcount(minus & support)) & _U1
     return {"in_x": px, "in_z": pz | (~support & v), "in_minus": minus, "obs_x": ox, "obs_z": oz,
             "obs_sign": sign.astype(np.uint8)}
+
+
+# --------------------------------------------------------------------------------------------------
+# Shots of a noisy Clifford circuit (fbx_clifford_reference_sample, fbx_clifford_sample_shots), restated in numpy from the
+# contract in include/fbx.h: a reference outcome of the noiseless circuit and one Pauli frame per shot.
+# --------------------------------------------------------------------------------------------------
+FRAMES_KEY_TAG = 0x43465253         # "CFRS": the stream of fbx_clifford_sample_shots
+
+
+def _weight(v) -> int:
+    return bin(v).count("1")
+
+
+def _multiply(a, b):
+    """The product of two signed Hermitian Paulis ``(x, z, sign)`` as Python ints.  With P = i^(x.z) X^x Z^z the product is i^e
+    times the Pauli ``(x1 ^ x2, z1 ^ z2)``, e = x1.z1 + x2.z2 - x3.z3 + 2 z1.x2 mod 4; for commuting factors e is 0 or 2 and
+    its bit 1 is the sign (for anticommuting ones the result is not Hermitian and the sign returned is meaningless)."""
+    (x1, z1, r1), (x2, z2, r2) = a, b
+    x3, z3 = x1 ^ x2, z1 ^ z2
+    e = (_weight(x1 & z1) + _weight(x2 & z2) - _weight(x3 & z3) + 2 * _weight(z1 & x2)) % 4
+    return x3, z3, r1 ^ r2 ^ (e >> 1)
+
+
+def reference_sample(gates, n, device=None) -> int:
+    """One outcome of the noiseless circuit ``gates`` on |0..0> measured in Z on every qubit, as an int whose bit q is qubit q:
+    the outcome of non-zero probability with the smallest outcome index (qubit 0 is the most significant bit of the index) --
+    measure qubits 0, 1, .., n - 1 in this order and take every random result as 0.  ``device=None`` computes here (the stabilizer
+    tableau of Aaronson and Gottesman, rows as Python ints); any other value runs ``fbx_clifford_reference_sample`` on the
+    selected GPU."""
+    n = check_width(n)
+    words = encode_gates(gates, n)
+    if device is not None:
+        from . import _lib
+        import ctypes as C
+        out = np.zeros(1, dtype=np.uint64)
+        _lib.check(_lib.lib().fbx_clifford_reference_sample(n, words.size, _lib.ptr(words, C.c_uint32), _lib.ptr(out, C.c_uint64)))
+        return int(out[0])
+    one = _U1 << np.arange(n, dtype=np.uint64)
+    zero = np.zeros(n, dtype=np.uint64)
+    dx, dz, _ = conjugate_paulis(words, n, one, zero)                     # destabilizers U X_i U^+ (their signs are never read)
+    sx, sz, sr = conjugate_paulis(words, n, zero, one)                    # stabilizers U Z_i U^+
+    destab = [(int(x), int(z)) for x, z in zip(dx, dz)]
+    stab = [(int(x), int(z), int(r)) for x, z, r in zip(sx, sz, sr)]
+    x0 = 0
+    for a in range(n):
+        anti = [i for i in range(n) if (stab[i][0] >> a) & 1]
+        if anti:                                                          # random: taken as 0
+            p = anti[0]
+            pivot = stab[p]
+            for i in range(n):
+                if i == p:
+                    continue
+                if (stab[i][0] >> a) & 1:
+                    stab[i] = _multiply(stab[i], pivot)
+                if (destab[i][0] >> a) & 1:
+                    destab[i] = (destab[i][0] ^ pivot[0], destab[i][1] ^ pivot[1])
+            destab[p] = pivot[:2]
+            stab[p] = (0, 1 << a, 0)
+        else:                                                             # determined: the sign of a product of stabilizers
+            acc = (0, 0, 0)
+            for i in range(n):
+                if (destab[i][0] >> a) & 1:
+                    acc = _multiply(acc, stab[i])
+            x0 |= acc[2] << a
+    return x0
+
+
+def frame_noise(n, n_gates, class_error=None, noise_class=None, readout_flip=None):
+    """The noise arguments of one frame-sampling call, checked and broadcast: ``(B, K, class_error [B, K] or None, noise_class
+    [G] uint8 or None, readout_flip [B, n, 2] or None)``.  ``class_error``: a scalar (B = 1, K = 1) or ``[B, K]``;
+    ``noise_class``: one entry per gate, a class below K or 255 (K is ``class_error``'s, or one more than the largest class
+    without it); ``readout_flip``: ``[n, 2]`` for the whole batch or ``[B, n, 2]``.  B is 1 when nothing says otherwise."""
+    n = check_width(n)
+    ce = None
+    if class_error is not None:
+        ce = np.asarray(class_error, dtype=np.float64)
+        if ce.ndim == 0:
+            ce = ce.reshape(1, 1)
+        if ce.ndim != 2 or not 1 <= ce.shape[1] <= 16:
+            raise ValueError("class_error must be a scalar or [B, K] with K in 1..16")
+        ce = np.ascontiguousarray(ce)
+    cls = None
+    if noise_class is not None:
+        cls = np.ascontiguousarray(np.asarray(noise_class, dtype=np.uint8).ravel())
+        if cls.size != n_gates:
+            raise ValueError("noise_class needs one entry per gate")
+    if ce is not None:
+        K = ce.shape[1]
+    else:
+        used = cls[cls != NOISELESS] if cls is not None else np.zeros(0, dtype=np.uint8)
+        K = int(used.max()) + 1 if used.size else 1
+    if cls is not None and np.any((cls >= K) & (cls != NOISELESS)):
+        raise ValueError("a noise class is neither below K nor 255")
+    if K > 16:
+        raise ValueError("at most 16 noise classes")
+    flips = None
+    if readout_flip is not None:
+        flips = np.asarray(readout_flip, dtype=np.float64)
+        if flips.shape[-2:] != (n, 2) or flips.ndim not in (2, 3):
+            raise ValueError(f"readout_flip must be [n, 2] = {(n, 2)} or [B, n, 2], not {flips.shape}")
+    B = ce.shape[0] if ce is not None else (flips.shape[0] if flips is not None and flips.ndim == 3 else 1)
+    if flips is not None:
+        if flips.ndim == 3 and flips.shape[0] != B:
+            raise ValueError(f"readout_flip has {flips.shape[0]} items, class_error {B}")
+        flips = np.ascontiguousarray(np.broadcast_to(flips, (B, n, 2)))
+    return B, K, ce, cls, flips
+
+
+def _bad_probabilities(a):
+    return a is not None and not bool(np.all((a >= 0.0) & (a <= 1.0)))          # NaN included
+
+
+def _pauli_bits(k):
+    """Pauli index 0 I, 1 X, 2 Y, 3 Z -> (x bit, z bit) as uint64 arrays."""
+    return ((k == 1) | (k == 2)).astype(np.uint64), (k >> np.uint64(1)) & _U1
+
+
+def restate_frame_shots(gates, n, shots, class_error=None, noise_class=None, readout_flip=None, seed=0, first_item=0):
+    """The packed outcomes ``fbx_clifford_sample_shots`` writes, ``uint64 [B, shots]`` with bit q = qubit q, restated from THE
+    MODEL and THE STREAM of include/fbx.h on the Philox of ``fbx.synthetic``, vectorised over the shots of an item.  The noise
+    arguments are those of ``frame_noise``; item b is global item ``first_item + b``.  A poisoned item (a probability outside
+    [0, 1] or NaN) is a row of zeros, as on the device."""
+    from .synthetic import _philox4x32_10
+    n = check_width(n)
+    words = encode_gates(gates, n)
+    G = int(words.size)
+    B, K, ce, cls, flips = frame_noise(n, G, class_error, noise_class, readout_flip)
+    shots, seed, first_item = int(shots), int(seed) & (2 ** 64 - 1), int(first_item)
+    if not 0 <= shots < 2 ** 32 or first_item < 0:
+        raise ValueError("need 0 <= shots < 2^32 and first_item >= 0")
+    x0 = np.uint64(reference_sample(words, n))
+    v = valid_mask(n)
+    k0, k1 = (seed & 0xFFFFFFFF) ^ FRAMES_KEY_TAG, seed >> 32
+    s = np.arange(shots, dtype=np.uint64)
+    out = np.zeros((B, shots), dtype=np.uint64)
+    scale = 2.0 ** -32
+    for b in range(B):
+        if _bad_probabilities(ce[b] if ce is not None else None) or _bad_probabilities(flips[b] if flips is not None else None):
+            continue
+        g = first_item + b
+        g_lo, g_hi = np.uint64(g & 0xFFFFFFFF), np.uint64(g >> 32)
+
+        def block(j):
+            return _philox4x32_10(g_lo, g_hi, s, np.uint64(j), k0, k1)
+        w = block(0)
+        fx, fz = np.zeros(shots, dtype=np.uint64), (w[0] | (w[1] << np.uint64(32))) & v
+        sign = np.zeros(shots, dtype=np.uint8)
+        have, w = -1, None
+        for l in range(G):
+            word = int(words[l])
+            op, q0, q1 = word & 0xFF, (word >> 8) & 0xFF, (word >> 16) & 0xFF
+            fx, fz, _ = _apply_gate(op, q0, q1, fx, fz, sign)
+            c = 0 if cls is None else int(cls[l])
+            p = 0.0 if (ce is None or c == NOISELESS) else float(ce[b, c])
+            if p > 0.0:
+                if have != l >> 1:
+                    w, have = block(1 + (l >> 1)), l >> 1
+                first, second = (w[2], w[3]) if l & 1 else (w[0], w[1])
+                errs = (first.astype(np.float64) * scale < p).astype(np.uint64)
+                if op >= _FIRST_TWO_QUBIT:
+                    k = second >> np.uint64(28)
+                    ax, az = _pauli_bits(k >> np.uint64(2))
+                    cx, cz = _pauli_bits(k & np.uint64(3))
+                    fx = fx ^ (((ax << np.uint64(q0)) ^ (cx << np.uint64(q1))) * errs)
+                    fz = fz ^ (((az << np.uint64(q0)) ^ (cz << np.uint64(q1))) * errs)
+                else:
+                    px, pz = _pauli_bits(second >> np.uint64(30))
+                    fx = fx ^ ((px << np.uint64(q0)) * errs)
+                    fz = fz ^ ((pz << np.uint64(q0)) * errs)
+        outcome = (x0 ^ fx) & v
+        if flips is not None:
+            J = 1 + ((G + 1) >> 1)
+            for j in range(n):
+                if j & 3 == 0:
+                    w = block(J + (j >> 2))
+                d = _bit(outcome, j)
+                f = np.where(d == 1, flips[b, j, 1], flips[b, j, 0])
+                outcome = outcome ^ ((w[j & 3].astype(np.float64) * scale < f).astype(np.uint64) << np.uint64(j))
+        out[b] = outcome
+    return out
+
+
+def unpack_shots(words, n):
+    """Packed outcomes ``[..]`` uint64 (bit q = qubit q) -> bit records ``[.., n]`` uint8, first column = qubit 0."""
+    words = np.asarray(words, dtype=np.uint64)
+    return ((words[..., None] >> np.arange(check_width(n), dtype=np.uint64)) & _U1).astype(np.uint8)

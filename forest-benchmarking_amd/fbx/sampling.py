@@ -4,14 +4,17 @@ diagonal of a state -- and the ``[shots, n]`` bit arrays that ``qc.run`` returns
 package consumes.  The reference gets such arrays from a QVM; nothing of it is mirrored here.
 
 The stream is part of the C contract (include/fbx.h): a record depends on ``(seed, first_item + b, shot)`` and its item's inputs
-only, so a batch may be drawn in pieces, on any number of calls, and checked shot by shot on the host."""
+only, so a batch may be drawn in pieces, on any number of calls, and checked shot by shot on the host.
+
+``sample_clifford_circuit_batch`` needs no distribution: it draws the shots of a Clifford circuit with Pauli gate noise on up to 64
+qubits from the gate list itself (``fbx_clifford_sample_shots``, one Pauli frame per shot)."""
 import ctypes as C
 
 import numpy as np
 
 from .operator_tools.random_operators import _stream_seed
 
-__all__ = ["sample_bitstrings_batch", "sample_bitstrings_wide_batch"]
+__all__ = ["sample_bitstrings_batch", "sample_bitstrings_wide_batch", "sample_clifford_circuit_batch"]
 
 MIN_WIDTH, MAX_WIDTH = 1, 13
 MIN_WIDE_WIDTH, MAX_WIDE_WIDTH = 14, 26                  # fbx_sample_bitstrings_wide
@@ -105,3 +108,44 @@ def sample_bitstrings_wide_batch(probabilities, shots, depolarizing=None, readou
         return bits, status
     _raise_poisoned(status, first_item, "sample_bitstrings_wide_batch")
     return bits
+
+
+def sample_clifford_circuit_batch(gates, n_qubits, shots, class_error=None, noise_class=None, readout_flip=None, seed=None,
+                                  first_item=0, packed=False, return_status=False):
+    """The shots of a Clifford circuit with Pauli gate noise, 1..64 qubits, without a state vector: ``gates`` (``(name, qubits)``
+    tuples or gate words, ``clifford_circuit.encode_gates``) on |0..0>, every qubit measured in Z -> ``[B, shots, n]`` uint8 bit
+    records, first column = qubit 0, or with ``packed=True`` ``[B, shots]`` uint64 words, bit q = qubit q.
+
+    The B items share the circuit and differ in noise (``clifford_circuit.frame_noise``): ``class_error`` a scalar or ``[B, K]``,
+    the depolarizing probability of every gate of class c -- with that probability a Pauli drawn uniformly from all 4 or 16 on the
+    gate's qubits follows the gate, the model of ``direct_fidelity_estimation.simulate_dfe_batch``; ``noise_class`` one class per
+    gate or 255 for a gate without noise (default: all class 0); ``readout_flip`` ``[n, 2]`` or ``[B, n, 2]`` as in
+    ``sample_bitstrings_batch``.  ``seed=None`` takes a fresh key; item b is global item ``first_item + b`` of the stream, which
+    ``clifford_circuit.restate_frame_shots`` restates on the host bit for bit.
+
+    An item with a probability outside [0, 1] (or NaN) raises ``ValueError``; with ``return_status=True`` nothing is raised and
+    ``(records, status [B] int32)`` comes back, status 1 and a record of zeros for such an item."""
+    from . import _lib
+    from . import clifford_circuit as cc
+    n = cc.check_width(n_qubits)
+    words = cc.encode_gates(gates, n)
+    B, K, ce, cls, flips = cc.frame_noise(n, words.size, class_error, noise_class, readout_flip)
+    shots, first_item = int(shots), int(first_item)
+    if shots < 0 or first_item < 0:
+        raise ValueError("need shots >= 0 and first_item >= 0")
+    lib = _lib.lib()
+    reference = np.zeros(1, dtype=np.uint64)
+    _lib.check(lib.fbx_clifford_reference_sample(n, words.size, _lib.ptr(words, C.c_uint32), _lib.ptr(reference, C.c_uint64)))
+    out = np.zeros((B, shots) if packed else (B, shots, n), dtype=np.uint64 if packed else np.uint8)
+    status = np.zeros(B, dtype=np.int32)
+    _lib.check(lib.fbx_clifford_sample_shots(n, words.size, _lib.ptr(words, C.c_uint32), _lib.ptr(cls, C.c_uint8), K,
+                                             _lib.ptr(reference, C.c_uint64), B, shots, _lib.dptr(ce), _lib.dptr(flips),
+                                             _stream_seed(seed), first_item, None if packed else _lib.ptr(out, C.c_uint8),
+                                             _lib.ptr(out, C.c_uint64) if packed else None, _lib.iptr(status)))
+    if return_status:
+        return out, status
+    bad = np.flatnonzero(status)
+    if bad.size:
+        raise ValueError(f"sample_clifford_circuit_batch: item {int(bad[0])} (global id {first_item + int(bad[0])}) cannot be "
+                         f"sampled: a class_error or readout_flip value outside [0, 1] ({bad.size} such item(s) in the batch)")
+    return out

@@ -1061,6 +1061,65 @@ int fbx_dfe_simulate_fidelity_dev(int n_qubits, int64_t m, int K, const int8_t* 
                                   int64_t first_item, int kind, int calibrate, double* d_fidelity_out, double* d_err_out,
                                   int32_t* d_status_out);
 
+/* ---------------------------------------------------------------- shots of a noisy Clifford circuit: Pauli frames, 1..64 qubits
+ * Measured bitstrings of a Clifford circuit with Pauli noise without a state vector (csrc/fbx_frames.hip): the
+ * experiment half of entangled_states.py (create_ghz_program, create_graph_state, measure_graph_state are Clifford circuits) at
+ * any width up to 64.  The circuit is gates[G] (the gate words above) on |0..0>, followed by a Z measurement of every qubit.
+ *
+ * fbx_clifford_reference_sample: reference_out[0] = x0, one outcome of the NOISELESS circuit, bit q = qubit q: the outcome of
+ * non-zero probability with the smallest outcome index, qubit 0 being the most significant bit of the index as everywhere in this
+ * library -- equivalently, what comes out when the qubits 0, 1, .., n - 1 are measured in this order and every random result is
+ * taken as 0.  It runs on the device, one wavefront: a stabilizer tableau with one generator pair per lane.  n_qubits outside
+ * 1..64, G < 0, NULL gates with G > 0, NULL reference_out: FBX_ERR_BAD_ARG.  G == 0 gives 0.  The host form validates the gate
+ * words; the _dev form enqueues on the calling thread's stream and does not synchronise. */
+int fbx_clifford_reference_sample(int n_qubits, int64_t G, const uint32_t* gates, uint64_t* reference_out);
+int fbx_clifford_reference_sample_dev(int n_qubits, int64_t G, const uint32_t* d_gates, uint64_t* d_reference_out);
+
+/* fbx_clifford_sample_shots: B items share the circuit and differ in noise; n_shots shots each, one lane per shot.
+ * noise_class [G] uint8: a class < K, 1 <= K <= 16, or FBX_DFE_NOISELESS; NULL = every gate is class 0.  class_error [B][K] or NULL
+ * (= 0).  readout_flip [B][n][2] or NULL (= no flips) with the meaning of fbx_sample_bitstrings: [j][0] = P(read 1 | drawn 0),
+ * [j][1] = P(read 0 | drawn 1).  reference: one uint64, the output of fbx_clifford_reference_sample for the same circuit (a DEVICE
+ * pointer in the _dev form: the chain reference -> shots needs no synchronisation).  Outputs, either may be NULL, not both:
+ * bits_out [B][n_shots][n] uint8 0 / 1, first column = qubit 0 (the records fbx_shots_to_moments and fbx_bit_histogram read);
+ * words_out [B][n_shots] uint64, the same outcome packed, bit q = qubit q.  status_out [B] or NULL: 0 good, 1 poisoned.
+ *
+ * THE MODEL.  After a gate of class c, item b applies the depolarizing channel of fbx_dfe_simulate to that gate's qubits: with
+ * probability class_error[b][c] a Pauli drawn uniformly from ALL 4 (one-qubit gate) or 16 (two-qubit gate) Paulis, the identity
+ * included, is applied -- rho -> (1 - p) rho + p tr_g(rho) (x) I / d_g, which scales a Pauli that is not the identity there by
+ * 1 - p, so the shots of this function have the means of fbx_dfe_simulate.  A shot carries a Pauli frame (fx, fz), its difference
+ * from the reference run.  It starts as fx = 0, fz = a uniformly random mask: Z on |0> is a stabilizer, so this changes nothing
+ * physical, and it is what spreads the shots over the whole support of the outcome distribution.  Every gate conjugates the frame
+ * with the table above (signs are not tracked: a frame is a Pauli up to phase), an error XORs its Pauli in, and the outcome is
+ * reference ^ fx.  Readout flips follow.  The shots are exact samples of the noisy circuit.
+ *
+ * THE STREAM (part of the contract: it is what a host check restates).  Shot s of the global item g = first_item + b owns the
+ * Philox4x32-10 blocks with counter (g low, g high, s, j) and key (seed low ^ 0x43465253, seed high), words x0 .. x3 each.
+ *   Block 0:             fz = (x0 | (uint64) x1 << 32) & valid, valid = the mask of the n low bits.
+ *   Block 1 + (l >> 1):  gate l, words (x0, x1) for even l and (x2, x3) for odd l.  A gate whose class is not FBX_DFE_NOISELESS errs
+ *                        iff (double) x_first * 2^-32 < class_error[b][c]; the Pauli index is then x_second >> 30 for a one-qubit
+ *                        gate and x_second >> 28 = 4 a + c for a two-qubit gate, a on q0 and c on q1; 0 I, 1 X, 2 Y, 3 Z.
+ *   Readout:             with J = 1 + ((G + 1) >> 1), column j reads word j & 3 of block J + (j >> 2) and flips iff
+ *                        (double) x * 2^-32 < readout_flip[b][j][d], d the drawn bit.
+ * Only the blocks that are needed are computed: a gate block when one of its gates has a class with a non-zero error probability,
+ * the readout blocks when readout_flip is given.  A record depends on (seed, g, s), the circuit and its item's noise only: not on
+ * B, n_shots or the launch shape -- a call of B' items from first_item + k repeats items k .. k + B' - 1, and a call of fewer shots
+ * repeats the first shots.
+ *
+ * n_qubits outside 1..64, G >= 2^31, n_shots >= 2^32, K outside 1..16, a negative size, first_item < 0, NULL gates with G > 0,
+ * NULL reference, both outputs NULL, B * ceil(n_shots / 256) >= 2^31: FBX_ERR_BAD_ARG before any buffer is touched.  B == 0 or
+ * n_shots == 0: nothing is done.  A poisoned item -- a class error or a flip outside [0, 1], or NaN -- gets status 1 and a record
+ * of zeros; its neighbours are untouched.  The host form also refuses an invalid gate word or class; the _dev form takes them as
+ * validated (see above: no access depends on a word's content).  The _dev form enqueues on the calling thread's stream and does
+ * not synchronise. */
+int fbx_clifford_sample_shots(int n_qubits, int64_t G, const uint32_t* gates, const uint8_t* noise_class, int K,
+                              const uint64_t* reference, int64_t B, int64_t n_shots, const double* class_error,
+                              const double* readout_flip, uint64_t seed, int64_t first_item, uint8_t* bits_out, uint64_t* words_out,
+                              int32_t* status_out);
+int fbx_clifford_sample_shots_dev(int n_qubits, int64_t G, const uint32_t* d_gates, const uint8_t* d_noise_class, int K,
+                                  const uint64_t* d_reference, int64_t B, int64_t n_shots, const double* d_class_error,
+                                  const double* d_readout_flip, uint64_t seed, int64_t first_item, uint8_t* d_bits_out,
+                                  uint64_t* d_words_out, int32_t* d_status_out);
+
 /* out[b] = op(a[b]) diag(scale[b]) op(b[b]) for stacks of N x N complex matrices, N in 1..1024: op = the matrix itself
  * (conj_t = 0) or its conjugate transpose (conj_t = 1); scale is [B][N] real or NULL.  The products around fbx_eigh:
  * V f(lambda) V^H (sqrtm_psd, calculational.py:77-91), sqrt(rho) sigma sqrt(rho) (fidelity, distance_measures.py:64-84). */

@@ -13,14 +13,12 @@
 // shots (the chip is full without cutting a setting); below, a WAVEFRONT takes a unit, lane l counts the Philox blocks l, l + 64,
 // ... and the 64 partial counts are summed (integers, exactly, in double).  A value depends on (seed, item id, setting, mean, shots)
 // only: both splits evaluate the mean with the same code in the same order and count the same words.
-#include "fbx_sim_shared.hpp"      // tomo_count and the unit threshold, shared with fbx_dfe.hip
+#include "fbx_sim_shared.hpp"      // tomo_count and the unit threshold, shared with fbx_dfe.hip; tomo_mean, with fbx_tomo_sim_grouped.hip
 
 namespace fbx {
 
 constexpr int TOMO_THREADS = 256;
 constexpr uint32_t TOMO_KEY_TAG = 0x544F4D4Fu;   // "TOMO": keeps the stream apart from fbx_sample_bitstrings under one seed
-
-__device__ __forceinline__ bool tomo_bad_probability(double v) { return !(v >= 0.0 && v <= 1.0); }      // NaN included
 
 // status[b] = 1 when item b has a non-finite truth entry or a flip probability outside [0, 1] (NaN included), else 0
 __global__ void __launch_bounds__(TOMO_THREADS)
@@ -40,66 +38,12 @@ tomo_poison_kernel(long long B, int truth_len, int flip_len, const double* __res
     if (lane == 0) status[b] = any ? 1 : 0;
 }
 
-// tr[P rho] of the Pauli with index `pidx` (base-4 digits, qubit 0 most significant): P = i^ny X^x Z^z, P |c> = i^ny (-1)^{|c & z|} |c ^ x>
-__device__ __forceinline__ double tomo_trace_state(const cplx* __restrict__ rho, int n, int pidx) {
-    int x = 0, z = 0, ny = 0;
-    for (int t = 0; t < n; ++t) {
-        const int code = (pidx >> (2 * t)) & 3;
-        x |= ((code == 1) | (code == 2)) << t; z |= ((code == 2) | (code == 3)) << t; ny += code == 2;
-    }
-    const int d = 1 << n;
-    double acc = 0.0;
-    for (int c = 0; c < d; ++c) {
-        const cplx v = rho[c * d + (c ^ x)];
-        double term = (ny & 1) ? v.im : v.re;               // Re(i^ny v): re, -im, -re, im
-        if (((ny + 1) >> 1) & 1) term = -term;
-        acc += (__popc(c & z) & 1) ? -term : term;
-    }
-    return acc;
-}
-
-// tr[P Lambda(rho_s)] = sum_j R[P][j] c_j(s): row `pidx` of the transfer matrix against the state's Bloch coefficients
-__device__ __forceinline__ double tomo_trace_process(const double* __restrict__ R, const double* __restrict__ ct, int D, int pidx) {
-    const double* row = R + (size_t)pidx * D;
-    double acc = 0.0;
-    for (int j = 0; j < D; ++j) acc = fma(row[j], ct[j], acc);
-    return acc;
-}
-
-// The mean of the measured +-1 product of the setting with the packed (state, Pauli) `sp` (include/fbx.h): over the subsets T
-// of the Pauli's support, prod_{S \ T} a_j prod_T b_j tr[P_T .]; without flips a = 0 and b = 1, and only T = S is left.
-__device__ double tomo_mean(const DesignDev& des, const double* __restrict__ truth, const double* __restrict__ flip, uint32_t sp) {
-    const int n = des.n, pidx = (int)(sp & 0xFFFFu), s = (int)(sp >> 16);
-    int support = 0;
-    double a[5], bb[5];
-#pragma unroll
-    for (int t = 0; t < 5; ++t) {                             // (fixed bounds: a and bb stay in registers)
-        if (t >= n) { a[t] = 0.0; bb[t] = 1.0; continue; }
-        if ((pidx >> (2 * t)) & 3) support |= 1 << t;
-        const int q = n - 1 - t;                              // digit t belongs to qubit n - 1 - t
-        const double f0 = flip ? flip[2 * q] : 0.0, f1 = flip ? flip[2 * q + 1] : 0.0;
-        a[t] = f1 - f0; bb[t] = 1.0 - f0 - f1;
-    }
-    if (support == 0) return 1.0;
-    const double* ct = des.Ct + (size_t)s * des.D;
-    double mu = 0.0;
-    for (int T = support;; T = (T - 1) & support) {
-        double w = 1.0;
-        int keep = 0;
-#pragma unroll
-        for (int t = 0; t < 5; ++t) {
-            if (!((support >> t) & 1)) continue;
-            if ((T >> t) & 1) { w *= bb[t]; keep |= 3 << (2 * t); } else { w *= a[t]; }
-        }
-        if (w != 0.0) {
-            const double tr = T == 0 ? 1.0
-                            : des.kind == FBX_KIND_PROCESS ? tomo_trace_process(truth, ct, des.D, pidx & keep)
-                                                           : tomo_trace_state(reinterpret_cast<const cplx*>(truth), n, pidx & keep);
-            mu = fma(w, tr, mu);
-        }
-        if (T == 0) break;
-    }
-    return mu;
+int tomo_poison_launch(int64_t B, int truth_len, int flip_len, const double* d_truth, const double* d_flips, int32_t* d_status) {
+    constexpr int WAVES = TOMO_THREADS / 64;
+    hipLaunchKernelGGL(tomo_poison_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(TOMO_THREADS), 0, stream(), (long long)B,
+                       truth_len, flip_len, d_truth, d_flips, d_status);
+    FBX_HIP(hipGetLastError());
+    return FBX_OK;
 }
 
 // unit u = (item u / m, grouped setting u % m); LANE: a lane per unit, else a wavefront per unit
@@ -190,9 +134,7 @@ int fbx_tomo_simulate_dev(const fbx_design* design, int64_t B, const double* d_t
     int32_t* status = d_status_out;
     if (!status) { FBX_TRY(scratch.alloc(sizeof(int32_t) * (size_t)B)); status = scratch.as<int32_t>(); }
     constexpr int WAVES = TOMO_THREADS / 64;
-    hipLaunchKernelGGL(tomo_poison_kernel, dim3((unsigned)((B + WAVES - 1) / WAVES)), dim3(TOMO_THREADS), 0, stream(), (long long)B,
-                       truth_len, 2 * des.n, d_truth, d_readout_flip, status);
-    FBX_HIP(hipGetLastError());
+    FBX_TRY(tomo_poison_launch(B, truth_len, 2 * des.n, d_truth, d_readout_flip, status));
     const int64_t units = B * des.m;
     if (units >= FBX_TOMO_LANE_MIN_UNITS) {
         const int64_t blocks = (units + TOMO_THREADS - 1) / TOMO_THREADS;

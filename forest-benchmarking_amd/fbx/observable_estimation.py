@@ -220,6 +220,96 @@ class ExperimentSetting:
         return cls(TensorProductState.from_str(prepared), PauliTerm.from_compact_str(measured))
 
 
+class ObservablesExperiment:
+    """Settings to estimate on one program, as a list of GROUPS of :class:`ExperimentSetting` (observable_estimation.py:234-353):
+    the settings of a group are estimated from the same shots.  A flat list of settings becomes groups of one.  The container
+    behaves as the list of its groups; it does not group by itself (:func:`group_settings` does).  ``program`` is kept as an
+    opaque attribute (a pyquil ``Program``, its text, or ``None``)."""
+
+    def __init__(self, settings, program=None):
+        settings = list(settings)
+        if settings and isinstance(settings[0], ExperimentSetting):
+            settings = [[s] for s in settings]
+        self._settings = [list(g) for g in settings]
+        self.program = program
+
+    def __len__(self):
+        return len(self._settings)
+
+    def __getitem__(self, item):
+        return self._settings[item]
+
+    def __setitem__(self, key, value):
+        self._settings[key] = value
+
+    def __delitem__(self, key):
+        del self._settings[key]
+
+    def __iter__(self):
+        return iter(self._settings)
+
+    def __reversed__(self):
+        return reversed(self._settings)
+
+    def __contains__(self, item):
+        return item in self._settings
+
+    def append(self, group):
+        self._settings.append(group if isinstance(group, list) else [group])
+
+    def extend(self, groups):
+        self._settings.extend(groups)
+
+    def insert(self, index, group):
+        self._settings.insert(index, group)
+
+    def pop(self, index=-1):
+        return self._settings.pop(index)
+
+    def remove(self, group):
+        self._settings.remove(group)
+
+    def count(self, group):
+        return self._settings.count(group)
+
+    def index(self, group, *bounds):
+        return self._settings.index(group, *bounds)
+
+    def reverse(self):
+        self._settings.reverse()
+
+    def sort(self, key=None, reverse=False):
+        self._settings.sort(key=key, reverse=reverse)
+
+    def setting_strings(self):
+        for i, group in enumerate(self._settings):
+            yield f"{i}: " + ", ".join(str(s) for s in group)
+
+    def settings_string(self, abbrev_after=None):
+        lines = list(self.setting_strings())
+        if abbrev_after is not None and len(lines) > abbrev_after:
+            head = abbrev_after // 2
+            tail = abbrev_after - head
+            lines = (lines[:head] + [f"... {len(lines) - abbrev_after} not shown ...", "... use e.settings_string() for all ..."]
+                     + lines[len(lines) - tail:])
+        return "\n".join(lines)
+
+    def _program_text(self):
+        return self.program.out() if hasattr(self.program, "out") else self.program
+
+    def __str__(self):
+        text = self._program_text()
+        head = "; ".join(str(text).splitlines()) if text is not None else ""
+        return head + "\n" + self.settings_string(abbrev_after=20)
+
+    def serializable(self):
+        return {"type": "ObservablesExperiment", "settings": [[str(s) for s in g] for g in self._settings],
+                "program": self._program_text()}
+
+    def __eq__(self, other):
+        return isinstance(other, ObservablesExperiment) and self.serializable() == other.serializable()
+
+
 _RESULT_FIELDS = ("setting", "expectation", "total_counts", "std_err", "raw_expectation", "raw_std_err",
                   "calibration_expectation", "calibration_std_err", "calibration_counts")
 
@@ -271,7 +361,7 @@ class OperatorEncoder(json.JSONEncoder):
     def default(self, o):
         if isinstance(o, ExperimentSetting):
             return str(o)
-        if isinstance(o, ExperimentResult):
+        if isinstance(o, (ExperimentResult, ObservablesExperiment)):
             return o.serializable()
         if isinstance(o, (np.integer,)):
             return int(o)
@@ -282,8 +372,8 @@ class OperatorEncoder(json.JSONEncoder):
 
 def to_json(fn, obj):
     """observable_estimation.py:367-373: same file layout as the reference (indent 2, settings as
-    ``'X+_0 * Z-_1→(1+0j)*X0Z1'`` strings), for ExperimentSetting / ExperimentResult objects and
-    lists of them."""
+    ``'X+_0 * Z-_1→(1+0j)*X0Z1'`` strings), for ExperimentSetting / ExperimentResult / ObservablesExperiment objects
+    and lists of them."""
     with open(fn, 'w') as f:
         json.dump(obj, f, cls=OperatorEncoder, indent=2, ensure_ascii=False)
     return fn
@@ -294,6 +384,8 @@ def _result_object_hook(obj):
         fields = {k: v for k, v in obj.items() if k != 'type'}
         fields['setting'] = ExperimentSetting.from_str(fields['setting'])
         return ExperimentResult(**fields)
+    if obj.get('type') == 'ObservablesExperiment':
+        return ObservablesExperiment([[ExperimentSetting.from_str(t) for t in g] for g in obj['settings']], program=obj.get('program'))
     return obj
 
 
@@ -303,6 +395,107 @@ def read_json(fn):
     ExperimentResult objects, ready for the estimators; files written by the reference parse too."""
     with open(fn) as f:
         return json.load(f, object_hook=_result_object_hook)
+
+
+# ==================================================================================================
+# grouping of settings by a shared tensor-product basis (observable_estimation.py:470-692)
+# ==================================================================================================
+def _max_weight_operator(ops) -> Union[None, PauliTerm]:
+    """The Pauli term (coefficient 1) that has, on every qubit, the one non-identity factor the given terms use there: XI and IZ
+    give XZ.  ``None`` when two terms use different factors on a qubit (XI and ZI): they are not diagonal in one basis."""
+    seen = {}
+    for term in ops:
+        for qubit, op in term:
+            if seen.setdefault(qubit, op) != op:
+                return None
+    return PauliTerm(seen)
+
+
+def _max_weight_state(states) -> Union[None, TensorProductState]:
+    """The product state with, on every qubit, the one preparation the given states use there; ``None`` when two of them
+    prepare a qubit differently."""
+    seen = {}
+    for state in states:
+        for one in state.states:
+            if seen.setdefault(one.qubit, one) != one:
+                return None
+    return TensorProductState(seen.values())
+
+
+def _ungrouped(obs_expt):
+    out = []
+    for group in obs_expt:
+        assert len(group) == 1, 'already grouped?'
+        out.append(group[0])
+    return out
+
+
+def _max_tpb_overlap(obs_expt: ObservablesExperiment):
+    """The greedy buckets: a dict, in insertion order, from a basis (an ``ExperimentSetting`` of the bucket's joint input state
+    and joint observable) to the settings that are diagonal in it.  Every setting goes to the FIRST bucket it fits; when it makes
+    that bucket's basis grow, the bucket is taken out and put back under the new basis -- at the END of the order in which later
+    settings look."""
+    buckets = {}
+    for setting in _ungrouped(obs_expt):
+        for basis, members in buckets.items():
+            trial = members + [setting]
+            joint_in = _max_weight_state(s.in_state for s in trial)
+            joint_out = _max_weight_operator(s.observable for s in trial)
+            if joint_in is None or joint_out is None:
+                continue
+            if len(joint_in) > len(basis.in_state) or len(joint_out) > len(basis.observable):
+                del buckets[basis]
+                buckets[ExperimentSetting(joint_in, joint_out)] = trial
+            else:
+                buckets[basis] = trial
+            break
+        else:
+            buckets[setting] = [setting]
+    return buckets
+
+
+def group_settings_greedy(obs_expt: ObservablesExperiment) -> ObservablesExperiment:
+    """The settings of an ungrouped experiment in the buckets of :func:`_max_tpb_overlap`, in the buckets' final order."""
+    return ObservablesExperiment(list(_max_tpb_overlap(obs_expt).values()), program=obs_expt.program)
+
+
+def construct_tpb_graph(obs_expt: ObservablesExperiment):
+    """networkx graph of the distinct settings (node attribute ``count`` = how often a setting occurs) with an edge between two
+    settings that share an input state and a tensor-product basis."""
+    import itertools
+    import networkx as nx
+    graph = nx.Graph()
+    settings = _ungrouped(obs_expt)
+    for s in settings:
+        if s in graph:
+            graph.nodes[s]['count'] += 1
+        else:
+            graph.add_node(s, count=1)
+    for a, b in itertools.combinations(settings, 2):
+        if a == b:
+            continue
+        if _max_weight_state([a.in_state, b.in_state]) is not None and \
+                _max_weight_operator([a.observable, b.observable]) is not None:
+            graph.add_edge(a, b)
+    return graph
+
+
+def group_settings_clique_removal(experiment: ObservablesExperiment) -> ObservablesExperiment:
+    """Groups = the cliques networkx's ``clique_removal`` finds in :func:`construct_tpb_graph`, every setting repeated as often
+    as it occurs."""
+    from networkx.algorithms.approximation.clique import clique_removal
+    graph = construct_tpb_graph(experiment)
+    _, cliques = clique_removal(graph)
+    groups = [[s for s in clique for _ in range(graph.nodes[s]['count'])] for clique in cliques]
+    return ObservablesExperiment(groups, program=experiment.program)
+
+
+def group_settings(obs_expt: ObservablesExperiment, method: str = 'greedy') -> ObservablesExperiment:
+    """The same settings, grouped so that the members of a group share an input state and are diagonal in one tensor-product
+    basis (one run estimates them all): ``method`` 'greedy' (first bucket that fits) or 'clique-removal' (networkx)."""
+    methods = {'greedy': group_settings_greedy, 'clique-removal': group_settings_clique_removal}
+    assert method in methods, f"'method' should be one of {list(methods)}."
+    return methods[method](obs_expt)
 
 
 def get_results_by_qubit_groups(results: Iterable, qubit_groups: Sequence[Sequence[int]]) -> Dict[Tuple[int, ...], list]:

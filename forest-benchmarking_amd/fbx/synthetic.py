@@ -356,7 +356,54 @@ def restate_dfe_counts(exact, coefs, shots, seed, first_item=0, key_tag=DFE_KEY_
     return e, np.full((B, m), float(N)), s, k_plus
 
 
-QV_GATE_ERROR_KEY_TAG = 0x51564745       # "QVGE": the Pauli errors of fbx_qv_noisy_trajectories
+TOMO_GROUPED_KEY_TAG = 0x544F4D47        # "TOMG": the shots of fbx_tomo_simulate_grouped
+
+
+def restate_grouped_tomography_counts(probabilities, grouping_or_group_of, paulis, coefs, shots, seed, first_item=0):
+    """Steps 3-5 of the contract of ``fbx_tomo_simulate_grouped`` (include/fbx.h) restated on the host from the distributions it
+    reports: ``probabilities [B, G, 2^n]`` (the ``return_probabilities`` output), the grouping (a ``design.Grouping`` or its
+    ``group_of [m]``), ``paulis [m, n]`` and ``coefs [m]`` of the design.  Per (item, group): c = cumsum(max(p, 0)) in outcome
+    order, thr_o = floor(c_o / c_last 2^32) for every outcome but the last; shot s reads word ``s & 3`` of the Philox4x32-10 block
+    with counter (gid low, gid high, group, s >> 2) and key (seed low ^ 0x544F4D47, seed high), gid = first_item + item; its
+    outcome is the number of thresholds <= the word.  Member k counts k+ = the shots whose outcome has even parity on its support
+    (bit t of an outcome = qubit n - 1 - t).  Returns ``(expectations [B, m], total_counts [B, m], std_errs [B, m], hist [B, G,
+    2^n] int64)`` with the integer formulas of ``restate_tomography_counts``."""
+    p = np.asarray(probabilities, dtype=np.float64)
+    group_of = np.asarray(getattr(grouping_or_group_of, "group_of", grouping_or_group_of)).astype(np.int64)
+    paulis = np.asarray(paulis)
+    m, n = paulis.shape
+    coefs = np.broadcast_to(np.asarray(coefs, dtype=np.float64), (m,))
+    N, seed, first_item = int(shots), int(seed) & (2 ** 64 - 1), int(first_item)
+    if p.ndim != 3 or p.shape[2] != 1 << n or group_of.shape != (m,) or group_of.min() < 0 or group_of.max() >= p.shape[1]:
+        raise ValueError("need probabilities [B, G, 2^n], paulis [m, n] and group ids [m] in [0, G)")
+    if not 1 <= N < 2 ** 32 or first_item < 0:
+        raise ValueError("need 1 <= shots < 2^32 and first_item >= 0")
+    B, G, d = p.shape
+    c = np.cumsum(np.where(p < 0.0, 0.0, p), axis=2)                    # one addition per outcome, in outcome order
+    if not np.all((c[:, :, -1] > 0.0) & np.isfinite(c[:, :, -1])):
+        raise ValueError("a distribution whose clamped sum is not a positive finite number (a poisoned item) cannot be restated")
+    thr = np.floor(c[:, :, :-1] / c[:, :, -1:] * 2.0 ** 32).astype(np.uint64)
+    k0, k1 = (seed & 0xFFFFFFFF) ^ TOMO_GROUPED_KEY_TAG, seed >> 32
+    blocks = np.arange((N + 3) // 4, dtype=np.uint64)
+    hist = np.zeros((B, G, d), dtype=np.int64)
+    for b in range(B):
+        gid = first_item + b
+        for g in range(G):
+            words = _philox4x32_10(np.uint64(gid & 0xFFFFFFFF), np.uint64(gid >> 32), np.uint64(g), blocks, k0, k1)
+            w = np.stack(np.broadcast_arrays(*words), axis=1).reshape(-1)[:N]                 # shot s = word s & 3 of block s >> 2
+            hist[b, g] = np.bincount(np.searchsorted(thr[b, g], w, side="right"), minlength=d)
+    z = ((paulis[:, ::-1] != 0) << np.arange(n)).sum(axis=1)             # bit t: the qubit n - 1 - t
+    outcomes = np.arange(d)
+    even = np.array([[bin(int(o) & int(zk)).count("1") % 2 == 0 for o in outcomes] for zk in z])       # [m, d]
+    k_plus = np.einsum("bmo,mo->bm", hist[:, group_of, :], even.astype(np.int64))
+    k_minus = N - k_plus
+    e = coefs[None, :] * ((k_plus - k_minus).astype(np.float64) / float(N))
+    prod = np.array([[int(a) * int(b_) * 4 for a, b_ in zip(rp, rm)] for rp, rm in zip(k_plus, k_minus)], dtype=object)
+    s = np.abs(coefs)[None, :] * np.sqrt(prod.astype(np.float64) / float(N)) / float(N)
+    return e, np.full((B, m), float(N)), s, hist
+
+
+QV_GATE_ERROR_KEY_TAG = 0x51564745      # "QVGE": the Pauli errors of fbx_qv_noisy_trajectories
 
 
 def restate_qv_gate_errors(B, trajectories, L, gate_error, seed, first_item=0):

@@ -5,6 +5,7 @@ Mirror of forest/benchmarking/tomography.py:130-633.  Every estimator takes the 
 complex128 ``np.ndarray``; ``*_batch`` variants take SoA arrays ``expectations[B, m]``,
 ``total_counts[B, m]`` plus a :class:`fbx.design.Design` and are where the throughput lives.
 """
+import ctypes as C
 import warnings
 from typing import Callable, List, Sequence, Tuple
 
@@ -12,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from . import distance_measures as dm
-from .design import Design, flatten_results, process_design, state_design  # noqa: F401
+from .design import Design, Grouping, flatten_results, group_design, process_design, state_design  # noqa: F401
 from .observable_estimation import (ExperimentResult, ExperimentSetting, PauliTerm,
                                     TensorProductState, zeros_state, SIC0, SIC1, SIC2, SIC3,  # noqa: F401
                                     plusX, minusX, plusY, minusY, plusZ, minusZ)  # noqa: F401
@@ -774,11 +775,83 @@ def simulate_state_tomography_batch(design: Design, states, shots, readout_flip=
                            return_std_errs, return_exact, return_status)
 
 
-def simulate_tomography_results(qubits, kind, truth, shots, in_basis="pauli", **kw) -> List[ExperimentResult]:
+def _sim_grouping(design: Design, groups) -> Grouping:
+    """``groups`` of the grouped simulators as a ``Grouping`` of ``design``: a ``Grouping``, a ``group_of [m]`` array, or a method
+    name of ``design.group_design`` (grouped once, kept on the design)."""
+    if isinstance(groups, Grouping):
+        if groups.design is not design:
+            raise ValueError("the grouping was made for another design")
+        return groups
+    if isinstance(groups, str):
+        cache = design.__dict__.setdefault("_groupings", {})
+        if groups not in cache:
+            cache[groups] = group_design(design, groups)
+        return cache[groups]
+    return Grouping(design, groups)
+
+
+def _simulate_grouped_batch(who, design, truth, shots, groups, readout_flip, seed, first_item, return_std_errs, return_exact,
+                            return_probabilities, return_histograms, return_status):
+    grouping = _sim_grouping(design, groups)
+    B, m, cells = truth.shape[0], design.m, (grouping.n_groups, design.dim)
+    shots, flips, seed, first_item = _sim_noise(B, design.n_qubits, shots, readout_flip, seed, first_item)
+    e, c = np.empty((B, m)), np.empty((B, m))
+    se = np.empty((B, m)) if return_std_errs else None
+    ex = np.empty((B, m)) if return_exact else None
+    pr = np.empty((B,) + cells) if return_probabilities else None
+    hi = np.empty((B,) + cells, dtype=np.uint32) if return_histograms else None
+    status = np.zeros(B, dtype=np.int32)
+    _lib.check(_lib.lib().fbx_tomo_simulate_grouped(design.handle, grouping.handle, B, _lib.dptr(truth.view(np.float64)), shots,
+                                                    _lib.dptr(flips), seed, first_item, _lib.dptr(e), _lib.dptr(c), _lib.dptr(se),
+                                                    _lib.dptr(ex), _lib.dptr(pr), _lib.ptr(hi, C.c_uint32), _lib.iptr(status)))
+    if not return_status:
+        bad = np.flatnonzero(status)
+        if bad.size:
+            b = int(bad[0])
+            raise ValueError(f"{who}: item {b} (global id {first_item + b}) cannot be simulated: a truth entry that is not finite, "
+                             f"a readout_flip value outside [0, 1] or a group whose clamped outcome probabilities do not sum to a "
+                             f"positive finite number ({bad.size} such item(s) in the batch)")
+    out = (e, c) + tuple(x for x, on in ((se, return_std_errs), (ex, return_exact), (pr, return_probabilities),
+                                         (hi, return_histograms), (status, return_status)) if on)
+    return out
+
+
+def simulate_grouped_process_tomography_batch(design: Design, channels, shots, groups="greedy", rep="pauli_liouville",
+                                              readout_flip=None, seed=None, first_item=0, return_std_errs=False,
+                                              return_exact=False, return_probabilities=False, return_histograms=False,
+                                              return_status=False):
+    """``simulate_process_tomography_batch`` with GROUPED settings (``fbx_tomo_simulate_grouped``): the settings of a group --
+    one input state, one tensor-product basis -- are read off the same ``shots`` shots, as ``do_tomography(...,
+    group_tpb_settings=True)`` acquires them, so that the results of a group are correlated the way real data are.  ``groups``: a
+    ``design.Grouping``, a ``group_of [m]`` array, or a method of ``design.group_design`` ("greedy", "clique-removal"; grouped once
+    and kept on the design).  Returns ``(expectations [B, m], total_counts [B, m][, std_errs][, exact][, probabilities [B, G,
+    2^n]][, histograms [B, G, 2^n] uint32][, status])``: ``exact`` is bit for bit that of the ungrouped call, ``probabilities`` the
+    outcome distribution of every group (bit t of an outcome = qubit n - 1 - t, 1 = eigenvalue -1; flips included),
+    ``histograms`` the outcomes drawn.  The stream is part of the C contract and restated by
+    ``synthetic.restate_grouped_tomography_counts``; it is not the stream of the ungrouped call under the same seed."""
+    truth = _sim_process_truth(design, channels, rep)
+    return _simulate_grouped_batch("simulate_grouped_process_tomography_batch", design, truth, shots, groups, readout_flip, seed,
+                                   first_item, return_std_errs, return_exact, return_probabilities, return_histograms, return_status)
+
+
+def simulate_grouped_state_tomography_batch(design: Design, states, shots, groups="greedy", readout_flip=None, seed=None,
+                                            first_item=0, return_std_errs=False, return_exact=False, return_probabilities=False,
+                                            return_histograms=False, return_status=False):
+    """B true density matrices [B, d, d] measured with the grouped settings of a state design (1..5 qubits): the options and
+    returns of ``simulate_grouped_process_tomography_batch``."""
+    truth = _sim_state_truth(design, states)
+    return _simulate_grouped_batch("simulate_grouped_state_tomography_batch", design, truth, shots, groups, readout_flip, seed,
+                                   first_item, return_std_errs, return_exact, return_probabilities, return_histograms, return_status)
+
+
+def simulate_tomography_results(qubits, kind, truth, shots, in_basis="pauli", group_tpb_settings=False,
+                                **kw) -> List[ExperimentResult]:
     """One simulated experiment as the ``List[ExperimentResult]`` the reference-signature estimators and ``estimate_dfe`` read:
     the stand-in for the acquisition half of ``do_tomography``.  ``kind`` "process" (``truth`` a channel, ``rep`` and the other
     options of ``simulate_process_tomography_batch`` by keyword; settings of ``generate_process_tomography_settings(qubits,
-    in_basis)``) or "state" (``truth`` a density matrix; ``generate_state_tomography_settings(qubits)``)."""
+    in_basis)``) or "state" (``truth`` a density matrix; ``generate_state_tomography_settings(qubits)``).
+    ``group_tpb_settings=True`` (the default of ``do_tomography``; not here) takes the settings of a greedy group from the same
+    shots (``simulate_grouped_*_tomography_batch``); the results come back in the order of the settings either way."""
     qubits = list(qubits)
     if kind not in ("process", "state"):
         raise ValueError("kind must be 'process' or 'state'")
@@ -787,10 +860,11 @@ def simulate_tomography_results(qubits, kind, truth, shots, in_basis="pauli", **
             raise ValueError(f"simulate_tomography_results does not take {name}")
     if kind == "process":
         design = process_design(len(qubits), in_basis)
-        e, c, se = simulate_process_tomography_batch(design, truth, shots, return_std_errs=True, **kw)
+        simulate = simulate_grouped_process_tomography_batch if group_tpb_settings else simulate_process_tomography_batch
     else:
         design = state_design(len(qubits))
-        e, c, se = simulate_state_tomography_batch(design, truth, shots, return_std_errs=True, **kw)
+        simulate = simulate_grouped_state_tomography_batch if group_tpb_settings else simulate_state_tomography_batch
+    e, c, se = simulate(design, truth, shots, return_std_errs=True, **kw)
     if e.shape[0] != 1:
         raise ValueError("simulate_tomography_results covers one experiment: pass one channel or state")
     return [ExperimentResult(setting=s, expectation=float(x), total_counts=int(n), std_err=float(v))
@@ -798,14 +872,15 @@ def simulate_tomography_results(qubits, kind, truth, shots, in_basis="pauli", **
 
 
 def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pauli_liouville", readout_flip=None, seed=None,
-                                        first_item=0, estimator="pgdb", **estimator_kw):
+                                        first_item=0, estimator="pgdb", groups=None, **estimator_kw):
     """The resident loop truth -> shots -> estimate -> fidelity to truth: the truth's transfer matrices are uploaded once,
     ``fbx_tomo_simulate_dev`` writes (expectations, counts) into HBM, the estimator's ``_dev`` form (``estimator`` "pgdb":
     ``trace_preserving``, ``mode``, ``max_iters`` by keyword as in ``pgdb_process_estimate_batch``; "linear_inv": no options)
     reconstructs from them, and the Choi matrices go through Choi -> Pauli-Liouville into ``fbx_process_fidelity_dev`` against
     the truth.  Returns ``(chois [B, D, D], fidelity_to_truth [B])`` -- all that leaves the device; bit for bit what
     ``simulate_process_tomography_batch``, the batched estimator and ``distance_measures.process_fidelity_batch`` give when
-    composed through the host."""
+    composed through the host.  ``groups`` (a ``Grouping``, a ``group_of`` array or a method name, as in
+    ``simulate_grouped_process_tomography_batch``): ``fbx_tomo_simulate_grouped_dev`` draws the shots instead, one set per group."""
     if estimator not in _SIM_ESTIMATORS:
         raise ValueError(f"estimator must be one of {_SIM_ESTIMATORS}, not {estimator!r}")
     allowed = {"trace_preserving", "mode", "max_iters"} if estimator == "pgdb" else set()
@@ -815,6 +890,7 @@ def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pa
     if mode not in ("converge", "fixed"):
         raise ValueError("mode must be 'converge' or 'fixed'")
     truth = _sim_process_truth(design, channels, rep)
+    grouping = None if groups is None else _sim_grouping(design, groups)
     B, m, n, D = truth.shape[0], design.m, design.n_qubits, design.dim ** 2
     shots, flips, seed, first_item = _sim_noise(B, n, shots, readout_flip, seed, first_item)
     if B == 0:
@@ -826,8 +902,13 @@ def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pa
     d_choi, d_ptm, d_f = DB(B * D * D * 16), DB(B * D * D * 16), DB(B * 8)
     bufs = [b for b in (d_truth, d_truth_c, d_flips, d_e, d_c, d_status, d_choi, d_ptm, d_f) if b is not None]
     try:
-        _lib.check(lib.fbx_tomo_simulate_dev(design.handle, B, d_truth.ptr, shots, d_flips.ptr if d_flips else None, seed,
-                                             first_item, d_e.ptr, d_c.ptr, None, None, d_status.ptr))
+        if grouping is None:
+            _lib.check(lib.fbx_tomo_simulate_dev(design.handle, B, d_truth.ptr, shots, d_flips.ptr if d_flips else None, seed,
+                                                 first_item, d_e.ptr, d_c.ptr, None, None, d_status.ptr))
+        else:
+            _lib.check(lib.fbx_tomo_simulate_grouped_dev(design.handle, grouping.handle, B, d_truth.ptr, shots,
+                                                         d_flips.ptr if d_flips else None, seed, first_item, d_e.ptr, d_c.ptr,
+                                                         None, None, None, None, d_status.ptr))
         if estimator == "pgdb":
             _lib.check(lib.fbx_pgdb_process_dev(design.handle, B, d_e.ptr, d_c.ptr,
                                                 int(bool(estimator_kw.get("trace_preserving", True))),
@@ -847,5 +928,6 @@ def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pa
     bad = np.flatnonzero(status)
     if bad.size:
         raise ValueError(f"simulate_and_estimate_process_batch: item {int(bad[0])} cannot be simulated: a truth entry that is not "
-                         f"finite or a readout_flip value outside [0, 1] ({bad.size} such item(s) in the batch)")
+                         f"finite or a readout_flip value outside [0, 1]" + (" or outcome probabilities of a group that do not sum "
+                         f"to a positive finite number" if grouping is not None else "") + f" ({bad.size} such item(s) in the batch)")
     return choi, fid

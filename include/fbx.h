@@ -84,6 +84,7 @@ extern "C" {
 #define FBX_PROJ_PHYSICAL_TNI 4  /* project_superoperators.py:87 proj_choi_to_physical(.., False) */
 
 typedef struct fbx_design fbx_design;   /* opaque: owns the device copy of a design */
+typedef struct fbx_grouping fbx_grouping;   /* opaque: owns the device tables of a grouping of a design's settings */
 
 /* ---------------------------------------------------------------- library / device */
 int         fbx_version(void);
@@ -667,6 +668,56 @@ int fbx_tomo_simulate(const fbx_design* design, int64_t B, const double* truth, 
 int fbx_tomo_simulate_dev(const fbx_design* design, int64_t B, const double* d_truth, int64_t n_shots, const double* d_readout_flip,
                           uint64_t seed, int64_t first_item, double* d_expect_out, double* d_counts_out, double* d_std_err_out,
                           double* d_exact_out, int32_t* d_status_out);
+
+/* ---------------------------------------------------------------- simulated tomography with grouped settings: one set of shots per basis
+ * What do_tomography(..., group_tpb_settings=True) acquires (observable_estimation.py:470-692, group_settings): settings that are
+ * diagonal in one tensor-product basis form a group and are estimated from the SAME bitstrings, so that within a group the
+ * results carry the correlations of real data -- in every shot the ZZ result is the product of the IZ and ZI results.
+ *
+ * fbx_grouping_create: group_of [m] gives the group id, in [0, n_groups), of every setting of `design` (the caller's order).
+ * FBX_ERR_BAD_ARG with a message for an id out of range, a group without a member, members of one group with different
+ * in_labels rows, or members whose Paulis differ on a qubit where both are not the identity.  The grouping holds per group the
+ * input state, the BASIS -- per qubit the one non-identity Pauli its members use there and Z where no member uses the qubit, so
+ * that every group measures all n qubits and the outcome space is always 2^n <= 32 -- and the members sorted by group, each
+ * with its parity mask (bit t set where base-4 digit t of its Pauli index is not the identity).  It belongs to `design` (which
+ * must outlive it) and to the device it was created on.
+ *
+ * fbx_tomo_simulate_grouped: truth, readout_flip, n_shots, seed, first_item, the limits (1..3 qubit process designs, 1..5
+ * qubit state designs, n_shots < 2^32) and expect_out / counts_out / std_err_out / exact_out [B][m] / status_out [B] are those of
+ * fbx_tomo_simulate; prob_out [B][G][2^n] double and hist_out [B][G][2^n] uint32 are per group.  Every output may be NULL, not
+ * all of them.  n_shots == 0 gives exact_out and prob_out only (the others must be NULL).  A unit is (item b, group g):
+ *  1. CLEAN MEANS.  For every subset T of the n qubits t_T = tr[P_T Lambda_b(rho_s)] (state designs: tr[P_T rho_b]), t of the
+ *     empty set = 1; P_T is the group's basis with the factors outside T replaced by I.
+ *  2. DISTRIBUTION.  p(o) = 2^-n sum_T (-1)^{|o & T|} t_T.  Bit t of an outcome belongs to the qubit of base-4 digit t of a
+ *     Pauli index (qubit n - 1 - t); bit value 1 = eigenvalue -1.  Then, per qubit j, the confusion matrix of readout_flip:
+ *     p'(bit = 0) = (1 - f0_j) p(bit = 0) + f1_j p(bit = 1), p'(bit = 1) = f0_j p(bit = 0) + (1 - f1_j) p(bit = 1).  prob_out
+ *     receives this p, unclamped, flips included.
+ *  3. THRESHOLDS.  c_o = the running sum of max(p(o'), 0) in outcome order, one addition per outcome (numpy.cumsum restates
+ *     it bit for bit); thr_o = floor(c_o / c_last 2^32) for every outcome but the last, which gets 2^32.  If c_last is not a
+ *     positive finite number the ITEM is poisoned.
+ *  4. SHOTS.  Shot s reads word s & 3 of the Philox4x32-10 block with counter (gid low, gid high, g, s >> 2) and key (seed low ^
+ *     0x544F4D47, seed high), gid = first_item + b; the tag "TOMG" keeps the stream apart from that of fbx_tomo_simulate under
+ *     the same seed.  The outcome of a word is the number of thresholds <= the word; hist_out[o] counts the outcomes.
+ *  5. MEMBERS.  For member k with parity mask z_k, k_plus = sum_o hist[o] [popcount(o & z_k) even], k_minus = N - k_plus, and
+ *     expect_out / counts_out / std_err_out follow the integer formulas of fbx_tomo_simulate, written at the caller's setting
+ *     index.  An all-identity observable gives its coefficient and std_err 0.
+ *  6. EXACT MEANS.  exact_out[k] is the very value fbx_tomo_simulate writes for setting k (the same code), bit for bit.
+ * A value depends on (seed, gid, g, p, n_shots) only: not on B or the launch shape.
+ * A poisoned item -- a non-finite truth entry, a flip probability outside [0, 1] or NaN, or a group whose c_last is not a
+ * positive finite number -- gets status 1, NaN in expect_out / std_err_out / exact_out / prob_out, N in counts_out and 0 in
+ * hist_out, for ALL its groups; its neighbours are untouched.  Bad arguments (those of fbx_tomo_simulate, a NULL grouping or
+ * one of another design or device): FBX_ERR_BAD_ARG before any buffer is touched.  B == 0: nothing is done.
+ * The _dev form enqueues on the calling thread's stream and does not synchronise. */
+int fbx_grouping_create(const fbx_design* design, int n_groups, const int32_t* group_of, fbx_grouping** out);
+int fbx_grouping_destroy(fbx_grouping* grouping);
+int fbx_tomo_simulate_grouped(const fbx_design* design, const fbx_grouping* grouping, int64_t B, const double* truth,
+                              int64_t n_shots, const double* readout_flip, uint64_t seed, int64_t first_item, double* expect_out,
+                              double* counts_out, double* std_err_out, double* exact_out, double* prob_out, uint32_t* hist_out,
+                              int32_t* status_out);
+int fbx_tomo_simulate_grouped_dev(const fbx_design* design, const fbx_grouping* grouping, int64_t B, const double* d_truth,
+                                  int64_t n_shots, const double* d_readout_flip, uint64_t seed, int64_t first_item,
+                                  double* d_expect_out, double* d_counts_out, double* d_std_err_out, double* d_exact_out,
+                                  double* d_prob_out, uint32_t* d_hist_out, int32_t* d_status_out);
 
 /* ---------------------------------------------------------------- curve fits (analysis/fitting.py, randomized_benchmarking.py,
  * qubit_spectroscopy.py)

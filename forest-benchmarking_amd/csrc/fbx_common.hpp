@@ -196,6 +196,11 @@ struct fbx_design {
     std::vector<int> order_host;
     std::vector<uint32_t> sp_host;
     std::vector<double> coef_host;
+    // the readout calibrations of the design (fbx_tomo_calibration_list), made on first use under replica_mu: the Pauli index of
+    // every calibration, the calibration of every setting (-1: an all-identity observable) and the parity masks on the device
+    mutable bool cal_ready = false;
+    mutable std::vector<int> cal_pauli_host, cal_index_host;
+    mutable void* cal_slab = nullptr;
 };
 
 namespace fbx {

@@ -802,6 +802,7 @@ int fbx_design_destroy(fbx_design* design) {
     design->replicas.clear();
     if (design->slab) (void)hipFree(design->slab);
     if (design->slab2) (void)hipFree(design->slab2);
+    if (design->cal_slab) (void)hipFree(design->cal_slab);
     delete design;
     return FBX_OK;
 }

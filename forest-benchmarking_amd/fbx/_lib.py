@@ -176,6 +176,13 @@ PROTOTYPES = {
     "fbx_grouping_destroy": [_vp],
     "fbx_tomo_simulate_grouped": [_vp, _vp, _i64, _dp, _i64, _dp, C.c_uint64, _i64, _dp, _dp, _dp, _dp, _dp, _u32p, _ip],
     "fbx_tomo_simulate_grouped_dev": [_vp, _vp, _i64, _vp, _i64, _vp, C.c_uint64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "fbx_tomo_simulate_symmetrized": [_vp, _vp, _i64, _dp, _dp, C.c_int, _i64, C.c_uint64, _i64, _dp, _dp, _dp, _dp, _dp, _u32p,
+                                      _ip],
+    "fbx_tomo_simulate_symmetrized_dev": [_vp, _vp, _i64, _vp, _vp, C.c_int, _i64, C.c_uint64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp],
+    "fbx_tomo_calibration_list": [_vp, _ip, _ip, _ip],
+    "fbx_tomo_simulate_calibration": [_vp, _i64, _dp, C.c_int, _i64, C.c_uint64, _i64, _dp, _dp, _dp, _dp, _ip],
+    "fbx_tomo_simulate_calibration_dev": [_vp, _i64, _vp, C.c_int, _i64, C.c_uint64, _i64, _vp, _vp, _vp, _vp, _vp],
     "fbx_curve_fit": [C.c_int, _i64, C.c_int, _dp, _i64, _dp, _dp, _dp, C.c_uint, C.c_double, C.c_double, C.c_int,
                       _dp, _dp, _dp, _dp, _ip, _ip, _dp],
     "fbx_curve_fit_dev": [C.c_int, _i64, C.c_int, _vp, _i64, _vp, _vp, _vp, C.c_uint, C.c_double, C.c_double, C.c_int,

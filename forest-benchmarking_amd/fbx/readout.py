@@ -111,3 +111,22 @@ def marginalize_confusion_matrix(confusion_matrix: np.ndarray, all_qubits: Seque
     ``ValueError`` where the reference asserts."""
     mat = np.asarray(confusion_matrix, dtype=np.float64)
     return marginalize_confusion_matrix_batch(mat[None], all_qubits, marginal_subset)[0]
+
+
+def confusion_from_flips(readout_flip) -> np.ndarray:
+    """The joint confusion matrix of independent per-bit flips: ``readout_flip [n, 2]`` (or ``[B, n, 2]``) with ``[j, 0]`` = P(read
+    1 | drawn 0) and ``[j, 1]`` = P(read 0 | drawn 1) of qubit j, the convention of the simulators' ``readout_flip`` argument ->
+    ``[2^n, 2^n]`` (``[B, 2^n, 2^n]``), the Kronecker product of the per-qubit [drawn][read] matrices with qubit 0 the most
+    significant bit: what the ``confusion`` argument of ``tomography.simulate_symmetrized_*_tomography_batch`` takes."""
+    f = np.asarray(readout_flip, dtype=np.float64)
+    single = f.ndim == 2
+    f = f[None] if single else f
+    if f.ndim != 3 or f.shape[2] != 2 or f.shape[1] < 1:
+        raise ValueError("readout_flip must be [n, 2] or [B, n, 2]")
+    out = np.ones((f.shape[0], 1, 1))
+    for j in range(f.shape[1]):
+        one = np.empty((f.shape[0], 2, 2))
+        one[:, 0, 0], one[:, 0, 1] = 1.0 - f[:, j, 0], f[:, j, 0]
+        one[:, 1, 0], one[:, 1, 1] = f[:, j, 1], 1.0 - f[:, j, 1]
+        out = np.einsum("bij,bkl->bikjl", out, one).reshape(f.shape[0], 2 * out.shape[1], 2 * out.shape[2])
+    return out[0] if single else out

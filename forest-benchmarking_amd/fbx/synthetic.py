@@ -403,6 +403,155 @@ def restate_grouped_tomography_counts(probabilities, grouping_or_group_of, pauli
     return e, np.full((B, m), float(N)), s, hist
 
 
+TOMO_SYMMETRIZED_KEY_TAG = 0x544F4D53    # "TOMS": the shots of fbx_tomo_simulate_symmetrized
+TOMO_CALIBRATION_KEY_TAG = 0x544F4D43    # "TOMC": the shots of fbx_tomo_simulate_calibration
+
+
+def symmetrization_patterns(mask, symm_type):
+    """The flip masks of a unit whose members act on the qubits of ``mask`` (bit t = qubit n - 1 - t), in ascending order:
+    every submask for ``symm_type = -1`` (exhaustive symmetrization), 0 alone for ``symm_type = 0``.  The orthogonal arrays
+    (1, 2, 3) are not implemented: ``ValueError``."""
+    if symm_type not in (-1, 0):
+        raise ValueError("symm_type must be -1 (exhaustive) or 0 (none); the orthogonal arrays 1, 2, 3 are not implemented")
+    mask = int(mask)
+    if symm_type == 0:
+        return [0]
+    out, f = [], 0
+    while True:
+        out.append(f)
+        f = (f - mask) & mask                                            # the next submask, ascending
+        if f == 0:
+            return out
+
+
+def shots_per_pattern(shots, mask, symm_type):
+    """``floor(shots / patterns)`` of a unit (this library's rule, include/fbx.h); 0 or 2^29 and more raise ``ValueError``"""
+    s = int(shots) // len(symmetrization_patterns(mask, symm_type))
+    if not 1 <= s < 2 ** 29:
+        raise ValueError("need at least one and fewer than 2^29 shots per flip pattern: floor(shots / patterns) is out of range")
+    return s
+
+
+def symmetrized_pattern_distributions(ideal, confusion, masks, symm_type):
+    """``q_f(r) = sum_o p(o) C[o ^ f][r ^ f]`` in dense float64 (not the device's summation order): ``ideal [B, G, 2^n]`` the
+    distributions without readout error, ``confusion [B, 2^n, 2^n]`` or ``[2^n, 2^n]`` laid out [drawn][read], ``masks [G]`` the
+    union of the members' parity masks per group -> ``[B, G, 2^n, 2^n]``, row f = pattern f, a zero row where f is no pattern."""
+    p = np.asarray(ideal, dtype=np.float64)
+    B, G, d = p.shape
+    c = np.broadcast_to(np.asarray(confusion, dtype=np.float64), (B, d, d))
+    idx = np.arange(d)
+    out = np.zeros((B, G, d, d))
+    for g in range(G):
+        for f in symmetrization_patterns(masks[g], symm_type):
+            out[:, g, f, :] = np.einsum("bo,bor->br", p[:, g, :], c[:, idx ^ f][:, :, idx ^ f])
+    return out
+
+
+def _restate_symmetrized_hist(q, patterns, s, k0, k1, gid, unit):
+    """the merged histogram of one unit: ``q [2^n, 2^n]`` its rows by flip mask, ``s`` shots per pattern"""
+    d = q.shape[1]
+    blocks = np.arange((s + 3) // 4, dtype=np.uint64)
+    hist = np.zeros(d, dtype=np.int64)
+    for f in patterns:
+        c = np.cumsum(np.where(q[f] < 0.0, 0.0, q[f]))
+        if not (c[-1] > 0.0 and np.isfinite(c[-1])):
+            raise ValueError("a pattern whose clamped sum is not a positive finite number (a poisoned item) cannot be restated")
+        thr = np.floor(c[:-1] / c[-1] * 2.0 ** 32).astype(np.uint64)
+        words = _philox4x32_10(np.uint64(gid & 0xFFFFFFFF), np.uint64(gid >> 32), np.uint64(unit),
+                               np.uint64(f << 27) | blocks, k0, k1)
+        w = np.stack(np.broadcast_arrays(*words), axis=1).reshape(-1)[:s]                     # shot t = word t & 3 of block t >> 2
+        hist += np.bincount(np.searchsorted(thr, w, side="right"), minlength=d)
+    return hist
+
+
+def _parity_counts(hist, z):
+    d = hist.shape[-1]
+    even = np.array([bin(o & int(z)).count("1") % 2 == 0 for o in range(d)])
+    return int(hist[even].sum())
+
+
+def restate_symmetrized_tomography_counts(probabilities, grouping_or_group_of, paulis, coefs, shots, symm_type, seed, first_item=0):
+    """Steps 4-5 of the contract of ``fbx_tomo_simulate_symmetrized`` (include/fbx.h) restated on the host from the per-pattern
+    distributions it reports: ``probabilities [B, G, 2^n, 2^n]`` (row f = the un-flipped record's distribution under flip mask f;
+    the ``return_probabilities`` output), the grouping (a ``design.Grouping`` or its ``group_of [m]``), ``paulis [m, n]`` and
+    ``coefs [m]`` of the design, ``shots`` the total of a group.  Per (item, group): the patterns are the submasks of the union of
+    the members' masks (``symm_type = -1``) or 0 alone (0); every pattern draws s = floor(shots / patterns) shots with the
+    thresholds of ``restate_grouped_tomography_counts``; shot t of pattern f reads word ``t & 3`` of the Philox4x32-10 block with
+    counter (gid low, gid high, group, (f << 27) | (t >> 2)) and key (seed low ^ 0x544F4D53, seed high).  The histograms of the
+    patterns are added, and member k counts k+ on the sum with N = s x patterns.  Returns ``(expectations [B, m], total_counts
+    [B, m], std_errs [B, m], hist [B, G, 2^n] int64)``; ``ValueError`` for the orthogonal arrays and for s == 0."""
+    p = np.asarray(probabilities, dtype=np.float64)
+    group_of = np.asarray(getattr(grouping_or_group_of, "group_of", grouping_or_group_of)).astype(np.int64)
+    paulis = np.asarray(paulis)
+    m, n = paulis.shape
+    coefs = np.broadcast_to(np.asarray(coefs, dtype=np.float64), (m,))
+    seed, first_item = int(seed) & (2 ** 64 - 1), int(first_item)
+    if p.ndim != 4 or p.shape[2:] != (1 << n, 1 << n) or group_of.shape != (m,) or group_of.min() < 0 or group_of.max() >= p.shape[1]:
+        raise ValueError("need probabilities [B, G, 2^n, 2^n], paulis [m, n] and group ids [m] in [0, G)")
+    if not 1 <= int(shots) < 2 ** 32 or first_item < 0:
+        raise ValueError("need 1 <= shots < 2^32 and first_item >= 0")
+    B, G, d = p.shape[:3]
+    z = ((paulis[:, ::-1] != 0) << np.arange(n)).sum(axis=1)             # bit t: the qubit n - 1 - t
+    union = np.zeros(G, dtype=np.int64)
+    np.bitwise_or.at(union, group_of, z)
+    patterns = [symmetrization_patterns(u, symm_type) for u in union]
+    per = [shots_per_pattern(shots, u, symm_type) for u in union]
+    k0, k1 = (seed & 0xFFFFFFFF) ^ TOMO_SYMMETRIZED_KEY_TAG, seed >> 32
+    hist = np.zeros((B, G, d), dtype=np.int64)
+    for b in range(B):
+        for g in range(G):
+            hist[b, g] = _restate_symmetrized_hist(p[b, g], patterns[g], per[g], k0, k1, first_item + b, g)
+    e, cnt, se = np.empty((B, m)), np.empty((B, m)), np.empty((B, m))
+    for k in range(m):
+        g = group_of[k]
+        N = per[g] * len(patterns[g])
+        for b in range(B):
+            kp = _parity_counts(hist[b, g], z[k]); km = N - kp
+            e[b, k] = coefs[k] * (float(kp - km) / float(N))
+            se[b, k] = abs(coefs[k]) * np.sqrt(float(4 * kp * km) / float(N)) / float(N)
+            cnt[b, k] = float(N)
+    return e, cnt, se, hist
+
+
+def restate_readout_calibration_counts(confusion, cal_paulis, shots, symm_type, seed, first_item=0):
+    """The stream of ``fbx_tomo_simulate_calibration`` (include/fbx.h) restated on the host: ``confusion [B, 2^n, 2^n]`` (or one
+    matrix) laid out [drawn][read], ``cal_paulis [n_cal, n]`` the Pauli codes of the calibrations.  Calibration c with parity mask
+    z_c draws, per flip mask f (the submasks of z_c, or 0 alone for ``symm_type = 0``), s = floor(shots / patterns) un-flipped
+    records from ``q_f(r) = C[f][r ^ f]``; shot t reads word ``t & 3`` of the block with counter (gid low, gid high, c, (f << 27) |
+    (t >> 2)) and key (seed low ^ 0x544F4D43, seed high).  Returns ``(cal_means, cal_vars, cal_counts [B, n_cal], hist [B, n_cal,
+    2^n] int64)``: mean = (k+ - k-) / N, var = 4 k+ k- / N^3 (the variance of the mean of the +-1 values), N = s x patterns."""
+    c = np.asarray(confusion, dtype=np.float64)
+    c = c[None] if c.ndim == 2 else c
+    cal_paulis = np.asarray(cal_paulis)
+    n_cal, n = cal_paulis.shape
+    d = 1 << n
+    seed, first_item = int(seed) & (2 ** 64 - 1), int(first_item)
+    if c.ndim != 3 or c.shape[1:] != (d, d):
+        raise ValueError("need confusion [B, 2^n, 2^n] and cal_paulis [n_cal, n]")
+    if not 1 <= int(shots) < 2 ** 32 or first_item < 0:
+        raise ValueError("need 1 <= shots < 2^32 and first_item >= 0")
+    B = c.shape[0]
+    z = ((cal_paulis[:, ::-1] != 0) << np.arange(n)).sum(axis=1)
+    patterns = [symmetrization_patterns(zc, symm_type) for zc in z]
+    per = [shots_per_pattern(shots, zc, symm_type) for zc in z]
+    k0, k1 = (seed & 0xFFFFFFFF) ^ TOMO_CALIBRATION_KEY_TAG, seed >> 32
+    idx = np.arange(d)
+    mean, var, cnt = np.empty((B, n_cal)), np.empty((B, n_cal)), np.empty((B, n_cal))
+    hist = np.zeros((B, n_cal, d), dtype=np.int64)
+    for b in range(B):
+        for k in range(n_cal):
+            q = np.zeros((d, d))
+            for f in patterns[k]:
+                q[f] = c[b, f, idx ^ f]
+            hist[b, k] = _restate_symmetrized_hist(q, patterns[k], per[k], k0, k1, first_item + b, k)
+            N = per[k] * len(patterns[k])
+            kp = _parity_counts(hist[b, k], z[k]); km = N - kp
+            mean[b, k] = float(kp - km) / float(N)
+            var[b, k] = float(4 * kp * km) / float(N) / float(N) / float(N)
+            cnt[b, k] = float(N)
+    return mean, var, cnt, hist
+
+
 QV_GATE_ERROR_KEY_TAG = 0x51564745      # "QVGE": the Pauli errors of fbx_qv_noisy_trajectories
 
 

@@ -844,20 +844,195 @@ def simulate_grouped_state_tomography_batch(design: Design, states, shots, group
                                    first_item, return_std_errs, return_exact, return_probabilities, return_histograms, return_status)
 
 
-def simulate_tomography_results(qubits, kind, truth, shots, in_basis="pauli", group_tpb_settings=False,
+# --------------------------------------------------------------------------------------------------
+# symmetrized readout and calibration under a joint confusion matrix (fbx_tomo_simulate_symmetrized / _calibration):
+# the reference's defaults symm_type = -1 and calibrate_observables = True of do_tomography
+# --------------------------------------------------------------------------------------------------
+def _sim_symm_type(symm_type):
+    if symm_type not in (-1, 0):
+        raise ValueError("symm_type must be -1 (exhaustive symmetrization) or 0 (none); the orthogonal arrays 1, 2, 3 are not "
+                         "implemented")
+    return int(symm_type)
+
+
+def _sim_confusion(B, n, confusion):
+    """``confusion`` as [B, 2^n, 2^n] float64; a row whose (finite) sum is not 1 is refused -- ``np.allclose(row sums, 1.0)``, the
+    rule of ``synthetic.readout_shots``.  A row with a non-finite sum goes on to the library, which poisons the item."""
+    d = 1 << n
+    c = np.asarray(confusion, dtype=np.float64)
+    if c.shape not in ((d, d), (B, d, d)):
+        raise ValueError(f"confusion must be [2^n, 2^n] = {(d, d)} or [B, 2^n, 2^n] = {(B, d, d)}, not {c.shape}")
+    c = np.ascontiguousarray(np.broadcast_to(c, (B, d, d)))
+    sums = c.sum(axis=2)
+    finite = np.isfinite(sums)
+    if not np.allclose(sums[finite], 1.0):
+        raise ValueError("every row of the confusion matrix ([drawn][read]) must sum to 1")
+    return c
+
+
+def calibration_list(design: Design):
+    """The readout calibrations of ``design`` (``fbx_tomo_calibration_list``): ``(cal_paulis [n_cal, n] uint8, cal_index [m]
+    int32)`` -- its distinct non-identity observables in order of first appearance, and the calibration of every setting (-1 for
+    an all-identity observable)."""
+    n_cal = C.c_int32(0)
+    idx = np.empty(design.m, dtype=np.int32)
+    pidx = np.empty(design.m, dtype=np.int32)
+    _lib.check(_lib.lib().fbx_tomo_calibration_list(design.handle, C.byref(n_cal), _lib.iptr(pidx),
+                                                    _lib.iptr(idx)))
+    n = design.n_qubits
+    pidx = pidx[:n_cal.value]
+    codes = np.array([[(int(p) >> (2 * (n - 1 - q))) & 3 for q in range(n)] for p in pidx], dtype=np.uint8).reshape(-1, n)
+    return codes, idx
+
+
+def _simulate_symmetrized_batch(who, design, truth, shots, confusion, symm_type, groups, seed, first_item, return_std_errs,
+                                return_exact, return_probabilities, return_histograms, return_status):
+    grouping = _sim_grouping(design, groups)
+    B, m, d = truth.shape[0], design.m, design.dim
+    symm_type = _sim_symm_type(symm_type)
+    shots, _, seed, first_item = _sim_noise(B, design.n_qubits, shots, None, seed, first_item)
+    conf = _sim_confusion(B, design.n_qubits, confusion)
+    e, c = np.empty((B, m)), np.empty((B, m))
+    se = np.empty((B, m)) if return_std_errs else None
+    ex = np.empty((B, m)) if return_exact else None
+    pr = np.empty((B, grouping.n_groups, d, d)) if return_probabilities else None
+    hi = np.empty((B, grouping.n_groups, d), dtype=np.uint32) if return_histograms else None
+    status = np.zeros(B, dtype=np.int32)
+    _lib.check(_lib.lib().fbx_tomo_simulate_symmetrized(design.handle, grouping.handle, B, _lib.dptr(truth.view(np.float64)),
+                                                        _lib.dptr(conf), symm_type, shots, seed, first_item, _lib.dptr(e),
+                                                        _lib.dptr(c), _lib.dptr(se), _lib.dptr(ex), _lib.dptr(pr),
+                                                        _lib.ptr(hi, C.c_uint32), _lib.iptr(status)))
+    if not return_status:
+        bad = np.flatnonzero(status)
+        if bad.size:
+            b = int(bad[0])
+            raise ValueError(f"{who}: item {b} (global id {first_item + b}) cannot be simulated: a truth entry that is not finite, "
+                             f"a confusion entry that is not finite or outside [0, 1], or a flip pattern whose clamped outcome "
+                             f"probabilities do not sum to a positive finite number ({bad.size} such item(s) in the batch)")
+    return (e, c) + tuple(x for x, on in ((se, return_std_errs), (ex, return_exact), (pr, return_probabilities),
+                                          (hi, return_histograms), (status, return_status)) if on)
+
+
+def simulate_symmetrized_process_tomography_batch(design: Design, channels, shots, confusion, symm_type=-1, groups="greedy",
+                                                  rep="pauli_liouville", seed=None, first_item=0, return_std_errs=False,
+                                                  return_exact=False, return_probabilities=False, return_histograms=False,
+                                                  return_status=False):
+    """``simulate_grouped_process_tomography_batch`` under a JOINT readout confusion matrix and the reference's readout
+    symmetrization (``fbx_tomo_simulate_symmetrized``).  ``confusion`` ([2^n, 2^n] for the batch or [B, 2^n, 2^n]): ``[drawn,
+    read]`` = the probability of reading bitstring ``read`` when ``drawn`` was drawn, index = the bitstring as a binary number
+    with qubit 0 first (the layout of ``readout.joint_confusion_matrices_batch`` and ``synthetic.readout_shots``;
+    ``readout.confusion_from_flips`` builds it from a ``readout_flip`` array); rows sum to 1.  ``symm_type=-1`` (the default of
+    ``do_tomography``): every group is measured under every combination of pre-measurement flips of the qubits its members act
+    on, the flips undone in the record, ``floor(shots / patterns)`` shots each; ``symm_type=0``: no symmetrization, the plain
+    correlated readout error.  ``total_counts`` of a setting = the shots its group really drew, ``floor(shots / patterns) x
+    patterns``, which can differ between the groups of one call.  ``exact`` is the mean of what is measured (matrix included),
+    ``probabilities [B, G, 2^n, 2^n]`` the distribution of the un-flipped record per flip mask (a zero row for a mask that is no
+    pattern of the group), ``histograms [B, G, 2^n]`` the merged record.  The stream is restated by
+    ``synthetic.restate_symmetrized_tomography_counts``."""
+    truth = _sim_process_truth(design, channels, rep)
+    return _simulate_symmetrized_batch("simulate_symmetrized_process_tomography_batch", design, truth, shots, confusion, symm_type,
+                                       groups, seed, first_item, return_std_errs, return_exact, return_probabilities,
+                                       return_histograms, return_status)
+
+
+def simulate_symmetrized_state_tomography_batch(design: Design, states, shots, confusion, symm_type=-1, groups="greedy", seed=None,
+                                                first_item=0, return_std_errs=False, return_exact=False, return_probabilities=False,
+                                                return_histograms=False, return_status=False):
+    """B true density matrices [B, d, d] measured with the grouped settings of a state design (1..5 qubits) under a joint confusion
+    matrix: the options and returns of ``simulate_symmetrized_process_tomography_batch``."""
+    truth = _sim_state_truth(design, states)
+    return _simulate_symmetrized_batch("simulate_symmetrized_state_tomography_batch", design, truth, shots, confusion, symm_type,
+                                       groups, seed, first_item, return_std_errs, return_exact, return_probabilities,
+                                       return_histograms, return_status)
+
+
+def simulate_readout_calibration_batch(design: Design, confusion, shots, symm_type=-1, seed=None, first_item=0, batch=None,
+                                       return_exact=False, return_status=False):
+    """The calibration runs of ``calibrate_observable_estimates`` simulated on the device (``fbx_tomo_simulate_calibration``):
+    every distinct non-identity observable of ``design`` is measured on its +1 eigenstate -- every bit drawn as 0 -- through
+    ``confusion`` with the symmetrization of ``symm_type``, ``shots`` shots in all per observable.  ``confusion`` [B, 2^n, 2^n],
+    or one matrix for ``batch`` items (default 1).  Returns ``(cal_means [B, n_cal], cal_vars [B, n_cal], cal_counts [B, n_cal],
+    cal_index [m][, exact [B, n_cal]][, status [B]])``: what ``observable_estimation.calibrate_expectations_batch`` takes per
+    item, ``cal_index`` as ``calibration_list`` gives it.  The stream is restated by
+    ``synthetic.restate_readout_calibration_counts``."""
+    n, d = design.n_qubits, design.dim
+    c = np.asarray(confusion, dtype=np.float64)
+    B = c.shape[0] if c.ndim == 3 else (1 if batch is None else int(batch))
+    symm_type = _sim_symm_type(symm_type)
+    shots, _, seed, first_item = _sim_noise(B, n, shots, None, seed, first_item)
+    conf = _sim_confusion(B, n, c)
+    cal_paulis, cal_index = calibration_list(design)
+    n_cal = cal_paulis.shape[0]
+    mean, var, cnt = np.empty((B, n_cal)), np.empty((B, n_cal)), np.empty((B, n_cal))
+    ex = np.empty((B, n_cal)) if return_exact else None
+    status = np.zeros(B, dtype=np.int32)
+    _lib.check(_lib.lib().fbx_tomo_simulate_calibration(design.handle, B, _lib.dptr(conf), symm_type, shots, seed, first_item,
+                                                        _lib.dptr(mean), _lib.dptr(var), _lib.dptr(ex), _lib.dptr(cnt),
+                                                        _lib.iptr(status)))
+    if not return_status:
+        bad = np.flatnonzero(status)
+        if bad.size:
+            raise ValueError(f"simulate_readout_calibration_batch: item {int(bad[0])} (global id {first_item + int(bad[0])}) cannot "
+                             f"be simulated: a confusion entry that is not finite or outside [0, 1], or a flip pattern whose "
+                             f"probabilities do not sum to a positive finite number ({bad.size} such item(s) in the batch)")
+    return (mean, var, cnt, cal_index) + ((ex,) if return_exact else ()) + ((status,) if return_status else ())
+
+
+def _flat_cal_index(cal_index, B, n_cal):
+    """[B m] int32: the calibration of (item, setting) among the B n_cal calibrations of a batch laid out [B][n_cal]"""
+    if np.any(cal_index < 0):
+        raise ValueError("a design with an all-identity observable cannot be calibrated here: it has no calibration run")
+    return np.ascontiguousarray((np.arange(B, dtype=np.int64)[:, None] * n_cal + cal_index[None, :]).reshape(-1), dtype=np.int32)
+
+
+def simulate_tomography_results(qubits, kind, truth, shots, in_basis="pauli", group_tpb_settings=False, confusion=None,
+                                symm_type=0, calibrate_observables=False, calibration_shots=None,
                                 **kw) -> List[ExperimentResult]:
     """One simulated experiment as the ``List[ExperimentResult]`` the reference-signature estimators and ``estimate_dfe`` read:
     the stand-in for the acquisition half of ``do_tomography``.  ``kind`` "process" (``truth`` a channel, ``rep`` and the other
     options of ``simulate_process_tomography_batch`` by keyword; settings of ``generate_process_tomography_settings(qubits,
     in_basis)``) or "state" (``truth`` a density matrix; ``generate_state_tomography_settings(qubits)``).
     ``group_tpb_settings=True`` (the default of ``do_tomography``; not here) takes the settings of a greedy group from the same
-    shots (``simulate_grouped_*_tomography_batch``); the results come back in the order of the settings either way."""
+    shots (``simulate_grouped_*_tomography_batch``); the results come back in the order of the settings either way.
+    ``confusion`` (a joint [2^n, 2^n] matrix) measures through ``simulate_symmetrized_*_tomography_batch`` with ``symm_type``
+    (0 here; ``do_tomography`` has -1) instead of ``readout_flip``, every setting a group of its own unless
+    ``group_tpb_settings``; ``calibrate_observables=True`` adds the calibration runs (``calibration_shots``, default ``shots``;
+    ``simulate_readout_calibration_batch``) and fills ``raw_expectation``, ``raw_std_err`` and the ``calibration_*`` fields through
+    ``calibrate_observable_estimates_from_moments``.  Without these options nothing changes."""
     qubits = list(qubits)
     if kind not in ("process", "state"):
         raise ValueError("kind must be 'process' or 'state'")
     for name in ("return_std_errs", "return_exact", "return_status", "first_item"):
         if name in kw:
             raise ValueError(f"simulate_tomography_results does not take {name}")
+    if confusion is not None or calibrate_observables:
+        if kw.get("readout_flip") is not None:
+            raise ValueError("give the readout error as confusion (readout.confusion_from_flips), not as readout_flip")
+        kw.pop("readout_flip", None)
+        design = process_design(len(qubits), in_basis) if kind == "process" else state_design(len(qubits))
+        conf = np.eye(design.dim) if confusion is None else np.asarray(confusion, dtype=np.float64)
+        if conf.shape != (design.dim, design.dim):
+            raise ValueError(f"confusion must be one [2^n, 2^n] = {(design.dim, design.dim)} matrix")
+        from .operator_tools.random_operators import _stream_seed
+        seed = _stream_seed(kw.pop("seed", None))              # one key for the measurement and the calibration runs
+        groups = kw.pop("groups", "greedy" if group_tpb_settings else np.arange(design.m))
+        simulate = simulate_symmetrized_process_tomography_batch if kind == "process" else simulate_symmetrized_state_tomography_batch
+        e, c, se = simulate(design, truth, shots, conf, symm_type=symm_type, groups=groups, seed=seed, return_std_errs=True, **kw)
+        if e.shape[0] != 1:
+            raise ValueError("simulate_tomography_results covers one experiment: pass one channel or state")
+        settings = _settings_of(design, qubits)
+        results = [ExperimentResult(setting=s, expectation=float(x), total_counts=int(n), std_err=float(v))
+                   for s, x, n, v in zip(settings, e[0], c[0], se[0])]
+        if not calibrate_observables:
+            return results
+        from .observable_estimation import calibrate_observable_estimates_from_moments, operations_as_set
+        means, variances, counts, index = simulate_readout_calibration_batch(
+            design, conf, shots if calibration_shots is None else calibration_shots, symm_type=symm_type, seed=seed)
+        if np.any(index < 0):
+            raise ValueError("a design with an all-identity observable cannot be calibrated here: it has no calibration run")
+        calibrations = {operations_as_set(s.observable): (float(means[0, i]), float(variances[0, i]), int(counts[0, i]))
+                        for s, i in zip(settings, index)}
+        return calibrate_observable_estimates_from_moments(results, calibrations)
     if kind == "process":
         design = process_design(len(qubits), in_basis)
         simulate = simulate_grouped_process_tomography_batch if group_tpb_settings else simulate_process_tomography_batch
@@ -872,7 +1047,8 @@ def simulate_tomography_results(qubits, kind, truth, shots, in_basis="pauli", gr
 
 
 def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pauli_liouville", readout_flip=None, seed=None,
-                                        first_item=0, estimator="pgdb", groups=None, **estimator_kw):
+                                        first_item=0, estimator="pgdb", groups=None, confusion=None, symm_type=-1, calibrate=True,
+                                        calibration_shots=None, **estimator_kw):
     """The resident loop truth -> shots -> estimate -> fidelity to truth: the truth's transfer matrices are uploaded once,
     ``fbx_tomo_simulate_dev`` writes (expectations, counts) into HBM, the estimator's ``_dev`` form (``estimator`` "pgdb":
     ``trace_preserving``, ``mode``, ``max_iters`` by keyword as in ``pgdb_process_estimate_batch``; "linear_inv": no options)
@@ -880,7 +1056,13 @@ def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pa
     the truth.  Returns ``(chois [B, D, D], fidelity_to_truth [B])`` -- all that leaves the device; bit for bit what
     ``simulate_process_tomography_batch``, the batched estimator and ``distance_measures.process_fidelity_batch`` give when
     composed through the host.  ``groups`` (a ``Grouping``, a ``group_of`` array or a method name, as in
-    ``simulate_grouped_process_tomography_batch``): ``fbx_tomo_simulate_grouped_dev`` draws the shots instead, one set per group."""
+    ``simulate_grouped_process_tomography_batch``): ``fbx_tomo_simulate_grouped_dev`` draws the shots instead, one set per group.
+    ``confusion`` (a joint matrix [2^n, 2^n] or [B, 2^n, 2^n], instead of ``readout_flip``; ``groups`` defaults to "greedy"): the
+    chain becomes ``fbx_tomo_simulate_symmetrized_dev`` (``symm_type``) -> with ``calibrate``, ``fbx_tomo_simulate_calibration_dev``
+    (``calibration_shots``, default ``shots``; the same seed) and ``fbx_calibrate_expectations_dev`` with the calibration of every
+    (item, setting) -> the estimator -> the fidelity, resident as before and bit for bit what
+    ``simulate_symmetrized_process_tomography_batch``, ``simulate_readout_calibration_batch``,
+    ``observable_estimation.calibrate_expectations_batch`` and the estimator give when composed through the host."""
     if estimator not in _SIM_ESTIMATORS:
         raise ValueError(f"estimator must be one of {_SIM_ESTIMATORS}, not {estimator!r}")
     allowed = {"trace_preserving", "mode", "max_iters"} if estimator == "pgdb" else set()
@@ -890,19 +1072,47 @@ def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pa
     if mode not in ("converge", "fixed"):
         raise ValueError("mode must be 'converge' or 'fixed'")
     truth = _sim_process_truth(design, channels, rep)
+    if confusion is not None and groups is None:
+        groups = "greedy"
     grouping = None if groups is None else _sim_grouping(design, groups)
     B, m, n, D = truth.shape[0], design.m, design.n_qubits, design.dim ** 2
     shots, flips, seed, first_item = _sim_noise(B, n, shots, readout_flip, seed, first_item)
     if B == 0:
         raise ValueError("need a non-empty batch")
     lib, DB = _lib.lib(), _lib.DeviceBuffer
+    if confusion is not None:
+        if flips is not None:
+            raise ValueError("give the readout error as confusion (readout.confusion_from_flips) or as readout_flip, not both")
+        symm_type = _sim_symm_type(symm_type)
+        conf = _sim_confusion(B, n, confusion)
+        cal_shots = _sim_noise(B, n, shots if calibration_shots is None else calibration_shots, None, seed, first_item)[0]
+        if calibrate:
+            cal_paulis, cal_index = calibration_list(design)
+            n_cal = cal_paulis.shape[0]
+            flat_index = _flat_cal_index(cal_index, B, n_cal)
     d_truth, d_truth_c = DB.from_array(truth), DB.from_array(truth.astype(np.complex128))
     d_flips = DB.from_array(flips) if flips is not None else None
     d_e, d_c, d_status = DB(B * m * 8), DB(B * m * 8), DB(B * 4)
     d_choi, d_ptm, d_f = DB(B * D * D * 16), DB(B * D * D * 16), DB(B * 8)
     bufs = [b for b in (d_truth, d_truth_c, d_flips, d_e, d_c, d_status, d_choi, d_ptm, d_f) if b is not None]
     try:
-        if grouping is None:
+        if confusion is not None:
+            d_conf, d_se = DB.from_array(conf), DB(B * m * 8)
+            bufs += [d_conf, d_se]
+            _lib.check(lib.fbx_tomo_simulate_symmetrized_dev(design.handle, grouping.handle, B, d_truth.ptr, d_conf.ptr, symm_type,
+                                                             shots, seed, first_item, d_e.ptr, d_c.ptr, d_se.ptr, None, None, None,
+                                                             d_status.ptr))
+            if calibrate:
+                d_cm, d_cv, d_ci = DB(B * n_cal * 8), DB(B * n_cal * 8), DB.from_array(flat_index)
+                d_e2, d_se2, d_cst = DB(B * m * 8), DB(B * m * 8), DB(B * 4)
+                bufs += [d_cm, d_cv, d_ci, d_e2, d_se2, d_cst]
+                _lib.check(lib.fbx_tomo_simulate_calibration_dev(design.handle, B, d_conf.ptr, symm_type, cal_shots, seed, first_item,
+                                                                 d_cm.ptr, d_cv.ptr, None, None, d_cst.ptr))
+                # every (item, setting) has the calibration of its item: one "experiment" of B m settings and B n_cal calibrations
+                _lib.check(lib.fbx_calibrate_expectations_dev(1, B * m, d_e.ptr, d_se.ptr, d_ci.ptr, B * n_cal, d_cm.ptr, d_cv.ptr,
+                                                              d_e2.ptr, d_se2.ptr))
+                d_e = d_e2
+        elif grouping is None:
             _lib.check(lib.fbx_tomo_simulate_dev(design.handle, B, d_truth.ptr, shots, d_flips.ptr if d_flips else None, seed,
                                                  first_item, d_e.ptr, d_c.ptr, None, None, d_status.ptr))
         else:
@@ -920,6 +1130,8 @@ def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pa
         _lib.check(lib.fbx_process_fidelity_dev(n, B, d_truth_c.ptr, d_ptm.ptr, None, d_f.ptr))
         _lib.synchronize()
         status = d_status.to_array(np.int32, (B,))
+        if confusion is not None and calibrate:
+            status |= d_cst.to_array(np.int32, (B,))
         choi = d_choi.to_array(np.complex128, (B, D, D))
         fid = d_f.to_array(np.float64, (B,))
     finally:
@@ -928,6 +1140,6 @@ def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pa
     bad = np.flatnonzero(status)
     if bad.size:
         raise ValueError(f"simulate_and_estimate_process_batch: item {int(bad[0])} cannot be simulated: a truth entry that is not "
-                         f"finite or a readout_flip value outside [0, 1]" + (" or outcome probabilities of a group that do not sum "
+                         f"finite or a readout_flip value or confusion entry outside [0, 1]" + (" or outcome probabilities of a group that do not sum "
                          f"to a positive finite number" if grouping is not None else "") + f" ({bad.size} such item(s) in the batch)")
     return choi, fid

@@ -719,6 +719,81 @@ int fbx_tomo_simulate_grouped_dev(const fbx_design* design, const fbx_grouping* 
                                   double* d_expect_out, double* d_counts_out, double* d_std_err_out, double* d_exact_out,
                                   double* d_prob_out, uint32_t* d_hist_out, int32_t* d_status_out);
 
+/* ---------------------------------------------------------------- symmetrized readout and calibration under a joint confusion matrix
+ * The two defaults of the reference's do_tomography that the calls above do not model: symm_type = -1 (every group is measured
+ * under exhaustive readout symmetrization: every combination of pre-measurement bit flips, undone in the record) and
+ * calibrate_observables = True (every distinct observable is measured on its +1 eigenstate with the same symmetrization, and
+ * every expectation is divided by that calibration: fbx_calibrate_expectations).  The readout error is a JOINT confusion matrix,
+ * so correlated (crosstalk) errors are covered; fbx/readout.py estimates such matrices from shots.
+ *
+ * design, grouping, truth, seed, first_item, the limits on the designs and the outputs expect_out / counts_out / std_err_out /
+ * exact_out [B][m], hist_out [B][G][2^n] uint32 and status_out [B] are those of fbx_tomo_simulate_grouped.  confusion [B][2^n][2^n]
+ * doubles, [drawn][read], rows summing to 1; bit t of an index is qubit n - 1 - t (the outcome convention of
+ * fbx_tomo_simulate_grouped, so that index = the bitstring read as a binary number, qubit 0 first).  prob_out
+ * [B][G][2^n][2^n]: row f of a unit is the distribution of pattern f (below).  Every output may be NULL, not all of them;
+ * n_shots == 0 gives exact_out and prob_out only.  A unit is (item b, group g); U_g = the union of the parity masks of the
+ * group's members, w = popcount(U_g):
+ *  1. PATTERNS.  symm_type = -1: the 2^w flip masks f that are subsets of U_g; symm_type = 0: f = 0 alone (the plain correlated
+ *     readout error, without symmetrization).  Qubits outside U_g are never flipped; they are still drawn and still pass through
+ *     the matrix (their state matters to crosstalk), and their read bits are ignored by the parities.  symm_type 1, 2, 3 (the
+ *     reference's orthogonal arrays): FBX_ERR_UNSUPPORTED.
+ *  2. SHOTS PER PATTERN.  s = floor(n_shots / patterns) for the unit, n_shots being the total of a group; the shots a member
+ *     is estimated from are N = s x patterns <= n_shots, which counts_out reports -- it CAN DIFFER between the groups of one
+ *     call.  (The floor is this library's rule: pyquil's run_symmetrized_readout, which the reference calls, was not at hand to
+ *     compare against.)  A call in which s would be 0 or >= 2^29 for any group is refused.
+ *  3. DISTRIBUTIONS.  p = the ideal outcome distribution of the group (steps 1-2 of fbx_tomo_simulate_grouped without flips,
+ *     the same code).  The un-flipped record of pattern f has q_f(r) = sum_o p(o) C[o ^ f][r ^ f], summed in ascending o with one
+ *     fused multiply-add per term from 0.  prob_out[f] = q_f, unclamped; a zero row for a mask that is not a pattern.
+ *  4. THE STREAM, per pattern, as step 3-4 of fbx_tomo_simulate_grouped: c_r = the running sum of max(q_f(r'), 0) in outcome
+ *     order, thr_r = floor(c_r / c_last 2^32) for every outcome but the last; shot t (0 <= t < s) of pattern f reads word t & 3 of
+ *     the Philox4x32-10 block with counter (gid low, gid high, g, (f << 27) | (t >> 2)) -- f the n-bit mask itself -- and key
+ *     (seed low ^ 0x544F4D53, seed high), gid = first_item + b; the tag "TOMS" keeps the stream apart from the others under one
+ *     seed.  The outcome of a word is the number of thresholds <= the word.  hist_out = the integer sum of the patterns'
+ *     histograms (of the un-flipped record).
+ *  5. MEMBERS.  k_plus, k_minus and the integer formulas of fbx_tomo_simulate_grouped on the merged histogram with N = s x
+ *     patterns.
+ *  6. EXACT MEANS.  exact_out[k] = c_k sum_r (-1)^{|r & z_k|} qbar(r), r ascending, qbar(r) = (the sum of q_f(r) over the patterns
+ *     in ascending f) / patterns: the mean of what is measured, matrix included (not the value fbx_tomo_simulate writes).
+ * A value depends on (seed, gid, g, f, t), the distributions and s only: not on B or on how lanes share the work.
+ * A poisoned item -- a non-finite truth entry, a confusion entry that is not finite or outside [0, 1], or a pattern whose c_last
+ * is not a positive finite number -- gets status 1, NaN in expect_out / std_err_out / exact_out / prob_out (all 2^n rows), N in
+ * counts_out and 0 in hist_out, for all its groups; its neighbours are untouched.  Rows are NOT required to sum to 1 here: the
+ * thresholds normalise by c_last (the Python layer refuses rows that do not).
+ * Refusals, before any buffer is touched: the bad arguments of fbx_tomo_simulate_grouped, NULL confusion, symm_type outside
+ * [-1, 3], s == 0 or s >= 2^29 for a group (FBX_ERR_BAD_ARG); symm_type 1..3 (FBX_ERR_UNSUPPORTED).  B == 0: nothing is done.
+ *
+ * fbx_tomo_calibration_list: the calibrations of a design are its distinct non-identity Pauli indices (base-4 digits, qubit 0
+ * most significant) in order of first appearance in the caller's setting order.  n_cal_out receives their number, cal_pauli_out
+ * (room for m, may be NULL) the indices, cal_index_out [m] (may be NULL) the calibration of every setting, -1 for an
+ * all-identity observable.  The list is made on the first call that needs it (this one or fbx_tomo_simulate_calibration[_dev])
+ * and kept on the design: that first call uploads the masks with one blocking copy.
+ *
+ * fbx_tomo_simulate_calibration: a unit is (item b, calibration c) with the parity mask z_c of its Pauli.  The drawn outcome is
+ * all zeros -- the +1 eigenstate on the support and |0> elsewhere, as get_calibration_program prepares it -- so p = (1, 0, ...)
+ * and q_f(r) = C[f][r ^ f]; the patterns are the subsets of z_c (f = 0 alone for symm_type = 0); s = floor(cal_shots / patterns)
+ * with the refusals above; the stream is that of step 4 with counter (gid low, gid high, c, (f << 27) | (t >> 2)) and key (seed low
+ * ^ 0x544F4D43, seed high) ("TOMC").  Outputs [B][n_cal], each may be NULL, not all: cal_mean_out = (k_plus - k_minus) / N,
+ * cal_var_out = (double) (4 k_plus k_minus) / N / N / N (the reference's var / N of the +-1 values), cal_exact_out as step 6 with
+ * coefficient 1, cal_counts_out = N; cal_shots == 0 gives cal_exact_out only.  Poison as above (there is no truth): NaN in the
+ * mean, the variance and the exact value, N in the counts.
+ * The _dev forms enqueue on the calling thread's stream and do not synchronise. */
+int fbx_tomo_simulate_symmetrized(const fbx_design* design, const fbx_grouping* grouping, int64_t B, const double* truth,
+                                  const double* confusion, int symm_type, int64_t n_shots, uint64_t seed, int64_t first_item,
+                                  double* expect_out, double* counts_out, double* std_err_out, double* exact_out, double* prob_out,
+                                  uint32_t* hist_out, int32_t* status_out);
+int fbx_tomo_simulate_symmetrized_dev(const fbx_design* design, const fbx_grouping* grouping, int64_t B, const double* d_truth,
+                                      const double* d_confusion, int symm_type, int64_t n_shots, uint64_t seed, int64_t first_item,
+                                      double* d_expect_out, double* d_counts_out, double* d_std_err_out, double* d_exact_out,
+                                      double* d_prob_out, uint32_t* d_hist_out, int32_t* d_status_out);
+int fbx_tomo_calibration_list(const fbx_design* design, int32_t* n_cal_out, int32_t* cal_pauli_out, int32_t* cal_index_out);
+int fbx_tomo_simulate_calibration(const fbx_design* design, int64_t B, const double* confusion, int symm_type, int64_t cal_shots,
+                                  uint64_t seed, int64_t first_item, double* cal_mean_out, double* cal_var_out,
+                                  double* cal_exact_out, double* cal_counts_out, int32_t* status_out);
+int fbx_tomo_simulate_calibration_dev(const fbx_design* design, int64_t B, const double* d_confusion, int symm_type,
+                                      int64_t cal_shots, uint64_t seed, int64_t first_item, double* d_cal_mean_out,
+                                      double* d_cal_var_out, double* d_cal_exact_out, double* d_cal_counts_out,
+                                      int32_t* d_status_out);
+
 /* ---------------------------------------------------------------- curve fits (analysis/fitting.py, randomized_benchmarking.py,
  * qubit_spectroscopy.py)
  * fbx_curve_fit: B independent weighted non-linear least-squares fits, one per GPU lane, of the four models of

@@ -1114,6 +1114,21 @@ proj_choi3_kernel(int kind, long long B, const double* __restrict__ in, double* 
         const double* p = in + ((item * D + row) * D + col) * 2;
         x.re[e] = p[0]; x.im[e] = p[1];
     }
+    // a non-finite item: NaN in every entry, the count 1 for the Dykstra kinds, nothing projected (proj_choi_body, fbx_superop.hip)
+    int nonfinite = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) nonfinite |= !(isfinite(x.re[e]) && isfinite(x.im[e]));
+    if (bsum(nonfinite ? 1.0 : 0.0, L) != 0.0) {               // (not __syncthreads_or: its static LDS word would not fit beside Lds::bytes())
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int row = 2 * I + (e >> 1), col = 2 * J + (e & 1);
+            double* p = out + ((item * D + row) * D + col) * 2;
+            p[0] = nan; p[1] = nan;
+        }
+        if (t == 0 && iters_out) iters_out[item] = kind >= FBX_PROJ_PHYSICAL_TP ? 1 : 0;
+        return;
+    }
     int iters = 0, sweeps = 0;
     Blk y;
     if (kind == FBX_PROJ_CP) y = proj_cp(x, L, t, sweeps);

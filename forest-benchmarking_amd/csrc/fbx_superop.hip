@@ -26,6 +26,19 @@ __device__ __forceinline__ void proj_choi_body(char* smem, int kind, long long B
     __syncthreads();
     const Blk x = blk_load<D, LD>(L.Mw, lane);
     __syncthreads();
+    // A non-finite item gives NaN in every entry and, for the Dykstra kinds, the count 1 (include/fbx.h): the eigensolver's
+    // stopping test is false on a NaN or an infinite norm, so it would hand back the diagonal with the identity, and the CP
+    // projection of a matrix with a NaN off its diagonal would be the finite max(diag, 0).  Nothing is projected.
+    int nonfinite = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) nonfinite |= !(isfinite(x.re[e]) && isfinite(x.im[e]));
+    if (__ballot(nonfinite) != 0) {                            // one wavefront per item
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+        double* o = out + item * (long long)D * D * 2;
+        for (int idx = lane; idx < 2 * D * D; idx += 64) o[idx] = nan;
+        if (lane == 0 && iters_out) iters_out[item] = kind >= FBX_PROJ_PHYSICAL_TP ? 1 : 0;
+        return;
+    }
     int iters = 0, sweeps = 0;
     Blk y;
     if (kind == FBX_PROJ_CP) y = proj_cp_blk<NQ>(x, L, lane, sweeps);

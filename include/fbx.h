@@ -332,7 +332,13 @@ int fbx_kraus_sweep_dev(int n_qubits, int64_t B, int K, const double* d_kraus,
                         double* d_chi_out, double* d_fid_out);
 
 /* Choi projections (operator_tools/project_superoperators.py:19-144): out[B][D][D];
- * iters_out[B] (may be NULL) = Dykstra iterations for the PHYSICAL kinds. */
+ * iters_out[B] (may be NULL) = Dykstra iterations for the PHYSICAL kinds, 0 for the others.
+ * Non-finite input: an item with a NaN or an Inf in any entry is not projected.  Every entry of its output is NaN, its count is
+ * 1 for the PHYSICAL kinds (the iteration in which the reference's check_finite raises), the call returns FBX_OK, and every
+ * other item is bit-identical to the same call with a finite matrix in that place.  (Left to the arithmetic, the eigensolver's
+ * stopping test is false on a NaN or an infinite norm: the CP projection of a matrix with a NaN off its diagonal would be the
+ * finite max(diag, 0).)  The input need not be Hermitian: CP projects its Hermitian part, TNI Hermitises the partial trace for
+ * the eigensolver only. */
 int fbx_proj_choi(int proj_kind, int n_qubits, int64_t B, const double* choi, double* out,
                   int32_t* iters_out);
 

@@ -15,7 +15,7 @@
 // its XOR with the Z column by XOR-ing the run with itself shifted by the distance of the two columns.  Counts are integers; lane 0
 // turns them into moments and advances the recursion, and once an item has ended (and no moments are asked for) the remaining
 // depths of that item are not read.
-#include "fbx_common.hpp"
+#include "fbx_sim_shared.hpp"      // rpe_moment, shared with fbx_rpe_sim.hip
 
 namespace fbx {
 
@@ -154,15 +154,6 @@ __device__ __forceinline__ void rpe_count_record(const uint8_t* __restrict__ bit
         c1 += a;
         if (zcol >= 0) c2 += a ^ (bits[s * NQ + zcol] & 1);
     }
-}
-
-// counts of -1 outcomes -> mean of the +-1 values and the variance of that mean, fbx_shots_to_moments' formulas with coef = 1
-__device__ __forceinline__ void rpe_moment(long long n_minus, long long n_shots, double& mean, double& var) {
-#pragma clang fp contract(off)
-    const long long n_plus = n_shots - n_minus;
-    const double m = ((double)n_plus - (double)n_minus) / (double)n_shots;
-    mean = m;
-    var = (1.0 - m * m) / (double)n_shots;
 }
 
 template <int NQ>

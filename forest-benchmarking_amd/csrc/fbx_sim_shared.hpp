@@ -1,6 +1,7 @@
 // fbx_sim_shared.hpp -- device code that two translation units evaluate and whose results the tests pin bit for bit: the shot
 // counting of the simulated experiments (fbx_tomo_sim.hip, fbx_dfe.hip), the exact mean of a tomography setting (fbx_tomo_sim.hip,
-// fbx_tomo_sim_grouped.hip) and the direct-fidelity formula (fbx_shots.hip, fbx_dfe.hip).
+// fbx_tomo_sim_grouped.hip), the direct-fidelity formula (fbx_shots.hip, fbx_dfe.hip) and the moments of a robust-phase-estimation
+// record (fbx_rpe.hip, fbx_rpe_sim.hip).
 #pragma once
 #include "fbx_common.hpp"
 
@@ -97,6 +98,16 @@ __device__ inline double tomo_mean(const DesignDev& des, const double* __restric
         if (T == 0) break;
     }
     return mu;
+}
+
+// counts of -1 outcomes -> mean of the +-1 values and the variance of that mean, fbx_shots_to_moments' formulas with coef = 1
+// (fbx_rpe.hip from measured records, fbx_rpe_sim.hip from simulated ones)
+__device__ __forceinline__ void rpe_moment(long long n_minus, long long n_shots, double& mean, double& var) {
+#pragma clang fp contract(off)
+    const long long n_plus = n_shots - n_minus;
+    const double m = ((double)n_plus - (double)n_minus) / (double)n_shots;
+    mean = m;
+    var = (1.0 - m * m) / (double)n_shots;
 }
 
 // direct fidelity estimate (direct_fidelity_estimation.py:291-307) of one experiment by one wavefront: the mean of the m

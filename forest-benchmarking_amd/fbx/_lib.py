@@ -30,6 +30,7 @@ CLIFFORD_NONE = 0xFFFFFFFF      # no element: "no interleaved gate" / "no such i
 RB_MAX_NOISE_PTMS = 16
 DFE_MAX_CLASSES = 16
 DFE_NOISELESS = 255             # noise class of a gate without noise (include/fbx.h)
+RPE_SIM_LANE_MIN_UNITS = 131072 # from this many (item, depth, basis) units on a lane takes a unit (csrc/fbx_rpe_sim.hip)
 
 
 class FbxError(RuntimeError):
@@ -198,6 +199,10 @@ PROTOTYPES = {
     "fbx_rpe_from_shots_dev": [C.c_int, _i64, C.c_int, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
     "fbx_circular_stats": [_i64, _i64, _dp, _dp, _dp, _ip],
     "fbx_circular_stats_dev": [_i64, _i64, _vp, _vp, _vp, _vp],
+    "fbx_rpe_simulate": [C.c_int, _i64, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _ip, C.c_uint64, _i64,
+                         _dp, _u32p, _dp, _u8p, _u8p, _ip],
+    "fbx_rpe_simulate_dev": [C.c_int, _i64, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _ip, C.c_uint64, _i64,
+                             _vp, _vp, _vp, _vp, _vp, _vp],
     "fbx_bit_histogram": [C.c_int, _i64, _i64, _u8p, C.c_int, _u8p, C.c_int, _u8p, C.c_int, C.POINTER(C.c_int64)],
     "fbx_bit_histogram_dev": [C.c_int, _i64, _i64, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp],
     "fbx_counts_to_frequencies": [_i64, C.POINTER(C.c_int64), _i64, _dp],

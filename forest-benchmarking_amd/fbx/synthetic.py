@@ -590,3 +590,126 @@ def restate_qv_gate_errors(B, trajectories, L, gate_error, seed, first_item=0):
         k = np.uint64(1) + ((second * np.uint64(15)) >> np.uint64(32))
         out[b] = np.where(errs, k, np.uint64(0)).astype(np.uint8)
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# fbx_rpe_simulate (include/fbx.h) on the host: the distributions mirrored in numpy, the shots restated in integers.
+# --------------------------------------------------------------------------------------------------
+RPE_SIM_KEY_TAG = 0x52504553             # "RPES": the shots of fbx_rpe_simulate
+
+
+def pauli_transfer_matrix(kraus_ops):
+    """The real Pauli transfer matrix R[i, j] = sum_k tr[P_i K_k P_j K_k^+] / d of a channel given by its Kraus operators (one
+    d x d matrix = a unitary), in numpy: Pauli indices in base 4 with qubit 0 most significant, the order of include/fbx.h."""
+    ks = np.asarray(kraus_ops, dtype=complex)
+    ks = ks[None] if ks.ndim == 2 else ks
+    d = ks.shape[-1]
+    n = int(round(np.log2(d)))
+    ps = np.array([pauli_matrix(codes) for codes in itertools.product(range(4), repeat=n)])
+    out = np.einsum('iab,kbc,jcd,kad->ij', ps, ks, ps, ks.conj()) / d
+    return np.ascontiguousarray(out.real)
+
+
+def pauli_vector_of_state(rho):
+    """tr[P_k rho] for every Pauli index k (the ``init`` of fbx_rpe_simulate); ``rho`` a density matrix or a state vector."""
+    rho = np.asarray(rho, dtype=complex)
+    rho = np.outer(rho, rho.conj()) if rho.ndim == 1 else rho
+    n = int(round(np.log2(rho.shape[0])))
+    return np.array([np.trace(pauli_matrix(codes) @ rho).real for codes in itertools.product(range(4), repeat=n)])
+
+
+def _rpe_sim_indices(n, xy_qubit, z_qubit):
+    sh_xy = 2 * (n - 1 - xy_qubit)
+    iz = 0 if z_qubit is None else 3 << (2 * (n - 1 - z_qubit))
+    return [1 << sh_xy, 2 << sh_xy], iz
+
+
+def rpe_distributions(gate_ptm, num_depths, prep_ptm=None, meas_ptm=None, init=None, xy_qubit=0, z_qubit=None, flips=None):
+    """Steps 1-2 of the contract of ``fbx_rpe_simulate`` (include/fbx.h) in numpy float64: ``gate_ptm [B, D, D]``, ``prep_ptm`` /
+    ``meas_ptm`` ``[D, D]``, ``[B, D, D]`` or None, ``init [D]`` (None: |+> on every qubit), ``flips [n, 2]``, ``[B, n, 2]`` or None.
+    G^(2^j) is ``np.linalg.matrix_power``.  Returns ``prob [B, K, 2, M]``, M = 4 with a partner (outcome 2 s + t) and 2 without;
+    the sums are numpy's, so the device agrees within rounding, not bit for bit."""
+    G = np.asarray(gate_ptm, dtype=np.float64)
+    G = G[None] if G.ndim == 2 else G
+    B, D = G.shape[0], G.shape[-1]
+    n = {4: 1, 16: 2}[D]
+    K = int(num_depths)
+    if init is None:
+        init = pauli_vector_of_state(np.full(1 << n, 2.0 ** (-n / 2)))
+    eye = np.eye(D)
+    prep = np.broadcast_to(eye if prep_ptm is None else np.asarray(prep_ptm, dtype=np.float64), (B, D, D))
+    meas = np.broadcast_to(eye if meas_ptm is None else np.asarray(meas_ptm, dtype=np.float64), (B, D, D))
+    fl = None if flips is None else np.broadcast_to(np.asarray(flips, dtype=np.float64), (B, n, 2))
+    iP, iZ = _rpe_sim_indices(n, xy_qubit, z_qubit)
+    M = 2 if z_qubit is None else 4
+    out = np.empty((B, K, 2, M))
+    for b in range(B):
+        w = prep[b] @ np.asarray(init, dtype=np.float64)
+        for j in range(K):
+            v = meas[b] @ (np.linalg.matrix_power(G[b], 2 ** j) @ w)
+            for basis in range(2):
+                vP = v[iP[basis]]
+                if z_qubit is None:
+                    p = np.array([(v[0] + vP) * 0.5, (v[0] - vP) * 0.5])
+                    if fl is not None:
+                        f0, f1 = fl[b, xy_qubit]
+                        p = np.array([(1 - f0) * p[0] + f1 * p[1], f0 * p[0] + (1 - f1) * p[1]])
+                else:
+                    vZ, vPZ = v[iZ], v[iP[basis] | iZ]
+                    p = np.array([[v[0] + vP + vZ + vPZ, v[0] + vP - vZ - vPZ],
+                                  [v[0] - vP + vZ - vPZ, v[0] - vP - vZ + vPZ]]) * 0.25             # [s, t]
+                    if fl is not None:
+                        (f0, f1), (g0, g1) = fl[b, xy_qubit], fl[b, z_qubit]
+                        p = np.array([[1 - f0, f1], [f0, 1 - f1]]) @ p @ np.array([[1 - g0, g1], [g0, 1 - g1]]).T
+                    p = p.reshape(4)
+                out[b, j, basis] = p
+    return out
+
+
+def restate_rpe_counts(probs, n_shots, seed, first_item=0):
+    """Steps 3-4 of the contract of ``fbx_rpe_simulate`` (include/fbx.h) restated on the host, in integers, from the distributions it
+    reports: ``probs [B, K, 2, M]`` (M = 2 or 4), ``n_shots [K]`` (or one number).  Per (item, depth j, basis): c = cumsum(max(p,
+    0)) in outcome order, thr_o = floor(c_o / c_last 2^32) for every outcome but the last; shot s reads word ``s & 3`` of the
+    Philox4x32-10 block with counter (gid low, gid high, 2 j + basis, s >> 2) and key (seed low ^ 0x52504553, seed high), gid =
+    first_item + item; its outcome is the number of thresholds <= the word.  Returns ``(hist [B, K, 2, M] int64, moments [8, B,
+    K])``: the planes x, y, xz, yz and their variances, mean = (n_plus - n_minus) / N and (1 - mean^2) / N with n_minus the
+    shots of odd parity (s for x / y, s ^ t for xz / yz; outcome = 2 s + t); without a partner (M = 2) the xz / yz planes are NaN."""
+    p = np.asarray(probs, dtype=np.float64)
+    if p.ndim != 4 or p.shape[2] != 2 or p.shape[3] not in (2, 4):
+        raise ValueError("need probs [B, K, 2, M] with M = 2 or 4")
+    B, K, _, M = p.shape
+    shots = np.broadcast_to(np.asarray(n_shots, dtype=np.int64), (K,))
+    seed, first_item = int(seed) & (2 ** 64 - 1), int(first_item)
+    if shots.min() < 1 or shots.max() >= 2 ** 31 or first_item < 0:
+        raise ValueError("need 1 <= n_shots < 2^31 and first_item >= 0")
+    c = np.cumsum(np.where(p < 0.0, 0.0, p), axis=3)                    # one addition per outcome, in outcome order
+    if not np.all((c[..., -1] > 0.0) & np.isfinite(c[..., -1])):
+        raise ValueError("a distribution whose clamped sum is not a positive finite number (a poisoned item) cannot be restated")
+    thr = np.floor(c[..., :-1] / c[..., -1:] * 2.0 ** 32).astype(np.uint64)
+    k0, k1 = (seed & 0xFFFFFFFF) ^ RPE_SIM_KEY_TAG, seed >> 32
+    gid = first_item + np.arange(B, dtype=np.uint64)
+    g0, g1 = gid & np.uint64(0xFFFFFFFF), gid >> np.uint64(32)
+    hist = np.zeros((B, K, 2, M), dtype=np.int64)
+    for j in range(K):
+        N = int(shots[j])
+        blocks = np.arange((N + 3) // 4, dtype=np.uint64)
+        rows = max(1, (1 << 20) // len(blocks))                          # items per pass: about 2^20 blocks at a time
+        for basis in range(2):
+            for lo in range(0, B, rows):
+                sl = slice(lo, lo + rows)
+                words = _philox4x32_10(g0[sl, None], g1[sl, None], np.uint64(2 * j + basis), blocks[None, :], k0, k1)
+                w = np.stack(np.broadcast_arrays(*words), axis=2).reshape(len(g0[sl]), -1)[:, :N]    # shot s = word s & 3 of block s >> 2
+                outcome = (thr[sl, j, basis, None, :] <= w[:, :, None]).sum(axis=2)
+                for o in range(M):
+                    hist[sl, j, basis, o] = (outcome == o).sum(axis=1)
+    Nf = shots.astype(np.float64)[None, :]
+    moments = np.full((8, B, K), np.nan)
+    for basis in range(2):
+        h = hist[:, :, basis, :]
+        odd = [h[..., 1] if M == 2 else h[..., 2] + h[..., 3]] + ([h[..., 1] + h[..., 2]] if M == 4 else [])
+        for which, n_minus in enumerate(odd):
+            n_plus = shots[None, :] - n_minus
+            mean = (n_plus.astype(np.float64) - n_minus.astype(np.float64)) / Nf
+            moments[2 * which + basis] = mean
+            moments[4 + 2 * which + basis] = (1.0 - mean * mean) / Nf
+    return hist, moments

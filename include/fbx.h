@@ -928,6 +928,67 @@ int fbx_circular_stats(int64_t R, int64_t B, const double* angles, double* mean_
 int fbx_circular_stats_dev(int64_t R, int64_t B, const double* d_angles, double* d_mean_out, double* d_std_out,
                            int32_t* d_nan_count_out);
 
+/* ---------------------------------------------------------------- simulated robust phase estimation: noisy gates to shot counts
+ * What generate_rpe_experiments + acquire_rpe_data (robust_phase_estimation.py:152-307) get from a QVM, for B experiments of K
+ * depths at once.  The gate is a Pauli transfer matrix, so depth 2^j is j squarings and every depth the analysis accepts (K in
+ * 1..62) can be simulated.  n_qubits is 1 or 2, D = 4^n_qubits; Pauli order and normalisation are those of fbx_rb_simulate: a
+ * Pauli vector has component k = tr[P_k rho] (identity component 1), an index is read in base 4 with qubit 0 most significant
+ * (I, X, Y, Z = 0, 1, 2, 3), and a matrix is row-major.
+ *
+ * Inputs.  gate_ptm [B][D][D].  prep_ptm and meas_ptm, the change of basis and its inverse, given separately so that each may
+ * be noisy: [D][D] shared by the batch, or [B][D][D] when basis_per_item != 0; NULL = the identity.  init [D]: the Pauli vector
+ * of the input state; NULL = |+> on every qubit.  xy_qubit: the qubit measured in X and in Y; z_qubit: a partner measured in Z, or
+ * -1 for none.  flips [B][n_qubits][2] or NULL: [q][0] = P(read 1 | 0), [q][1] = P(read 0 | 1) of qubit q, independent per bit,
+ * as in fbx_tomo_simulate.  n_shots [K]: the shots at depth 2^j, each >= 1; a HOST array in both forms (its K numbers travel
+ * with the launch).  seed, first_item: as in fbx_tomo_simulate.
+ *
+ * Outputs, each may be NULL, not all.  M = 4 outcomes with a partner, 2 without; basis index 0 = X, 1 = Y.
+ *   prob_out    [B][K][2][M] double     hist_out [B][K][2][M] uint32     status_out [B] int32
+ *   moments_out [8][B][K] double: the planes x, y, xz, yz, var x, var y, var xz, var yz -- what fbx_rpe_phase_dev takes with
+ *               errors_are_variances = 1; without a partner the four xz / yz planes are NaN
+ *   x_bits_out, y_bits_out [B][K][S][n_qubits] bytes: the records fbx_rpe_from_shots reads with col = xy_qubit and zcol =
+ *               z_qubit.  Only when every n_shots[j] equals one S; asked for with a ragged schedule: FBX_ERR_BAD_ARG.
+ *
+ * Per item b, depth j and basis P in {X, Y}:
+ *  1. FINAL PAULI VECTOR.  v_j = meas G^(2^j) prep init, all in fp64: w = prep init once, G^(2^j) by squaring the matrix of
+ *     depth j - 1, u = G^(2^j) w, v = meas u; a NULL factor is skipped.  Every row of every product is one chain of fused
+ *     multiply-adds in ascending column order from 0.0.
+ *  2. DISTRIBUTION.  The bits are (s, t): s belongs to xy_qubit, measured in P, t to z_qubit, measured in Z; bit value 1 =
+ *     eigenvalue -1.  With v_I the identity component of v_j (1 for a trace-preserving map; a map that loses trace loses it
+ *     here), outcome o = 2 s + t has
+ *         p(s, t) = (v_I + (-1)^s <P_a> + (-1)^t <Z_b> + (-1)^(s+t) <P_a Z_b>) / 4,
+ *     and without a partner outcome o = s has p(s) = (v_I + (-1)^s <P_a>) / 2; <.> are the components of v_j.  Then per
+ *     measured bit the confusion matrix of its qubit's flips, exactly as step 2 of fbx_tomo_simulate_grouped.  prob_out
+ *     receives this p, unclamped, flips included: it is what a host check restates the shots from.
+ *  3. SHOTS.  c_o = the running sum of max(p(o'), 0) in outcome order; thr_o = floor(c_o / c_last 2^32) for every outcome but
+ *     the last.  Shot s of N = n_shots[j] reads word s & 3 of the Philox4x32-10 block with counter (gid low, gid high, 2 j +
+ *     basis, s >> 2) and key (seed low ^ 0x52504553, seed high), gid = first_item + b; the tag "RPES" keeps the stream apart
+ *     from the tomography simulators' under one seed.  The outcome of a word is the number of thresholds <= the word; hist_out
+ *     counts the outcomes.  X and XZ of a depth are read off the SAME shots, as the grouped settings of
+ *     generate_rpe_experiments are: the post-selected sums x +- xz see that correlation.
+ *  4. MOMENTS.  With n_minus the shots of odd parity -- s for x / y, s ^ t for xz / yz -- mean = ((N - n_minus) - n_minus) / N
+ *     and the variance of the mean (1 - mean^2) / N, the formulas of fbx_rpe_from_shots, without fused multiply-adds.
+ *  5. RECORDS.  Shot s of the record has column xy_qubit = s, column z_qubit = t and 0 in any other column.
+ * A value depends on (seed, gid, j, basis), the item's inputs and n_shots[j] only: not on B, the item's position or the launch
+ * shape (csrc/fbx_rpe_sim.hip has two work splits for the shots, chosen by B K alone).
+ *
+ * A poisoned item -- a non-finite entry of its gate, of init or of the prep / meas it uses, a flip outside [0, 1] or NaN, or a
+ * distribution whose c_last is not a positive finite number (an all-zero matrix, a power that overflows) -- gets status 1, NaN in
+ * prob_out and moments_out, 0 in hist_out and the records, at ALL its depths; its neighbours are untouched.
+ * n_qubits >= 3 and K > 62: FBX_ERR_UNSUPPORTED.  n_qubits < 1, K < 1, a negative size, first_item < 0, NULL gate_ptm or
+ * n_shots, an n_shots entry below 1, xy_qubit outside the gate, z_qubit neither -1 nor another qubit of the gate, every output
+ * NULL, records with a ragged schedule: FBX_ERR_BAD_ARG before any buffer is touched.  B == 0: nothing is done.
+ * The _dev form enqueues on the calling thread's stream and does not synchronise. */
+int fbx_rpe_simulate(int n_qubits, int64_t B, int K, const double* gate_ptm, const double* prep_ptm, const double* meas_ptm,
+                     int basis_per_item, const double* init, int xy_qubit, int z_qubit, const double* flips, const int32_t* n_shots,
+                     uint64_t seed, int64_t first_item, double* prob_out, uint32_t* hist_out, double* moments_out,
+                     uint8_t* x_bits_out, uint8_t* y_bits_out, int32_t* status_out);
+int fbx_rpe_simulate_dev(int n_qubits, int64_t B, int K, const double* d_gate_ptm, const double* d_prep_ptm,
+                         const double* d_meas_ptm, int basis_per_item, const double* d_init, int xy_qubit, int z_qubit,
+                         const double* d_flips, const int32_t* n_shots, uint64_t seed, int64_t first_item, double* d_prob_out,
+                         uint32_t* d_hist_out, double* d_moments_out, uint8_t* d_x_bits_out, uint8_t* d_y_bits_out,
+                         int32_t* d_status_out);
+
 /* ---------------------------------------------------------------- histograms of measured bitstrings
  * How often each bitstring, or each Hamming weight, occurred in every one of B records: the reduction under the joint readout
  * confusion matrices (readout.py:69-180, 236-335: row = the prepared string, one record per row), the ripple-carry adder's success

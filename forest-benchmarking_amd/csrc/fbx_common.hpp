@@ -106,6 +106,19 @@ struct DevBuf {
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
+// The per-item status [B] of a `_dev` launcher: the caller's buffer, or the status when the caller does not want it (stream
+// order protects it)
+struct StatusBuf {
+    int32_t* p = nullptr;
+    int take(int32_t* callers, int64_t B) {
+        p = callers;
+        if (!p) { FBX_TRY(scratch.alloc(sizeof(int32_t) * (size_t)B)); p = scratch.as<int32_t>(); }
+        return FBX_OK;
+    }
+private:
+    DevBuf scratch;
+};
+
 // Staging of a host-pointer entry point, all of it on the calling thread's stream(): in() uploads, out() / out_opt() reserve
 // a device block for a result and remember where it goes, the entry point calls its `_dev` form, and `return io.finish();`
 // downloads every registered result in the order it was registered and waits for the stream.  Leaving any other way -- a

@@ -10,7 +10,7 @@
 //   propagate_kernel   the observable of setting k walked backwards: per noise class the number of gates it touches, and the
 //                      ideal expectation of the Pauli it arrives as in the setting's product in-state.
 //   dfe_sim_kernel     unit = (item b, setting k): the mean as a product of attenuations, then the shot counting of
-//                      fbx_tomo_simulate (tomo_count, fbx_sim_shared.hpp) under a key tag of its own; a lane per unit from
+//                      fbx_tomo_simulate (sim_bernoulli_unit, fbx_sim_shared.hpp) under a key tag of its own; a lane per unit from
 //                      FBX_TOMO_LANE_MIN_UNITS units on, a wavefront per unit below, the same bits either way.
 //   dfe_fidelity_kernel  dfe_item (fbx_sim_shared.hpp) with d = 2^n as a double, for the resident chain.
 // The walks cost about twenty integer instructions per gate and lane and read nothing but the gate words (from L2 / the scalar
@@ -187,44 +187,15 @@ dfe_sim_kernel(int n, long long m, int K, const int8_t* __restrict__ sigma, cons
     if (u >= units) return;
     const long long b = u / m, k = u - b * m;
     const double coef = (!calibration && (obs_sign[k] & 1u)) ? -1.0 : 1.0;     // the calibration measures the observable with coefficient 1
-    const double nd = (double)n_shots;
     if (status[b]) {
-        if (!LANE && lane != 0) return;
-        const double nan = __builtin_nan("");
-        if (expect_out) expect_out[u] = nan;
-        if (std_err_out) std_err_out[u] = nan;
-        if (exact_out) exact_out[u] = nan;
-        if (counts_out) counts_out[u] = nd;
+        if (LANE || lane == 0) sim_write_poisoned(expect_out, counts_out, std_err_out, exact_out, u, n_shots);
         return;
     }
     const double mu = dfe_mean(n, K, calibration, (int)sigma[k], touches + k * K, (obs_x[k] | obs_z[k]) & dfe_valid_mask(n),
                                class_error ? class_error + b * K : nullptr, flips ? flips + b * n : nullptr);
-    if (exact_out && (LANE || lane == 0)) exact_out[u] = coef * mu;
-    if (n_shots == 0) return;
-    double q = 0.5 * mu + 0.5;
-    q = fmin(fmax(q, 0.0), 1.0);
-    const unsigned long long t = (unsigned long long)(q * 0x1p32);
-    unsigned long long k_plus;
-    if (t >> 32) {
-        k_plus = n_shots;                                       // every word is below 2^32: no draws
-    } else if (t == 0) {
-        k_plus = 0;
-    } else {
-        const unsigned long long gid = (unsigned long long)(first_item + b);
-        const uint32_t k0 = (uint32_t)seed ^ (calibration ? DFE_KEY_CALIBRATION : DFE_KEY_SHOTS), k1 = (uint32_t)(seed >> 32);
-        if constexpr (LANE) {
-            k_plus = tomo_count((uint32_t)t, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)k, k0, k1, 0u, 1u, n_shots);
-        } else {
-            const uint32_t part = tomo_count((uint32_t)t, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)k, k0, k1, (uint32_t)lane,
-                                             64u, n_shots);
-            k_plus = (unsigned long long)wave_sum((double)part);    // integers below 2^32: the sum is exact
-        }
-    }
-    if (!LANE && lane != 0) return;
-    const unsigned long long k_minus = n_shots - k_plus;
-    if (expect_out) expect_out[u] = coef * ((double)((long long)k_plus - (long long)k_minus) / nd);
-    if (counts_out) counts_out[u] = nd;
-    if (std_err_out) std_err_out[u] = sqrt((double)(k_plus * k_minus) * 4.0 / nd) / nd;
+    sim_bernoulli_unit<LANE>(mu, coef, (unsigned long long)(first_item + b), (uint32_t)k,
+                             (uint32_t)seed ^ (calibration ? DFE_KEY_CALIBRATION : DFE_KEY_SHOTS), (uint32_t)(seed >> 32), lane,
+                             n_shots, u, expect_out, counts_out, std_err_out, exact_out);
 }
 
 // the calibration's standard errors -> variances, in place (what fbx_calibrate_expectations reads)
@@ -458,12 +429,11 @@ int fbx_dfe_simulate_dev(int n_qubits, int64_t m, int K, const int8_t* d_sigma, 
                                d_counts_out, d_std_err_out, d_exact_out));
     FBX_TRY(ensure_device());
     if (B == 0 || m == 0) return FBX_OK;
-    DevBuf scratch;                                  // the status when the caller does not want it (stream order protects it)
-    int32_t* status = d_status_out;
-    if (!status) { FBX_TRY(scratch.alloc(sizeof(int32_t) * (size_t)B)); status = scratch.as<int32_t>(); }
+    StatusBuf status;
+    FBX_TRY(status.take(d_status_out, B));
     return dfe_simulate_launch(n_qubits, m, K, d_sigma, d_touches, d_obs_x, d_obs_z, d_obs_sign, B, d_class_error, d_readout_flip,
-                               calibration, n_shots, seed, first_item, d_expect_out, d_counts_out, d_std_err_out, d_exact_out, status,
-                               true);
+                               calibration, n_shots, seed, first_item, d_expect_out, d_counts_out, d_std_err_out, d_exact_out,
+                               status.p, true);
 }
 
 // the settings and noise of a simulate call, uploaded
@@ -489,15 +459,11 @@ int fbx_dfe_simulate(int n_qubits, int64_t m, int K, const int8_t* sigma, const 
     FBX_TRY(ensure_device());
     if (B == 0 || m == 0) return FBX_OK;
     const size_t units = (size_t)B * (size_t)m;
-    HostIO io; DfeSimInputs in; double *de, *dc, *ds, *dx; int32_t* dst;
+    HostIO io; DfeSimInputs in; SimOut o;
     FBX_TRY(in.upload(io, n_qubits, m, K, sigma, touches, obs_x, obs_z, obs_sign, B, class_error, readout_flip));
-    FBX_TRY(io.out_opt(expect_out, units, &de));
-    FBX_TRY(io.out_opt(counts_out, units, &dc));
-    FBX_TRY(io.out_opt(std_err_out, units, &ds));
-    FBX_TRY(io.out_opt(exact_out, units, &dx));
-    FBX_TRY(io.out_opt(status_out, (size_t)B, &dst));
+    FBX_TRY(o.stage(io, (size_t)B, units, expect_out, counts_out, std_err_out, exact_out, status_out));
     FBX_TRY(fbx_dfe_simulate_dev(n_qubits, m, K, in.sigma, in.touches, in.obs_x, in.obs_z, in.obs_sign, B, in.class_error, in.flips,
-                                 calibration, n_shots, seed, first_item, de, dc, ds, dx, dst));
+                                 calibration, n_shots, seed, first_item, o.expect, o.counts, o.std_err, o.exact, o.status));
     return io.finish();
 }
 
@@ -521,11 +487,12 @@ int fbx_dfe_simulate_fidelity_dev(int n_qubits, int64_t m, int K, const int8_t* 
     FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const size_t units = (size_t)B * (size_t)m;
-    DevBuf work, scratch;                              // [B][m] doubles: e, se (and the calibration's e, se, the corrected e, se)
+    DevBuf work;                                       // [B][m] doubles: e, se (and the calibration's e, se, the corrected e, se)
     FBX_TRY(work.alloc(sizeof(double) * units * (calibrate ? 6 : 2)));
     double* e = work.as<double>(); double* se = e + units;
-    int32_t* status = d_status_out;
-    if (!status) { FBX_TRY(scratch.alloc(sizeof(int32_t) * (size_t)B)); status = scratch.as<int32_t>(); }
+    StatusBuf status_buf;
+    FBX_TRY(status_buf.take(d_status_out, B));
+    int32_t* status = status_buf.p;
     FBX_TRY(dfe_simulate_launch(n_qubits, m, K, d_sigma, d_touches, d_obs_x, d_obs_z, d_obs_sign, B, d_class_error, d_readout_flip, 0,
                                 n_shots, seed, first_item, e, nullptr, se, nullptr, status, true));
     if (calibrate) {

@@ -18,6 +18,8 @@
 //                      draws all its blocks; the lane form orders its units depth-major, so that the lanes of a wavefront
 //                      share a shot count when the schedule depends on the depth.  Both read the same stored probabilities and
 //                      count the same words: a value depends on (seed, item id, depth, basis, distribution, shots) only.
+//                      The walk, the thresholds and the histogram step are those of fbx_sim_shared.hpp; without records the
+//                      kernel keeps its own compare (`tlo <= w` alone, the dead thresholds' counts zeroed after the walk).
 // The cost is the Philox blocks: n_shots / 4 blocks of about a hundred integer instructions per unit against a few dozen
 // fused multiply-adds per depth for the distributions.
 #include "fbx_sim_shared.hpp"      // rpe_moment, shared with fbx_rpe.hip: the moments of both come from one formula
@@ -312,21 +314,14 @@ rpes_shots_kernel(long long B, int K, int n, int xy, int zq, RpeSimSchedule sche
 #pragma unroll
     for (int o = 0; o < M; ++o) { const double p = prob[unit * M + o]; run += p < 0.0 ? 0.0 : p; c[o] = run; }
     uint32_t tlo[M - 1], reach[M - 1];
-    bool live[M - 1];                                           // (a threshold of 2^32 is reached by no word)
-#pragma unroll
-    for (int o = 0; o < M - 1; ++o) {
-        const unsigned long long t = (unsigned long long)(c[o] / c[M - 1] * 0x1p32);
-        tlo[o] = (uint32_t)t; live[o] = (t >> 32) == 0; reach[o] = 0u;
-    }
+    bool live[M - 1];
+    sim_thresholds<M>(c, tlo, live, reach);
     const unsigned long long gid = (unsigned long long)(first_item + b);
     const uint32_t g0 = (uint32_t)gid, g1 = (uint32_t)(gid >> 32), g2 = (uint32_t)(2 * j + basis);
     const uint32_t k0 = (uint32_t)seed ^ RPES_KEY_TAG, k1 = (uint32_t)(seed >> 32);
-    const uint32_t full = N >> 2, tail = N & 3u;
-    auto count_word = [&](uint32_t w, uint32_t shot) {
+    sim_walk(g0, g1, g2, k0, k1, first, step, N, [&](uint32_t w, uint32_t shot) {
         if constexpr (REC) {
-            int o = 0;
-#pragma unroll
-            for (int i = 0; i < M - 1; ++i) { const int hit = live[i] && tlo[i] <= w; reach[i] += (uint32_t)hit; o += hit; }
+            const int o = sim_count_word<M>(w, tlo, live, reach);
             if (rec) {
                 const int s = PARTNER ? o >> 1 : o, t = o & 1;
                 for (int q = 0; q < n; ++q) rec[(long long)shot * n + q] = (uint8_t)(q == xy ? s : (PARTNER && q == zq) ? t : 0);
@@ -335,31 +330,13 @@ rpes_shots_kernel(long long B, int K, int n, int xy, int zq, RpeSimSchedule sche
 #pragma unroll
             for (int i = 0; i < M - 1; ++i) reach[i] += (uint32_t)(tlo[i] <= w);
         }
-    };
-    for (uint32_t blk = first; blk < full; blk += step) {
-        uint32_t x[4] = {g0, g1, g2, blk};
-        philox4x32_10(x, k0, k1);
-        count_word(x[0], 4 * blk); count_word(x[1], 4 * blk + 1); count_word(x[2], 4 * blk + 2); count_word(x[3], 4 * blk + 3);
-    }
-    if (tail && full % step == first) {                         // the last block of a shot count that is no multiple of 4
-        uint32_t x[4] = {g0, g1, g2, full};
-        philox4x32_10(x, k0, k1);
-        count_word(x[0], 4 * full);
-        if (tail > 1) count_word(x[1], 4 * full + 1);
-        if (tail > 2) count_word(x[2], 4 * full + 2);
-    }
+    });
     if constexpr (!REC) {
 #pragma unroll
         for (int i = 0; i < M - 1; ++i) reach[i] = live[i] ? reach[i] : 0u;
     }
     uint32_t hist[M];
-    uint32_t above = N;                                         // shots with outcome >= o
-#pragma unroll
-    for (int o = 0; o < M - 1; ++o) {
-        const uint32_t next = LANE ? reach[o] : (uint32_t)wave_sum((double)reach[o]);      // integers below 2^32: exact
-        hist[o] = above - next; above = next;
-    }
-    hist[M - 1] = above;
+    sim_histogram<M, LANE>(reach, N, hist);
     if (!writer) return;
     if (hist_out) {
 #pragma unroll
@@ -431,11 +408,12 @@ int fbx_rpe_simulate_dev(int n_qubits, int64_t B, int K, const double* d_gate_pt
     const int64_t per_block = lane ? RPES_THREADS : RPES_WAVES, blocks = (units + per_block - 1) / per_block;
     FBX_REQUIRE(dist_blocks < ((int64_t)1 << 31) && blocks < ((int64_t)1 << 31),
                 "fbx_rpe_simulate: B * K is beyond one launch; cut the batch with first_item");
-    DevBuf scratch_prob, scratch_status;             // what the caller does not want (stream order protects them)
+    DevBuf scratch_prob;                             // the distributions when the caller does not want them (stream order protects them)
     double* prob = d_prob_out;
-    int32_t* status = d_status_out;
     if (!prob) { FBX_TRY(scratch_prob.alloc(sizeof(double) * (size_t)units * M)); prob = scratch_prob.as<double>(); }
-    if (!status) { FBX_TRY(scratch_status.alloc(sizeof(int32_t) * (size_t)B)); status = scratch_status.as<int32_t>(); }
+    StatusBuf status_buf;
+    FBX_TRY(status_buf.take(d_status_out, B));
+    int32_t* status = status_buf.p;
     RpeSimIn in{};
     in.B = B; in.K = K; in.n = n_qubits; in.per_item = basis_per_item ? 1 : 0;
     in.xy = xy_qubit; in.zq = z_qubit;

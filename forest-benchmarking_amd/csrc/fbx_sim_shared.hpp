@@ -1,11 +1,42 @@
-// fbx_sim_shared.hpp -- device code that two translation units evaluate and whose results the tests pin bit for bit: the shot
-// counting of the simulated experiments (fbx_tomo_sim.hip, fbx_dfe.hip), the exact mean of a tomography setting (fbx_tomo_sim.hip,
-// fbx_tomo_sim_grouped.hip), the direct-fidelity formula (fbx_shots.hip, fbx_dfe.hip) and the moments of a robust-phase-estimation
-// record (fbx_rpe.hip, fbx_rpe_sim.hip).
+// fbx_sim_shared.hpp -- code that several translation units evaluate and whose results the tests pin bit for bit: the shot
+// counting of the simulated experiments (sim_*, tomo_count: fbx_tomo_sim.hip, fbx_tomo_sim_grouped.hip, fbx_tomo_sim_symm.hip,
+// fbx_dfe.hip, fbx_rpe_sim.hip) with the host checks and staging their entry points share, the exact mean of a tomography
+// setting (fbx_tomo_sim.hip, fbx_tomo_sim_grouped.hip), the direct-fidelity formula (fbx_shots.hip, fbx_dfe.hip) and the
+// moments of a robust-phase-estimation record (fbx_rpe.hip, fbx_rpe_sim.hip).
+//
+// Three compare loops stay where they are, different on purpose: tomog_sim_kernel<NQ> tests `thi == 0 && tlo <= w` on
+// wave-uniform operands (fbx_tomo_sim_grouped.hip); the lane forms test `live && tlo <= w` (sim_count_word below); and
+// rpes_shots_kernel without records tests `tlo <= w` alone and zeroes the dead thresholds' counts afterwards (fbx_rpe_sim.hip).
 #pragma once
 #include "fbx_common.hpp"
 
 namespace fbx {
+
+inline int tomo_truth_len(const DesignDev& d) { return d.kind == FBX_KIND_PROCESS ? d.D * d.D : 2 * d.D; }
+
+// the batch arguments of the tomography simulators; per_unit: n_shots is the total of a unit (fbx_tomo_sim_symm.hip's wording)
+inline int sim_check_batch(const char* who, int64_t B, int64_t n_shots, int64_t first_item, bool per_unit = false) {
+    const std::string w(who);
+    FBX_REQUIRE(B >= 0 && n_shots >= 0 && first_item >= 0,
+                w + (per_unit ? ": need B >= 0, shots >= 0 and first_item >= 0" : ": need B >= 0, n_shots >= 0 and first_item >= 0"));
+    FBX_REQUIRE(n_shots < ((int64_t)1 << 32), w + (per_unit ? ": the shots of a unit must be below 2^32" : ": n_shots must be below 2^32"));
+    FBX_REQUIRE(B <= INT64_MAX / 65536 / 4096, w + ": B * m overflows");
+    return FBX_OK;
+}
+
+// the outputs every simulator has, reserved through `io`: four of [units] doubles and the status [B]; NULL stays NULL
+struct SimOut {
+    double *expect, *counts, *std_err, *exact;
+    int32_t* status;
+    int stage(HostIO& io, size_t B, size_t units, double* h_expect, double* h_counts, double* h_std_err, double* h_exact,
+              int32_t* h_status) {
+        FBX_TRY(io.out_opt(h_expect, units, &expect));
+        FBX_TRY(io.out_opt(h_counts, units, &counts));
+        FBX_TRY(io.out_opt(h_std_err, units, &std_err));
+        FBX_TRY(io.out_opt(h_exact, units, &exact));
+        return io.out_opt(h_status, B, &status);
+    }
+};
 
 // status[b] = 1 when item b has a non-finite truth entry or a flip probability outside [0, 1] (NaN included), else 0: one launch
 // on the calling thread's stream (fbx_tomo_sim.hip); d_flips may be NULL
@@ -17,23 +48,129 @@ int tomo_poison_launch(int64_t B, int truth_len, int flip_len, const double* d_t
 
 #if defined(__HIPCC__)
 
-// How many of the Philox blocks first, first + step, ... of the setting (g, k) hold words below t (< 2^32); the last block of a
-// shot count that is no multiple of 4 counts its first n_shots & 3 words only.
-__device__ __forceinline__ uint32_t tomo_count(uint32_t t, uint32_t g0, uint32_t g1, uint32_t k, uint32_t k0, uint32_t k1,
-                                               uint32_t first, uint32_t step, uint32_t n_shots) {
+// The shots of one unit: f(word, shot) for the words of the Philox blocks first, first + step, ... of counter {g0, g1, g2, j}
+// under the key (k0, k1), four shots a block.  The last block of a shot count that is no multiple of 4 gives its first
+// n_shots & 3 words only and belongs to the walker with full % step == first.  (first, step) = (0, 1): one lane draws every
+// shot; (lane, 64): a wavefront shares them.  Every simulator draws through this loop but toms_kernel (fbx_tomo_sim_symm.hip,
+// which flattens (pattern, block) pairs over the lanes) and tomog_sim_lane_kernel (fbx_tomo_sim_grouped.hip: the same loop
+// spelled out, because it measured 0.9 % slower through here).
+template <class F>
+__device__ __forceinline__ void sim_walk(uint32_t g0, uint32_t g1, uint32_t g2, uint32_t k0, uint32_t k1, uint32_t first,
+                                         uint32_t step, uint32_t n_shots, F&& f) {
     const uint32_t full = n_shots >> 2, tail = n_shots & 3u;
-    uint32_t cnt = 0;
     for (uint32_t j = first; j < full; j += step) {
-        uint32_t c[4] = {g0, g1, k, j};
+        uint32_t c[4] = {g0, g1, g2, j};
         philox4x32_10(c, k0, k1);
-        cnt += (uint32_t)(c[0] < t) + (uint32_t)(c[1] < t) + (uint32_t)(c[2] < t) + (uint32_t)(c[3] < t);
+        f(c[0], 4 * j); f(c[1], 4 * j + 1); f(c[2], 4 * j + 2); f(c[3], 4 * j + 3);
     }
     if (tail && full % step == first) {
-        uint32_t c[4] = {g0, g1, k, full};
+        uint32_t c[4] = {g0, g1, g2, full};
         philox4x32_10(c, k0, k1);
-        cnt += (uint32_t)(c[0] < t) + (uint32_t)(tail > 1 && c[1] < t) + (uint32_t)(tail > 2 && c[2] < t);
+        f(c[0], 4 * full);
+        if (tail > 1) f(c[1], 4 * full + 1);
+        if (tail > 2) f(c[2], 4 * full + 2);
     }
+}
+
+// How many of those words of the setting (g, k) are below t (< 2^32)
+__device__ __forceinline__ uint32_t tomo_count(uint32_t t, uint32_t g0, uint32_t g1, uint32_t k, uint32_t k0, uint32_t k1,
+                                               uint32_t first, uint32_t step, uint32_t n_shots) {
+    uint32_t cnt = 0;
+    sim_walk(g0, g1, k, k0, k1, first, step, n_shots, [&](uint32_t w, uint32_t) { cnt += (uint32_t)(w < t); });
     return cnt;
+}
+
+// k_plus of N shots gave +1 -> the mean of the +-1 values times coef, N, and the standard error of that mean
+// (fbx_dfe.hip calls it with coef = +-1: the product with |coef| is exact)
+__device__ __forceinline__ void sim_write_pm1(double* __restrict__ expect, double* __restrict__ counts, double* __restrict__ std_err,
+                                              long long out, double coef, unsigned long long k_plus, unsigned long long N) {
+    const unsigned long long k_minus = N - k_plus;
+    const double nd = (double)N;
+    if (expect) expect[out] = coef * ((double)((long long)k_plus - (long long)k_minus) / nd);
+    if (counts) counts[out] = nd;
+    if (std_err) std_err[out] = fabs(coef) * sqrt((double)(k_plus * k_minus) * 4.0 / nd) / nd;
+}
+
+// ... and the same cells of a poisoned item: NaN, NaN, NaN and N
+__device__ __forceinline__ void sim_write_poisoned(double* __restrict__ expect, double* __restrict__ counts, double* __restrict__ std_err,
+                                                   double* __restrict__ exact, long long out, unsigned long long N) {
+    const double nan = __builtin_nan("");
+    if (expect) expect[out] = nan;
+    if (std_err) std_err[out] = nan;
+    if (exact) exact[out] = nan;
+    if (counts) counts[out] = (double)N;
+}
+
+// One +-1 observable of mean mu (item gid, setting k, cell `out`), everything below the mean of tomo_sim_kernel and
+// dfe_sim_kernel: the exact value, the threshold floor(q 2^32) of q = (1 + mu) / 2 clamped to [0, 1], the count of the words
+// below it and the outputs.  LANE: the calling lane has the unit to itself; else its wavefront shares the shots and lane 0 writes.
+template <bool LANE>
+__device__ __forceinline__ void sim_bernoulli_unit(double mu, double coef, unsigned long long gid, uint32_t k, uint32_t k0, uint32_t k1,
+                                                   int lane, unsigned n_shots, long long out, double* __restrict__ expect_out,
+                                                   double* __restrict__ counts_out, double* __restrict__ std_err_out,
+                                                   double* __restrict__ exact_out) {
+    if (exact_out && (LANE || lane == 0)) exact_out[out] = coef * mu;
+    if (n_shots == 0) return;
+    double q = 0.5 * mu + 0.5;
+    q = fmin(fmax(q, 0.0), 1.0);
+    const unsigned long long t = (unsigned long long)(q * 0x1p32);
+    unsigned long long k_plus;
+    if (t >> 32) {
+        k_plus = n_shots;                                       // every word is below 2^32: no draws
+    } else if (t == 0) {
+        k_plus = 0;
+    } else if constexpr (LANE) {
+        k_plus = tomo_count((uint32_t)t, (uint32_t)gid, (uint32_t)(gid >> 32), k, k0, k1, 0u, 1u, n_shots);
+    } else {
+        const uint32_t part = tomo_count((uint32_t)t, (uint32_t)gid, (uint32_t)(gid >> 32), k, k0, k1, (uint32_t)lane, 64u, n_shots);
+        k_plus = (unsigned long long)wave_sum((double)part);    // integers below 2^32: the sum is exact
+    }
+    if (!LANE && lane != 0) return;
+    sim_write_pm1(expect_out, counts_out, std_err_out, out, coef, k_plus, n_shots);
+}
+
+// Outcome o of M has the words in [thr[o - 1], thr[o]), thr[o] = floor(c[o] / c[M - 1] 2^32) from the running sums c of the
+// clamped probabilities.  A counter holds tlo = the low word of each threshold, live = "it is below 2^32" (one of 2^32 is
+// reached by no word) and reach[o] = the words seen with thr[o] <= word, i.e. with an outcome above o.
+template <int M>
+__device__ __forceinline__ void sim_thresholds(const double (&c)[M], uint32_t (&tlo)[M - 1], bool (&live)[M - 1], uint32_t (&reach)[M - 1]) {
+#pragma unroll
+    for (int o = 0; o < M - 1; ++o) {
+        const unsigned long long t = (unsigned long long)(c[o] / c[M - 1] * 0x1p32);
+        tlo[o] = (uint32_t)t; live[o] = (t >> 32) == 0; reach[o] = 0u;
+    }
+}
+
+// one word into reach[]; returns its outcome
+template <int M>
+__device__ __forceinline__ int sim_count_word(uint32_t w, const uint32_t (&tlo)[M - 1], const bool (&live)[M - 1], uint32_t (&reach)[M - 1]) {
+    int o = 0;
+#pragma unroll
+    for (int i = 0; i < M - 1; ++i) { const int hit = live[i] && tlo[i] <= w; reach[i] += (uint32_t)hit; o += hit; }
+    return o;
+}
+
+// reach[] -> the histogram of n_shots shots.  LANE: reach is the calling lane's own; else the wavefront's lanes hold partial
+// counts, which are summed (integers below 2^32: exactly, in double) and every lane gets the histogram.
+template <int M, bool LANE>
+__device__ __forceinline__ void sim_histogram(const uint32_t (&reach)[M - 1], uint32_t n_shots, uint32_t (&hist)[M]) {
+    uint32_t above = n_shots;                                   // shots with outcome >= o
+#pragma unroll
+    for (int o = 0; o < M - 1; ++o) {
+        const uint32_t next = LANE ? reach[o] : (uint32_t)wave_sum((double)reach[o]);
+        hist[o] = above - next; above = next;
+    }
+    hist[M - 1] = above;
+}
+
+// The other way to a histogram, for many outcomes: every lane increments PRIVATE counters cnt[o * 64 + lane] in LDS (the lane
+// is the bank) and lane o < d sums row o here, starting at its own column so that the lanes read different banks.
+__device__ __forceinline__ void sim_column_sum(const uint32_t* cnt, int d, int lane, uint32_t* hist) {
+    if (lane < d) {
+        uint32_t h = 0;
+        for (int l = 0; l < 64; ++l) h += cnt[lane * 64 + ((l + lane) & 63)];
+        hist[lane] = h;
+    }
 }
 
 __device__ __forceinline__ bool tomo_bad_probability(double v) { return !(v >= 0.0 && v <= 1.0); }      // NaN included

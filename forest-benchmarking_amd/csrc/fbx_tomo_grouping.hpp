@@ -86,6 +86,4 @@ inline int check_grouping(const fbx_grouping* grp, const fbx_design* design, con
     return FBX_OK;
 }
 
-inline int tomog_truth_len(const DesignDev& d) { return d.kind == FBX_KIND_PROCESS ? d.D * d.D : 2 * d.D; }
-
 }  // namespace fbx

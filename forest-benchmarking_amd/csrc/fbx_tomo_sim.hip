@@ -13,7 +13,7 @@
 // shots (the chip is full without cutting a setting); below, a WAVEFRONT takes a unit, lane l counts the Philox blocks l, l + 64,
 // ... and the 64 partial counts are summed (integers, exactly, in double).  A value depends on (seed, item id, setting, mean, shots)
 // only: both splits evaluate the mean with the same code in the same order and count the same words.
-#include "fbx_sim_shared.hpp"      // tomo_count and the unit threshold, shared with fbx_dfe.hip; tomo_mean, with fbx_tomo_sim_grouped.hip
+#include "fbx_sim_shared.hpp"      // sim_bernoulli_unit and the unit threshold, shared with fbx_dfe.hip; tomo_mean, with fbx_tomo_sim_grouped.hip
 
 namespace fbx {
 
@@ -62,59 +62,24 @@ tomo_sim_kernel(DesignDev des, long long B, const double* __restrict__ truth, in
     const int g = (int)(u - b * des.m), k = des.order[g];
     const double coef = des.coef[g];
     const long long out = b * des.m + k;
-    const double nd = (double)n_shots;
     if (status[b]) {
-        if (!LANE && lane != 0) return;
-        const double nan = __builtin_nan("");
-        if (expect_out) expect_out[out] = nan;
-        if (std_err_out) std_err_out[out] = nan;
-        if (exact_out) exact_out[out] = nan;
-        if (counts_out) counts_out[out] = nd;
+        if (LANE || lane == 0) sim_write_poisoned(expect_out, counts_out, std_err_out, exact_out, out, n_shots);
         return;
     }
     const double mu = tomo_mean(des, truth + b * truth_len, flips ? flips + b * 2 * des.n : nullptr, des.sp[g]);
-    if (exact_out && (LANE || lane == 0)) exact_out[out] = coef * mu;
-    if (n_shots == 0) return;
-    double q = 0.5 * mu + 0.5;
-    q = fmin(fmax(q, 0.0), 1.0);
-    const unsigned long long t = (unsigned long long)(q * 0x1p32);
-    unsigned long long k_plus;
-    if (t >> 32) {
-        k_plus = n_shots;                                       // every word is below 2^32: no draws
-    } else if (t == 0) {
-        k_plus = 0;
-    } else {
-        const unsigned long long gid = (unsigned long long)(first_item + b);
-        const uint32_t k0 = (uint32_t)seed ^ TOMO_KEY_TAG, k1 = (uint32_t)(seed >> 32);
-        if constexpr (LANE) {
-            k_plus = tomo_count((uint32_t)t, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)k, k0, k1, 0u, 1u, n_shots);
-        } else {
-            const uint32_t part = tomo_count((uint32_t)t, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)k, k0, k1, (uint32_t)lane,
-                                             64u, n_shots);
-            k_plus = (unsigned long long)wave_sum((double)part);    // integers below 2^32: the sum is exact
-        }
-    }
-    if (!LANE && lane != 0) return;
-    const unsigned long long k_minus = n_shots - k_plus;
-    if (expect_out) expect_out[out] = coef * ((double)((long long)k_plus - (long long)k_minus) / nd);
-    if (counts_out) counts_out[out] = nd;
-    if (std_err_out) std_err_out[out] = fabs(coef) * sqrt((double)(k_plus * k_minus) * 4.0 / nd) / nd;
+    sim_bernoulli_unit<LANE>(mu, coef, (unsigned long long)(first_item + b), (uint32_t)k, (uint32_t)seed ^ TOMO_KEY_TAG,
+                             (uint32_t)(seed >> 32), lane, n_shots, out, expect_out, counts_out, std_err_out, exact_out);
 }
 
 static int tomo_check(const fbx_design* design, int64_t B, const void* truth, int64_t n_shots, int64_t first_item,
                       const void* expect, const void* counts, const void* std_err, const void* exact) {
-    FBX_REQUIRE(B >= 0 && n_shots >= 0 && first_item >= 0, "fbx_tomo_simulate: need B >= 0, n_shots >= 0 and first_item >= 0");
-    FBX_REQUIRE(n_shots < ((int64_t)1 << 32), "fbx_tomo_simulate: n_shots must be below 2^32");
+    FBX_TRY(sim_check_batch("fbx_tomo_simulate", B, n_shots, first_item));
     FBX_REQUIRE(truth != nullptr, "fbx_tomo_simulate: NULL truth");
     FBX_REQUIRE(expect || counts || std_err || exact, "fbx_tomo_simulate: every output is NULL");
     FBX_REQUIRE(n_shots > 0 || !(expect || counts || std_err),
                 "fbx_tomo_simulate: n_shots == 0 gives exact_out only (expect_out, counts_out and std_err_out must be NULL)");
-    FBX_TRY(check_design(design, "fbx_tomo_simulate"));
-    FBX_REQUIRE(B <= INT64_MAX / 65536 / 4096, "fbx_tomo_simulate: B * m overflows");
-    return FBX_OK;
+    return check_design(design, "fbx_tomo_simulate");
 }
-
-static int tomo_truth_len(const DesignDev& d) { return d.kind == FBX_KIND_PROCESS ? d.D * d.D : 2 * d.D; }
 
 }  // namespace fbx
 
@@ -130,22 +95,21 @@ int fbx_tomo_simulate_dev(const fbx_design* design, int64_t B, const double* d_t
     if (B == 0) return FBX_OK;
     const DesignDev& des = design->dev;
     const int truth_len = tomo_truth_len(des);
-    DevBuf scratch;                                  // the status when the caller does not want it (stream order protects it)
-    int32_t* status = d_status_out;
-    if (!status) { FBX_TRY(scratch.alloc(sizeof(int32_t) * (size_t)B)); status = scratch.as<int32_t>(); }
+    StatusBuf status;
+    FBX_TRY(status.take(d_status_out, B));
     constexpr int WAVES = TOMO_THREADS / 64;
-    FBX_TRY(tomo_poison_launch(B, truth_len, 2 * des.n, d_truth, d_readout_flip, status));
+    FBX_TRY(tomo_poison_launch(B, truth_len, 2 * des.n, d_truth, d_readout_flip, status.p));
     const int64_t units = B * des.m;
     if (units >= FBX_TOMO_LANE_MIN_UNITS) {
         const int64_t blocks = (units + TOMO_THREADS - 1) / TOMO_THREADS;
         FBX_REQUIRE(blocks < ((int64_t)1 << 31), "fbx_tomo_simulate: B * m is beyond one launch; cut the batch with first_item");
         hipLaunchKernelGGL(tomo_sim_kernel<true>, dim3((unsigned)blocks), dim3(TOMO_THREADS), 0, stream(), des, (long long)B, d_truth,
                            truth_len, d_readout_flip, (unsigned)n_shots, (unsigned long long)seed, (long long)first_item,
-                           (const int*)status, d_expect_out, d_counts_out, d_std_err_out, d_exact_out);
+                           (const int*)status.p, d_expect_out, d_counts_out, d_std_err_out, d_exact_out);
     } else {
         hipLaunchKernelGGL(tomo_sim_kernel<false>, dim3((unsigned)((units + WAVES - 1) / WAVES)), dim3(TOMO_THREADS), 0, stream(), des,
                            (long long)B, d_truth, truth_len, d_readout_flip, (unsigned)n_shots, (unsigned long long)seed,
-                           (long long)first_item, (const int*)status, d_expect_out, d_counts_out, d_std_err_out, d_exact_out);
+                           (long long)first_item, (const int*)status.p, d_expect_out, d_counts_out, d_std_err_out, d_exact_out);
     }
     FBX_HIP(hipGetLastError());
     return FBX_OK;
@@ -158,15 +122,11 @@ int fbx_tomo_simulate(const fbx_design* design, int64_t B, const double* truth, 
     FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const size_t n = (size_t)B, m = (size_t)design->dev.m;
-    HostIO io; double *dt, *df = nullptr, *de, *dc, *ds, *dx; int32_t* dst;
+    HostIO io; SimOut o; double *dt, *df = nullptr;
     FBX_TRY(io.in(truth, n * (size_t)tomo_truth_len(design->dev), &dt));
     if (readout_flip) FBX_TRY(io.in(readout_flip, n * 2 * (size_t)design->dev.n, &df));
-    FBX_TRY(io.out_opt(expect_out, n * m, &de));
-    FBX_TRY(io.out_opt(counts_out, n * m, &dc));
-    FBX_TRY(io.out_opt(std_err_out, n * m, &ds));
-    FBX_TRY(io.out_opt(exact_out, n * m, &dx));
-    FBX_TRY(io.out_opt(status_out, n, &dst));
-    FBX_TRY(fbx_tomo_simulate_dev(design, B, dt, n_shots, df, seed, first_item, de, dc, ds, dx, dst));
+    FBX_TRY(o.stage(io, n, n * m, expect_out, counts_out, std_err_out, exact_out, status_out));
+    FBX_TRY(fbx_tomo_simulate_dev(design, B, dt, n_shots, df, seed, first_item, o.expect, o.counts, o.std_err, o.exact, o.status));
     return io.finish();
 }
 

@@ -20,7 +20,9 @@
 // wavefront form counts in registers instead of LDS (per threshold, the words that reach it), and there is a second work split,
 // chosen by the number of units alone: from FBX_TOMOG_LANE_MIN_UNITS units on a LANE takes a unit -- the same sums in the same
 // order for the distribution, all the unit's Philox blocks, registers only.  A value depends on (seed, item id, group,
-// distribution, shots) only, whichever form ran.
+// distribution, shots) only, whichever form ran.  The walk over the Philox blocks, the step from the counts to the histogram
+// and the members' formulas are those of fbx_sim_shared.hpp; the wavefront form keeps its own compare (`thi == 0 && tlo <= w` on
+// wave-uniform operands), the lane form uses sim_count_word (`live && tlo <= w`) and keeps its own copy of the walk (measured).
 #include "fbx_tomo_grouping.hpp"
 
 #ifndef FBX_TOMOG_LANE_MIN_UNITS
@@ -91,6 +93,27 @@ tomog_status_kernel(DesignDev des, GroupingDev grp, long long B, const double* _
     if (lane == 0 && tomog_bad_total(c_last)) status[b] = 1;   // (several wavefronts may store the same 1)
 }
 
+// The members first, first + step, ... of group [m0, m1) of a poisoned item, `base` = b * m: (lane, 64) for a wavefront, (0, 1) for a lane
+__device__ __forceinline__ void tomog_members_poisoned(const GroupingDev& grp, int m0, int m1, int first, int step, long long base,
+                                                       unsigned n_shots, double* __restrict__ expect_out, double* __restrict__ counts_out,
+                                                       double* __restrict__ std_err_out, double* __restrict__ exact_out) {
+    for (int j = m0 + first; j < m1; j += step) sim_write_poisoned(expect_out, counts_out, std_err_out, exact_out, base + grp.mk[j], n_shots);
+}
+
+// ... and of a sampled one: the parity sum over the histogram of the group's d outcomes (LDS words or a lane's registers)
+template <class Hist>
+__device__ __forceinline__ void tomog_members_sampled(const GroupingDev& grp, int m0, int m1, int first, int step, long long base,
+                                                      const Hist& hist, int d, unsigned n_shots, double* __restrict__ expect_out,
+                                                      double* __restrict__ counts_out, double* __restrict__ std_err_out) {
+    for (int j = m0 + first; j < m1; j += step) {
+        const int z = grp.mmask[j];
+        unsigned long long k_plus = 0;
+#pragma unroll
+        for (int o = 0; o < d; ++o) if (!(__popc(o & z) & 1)) k_plus += hist[o];
+        sim_write_pm1(expect_out, counts_out, std_err_out, base + grp.mk[j], grp.mcoef[j], k_plus, n_shots);
+    }
+}
+
 // unit u = (item u / G, group u % G), a wavefront each.  NQ = the number of qubits when it is 1..3: the lanes count in registers,
 // per threshold, the words that reach it (2^n - 1 compares against wave-uniform operands and as many adds per word, no LDS);
 // NQ = 0: any n, the search and the private LDS counters.  The histogram is the same integers either way.
@@ -110,19 +133,11 @@ tomog_sim_kernel(DesignDev des, GroupingDev grp, long long B, const double* __re
     const long long b = u / grp.G;
     const int g = (int)(u - b * grp.G);
     const int n = NQ ? NQ : des.n, d = 1 << n, m0 = grp.mptr[g], m1 = grp.mptr[g + 1];
-    const double nd = (double)n_shots;
     const long long cell = (b * grp.G + g) * d + lane;         // of prob_out / hist_out, lanes < d
     if (status[b]) {
-        const double nan = __builtin_nan("");
-        for (int j = m0 + lane; j < m1; j += 64) {
-            const long long out = b * des.m + grp.mk[j];
-            if (expect_out) expect_out[out] = nan;
-            if (std_err_out) std_err_out[out] = nan;
-            if (exact_out) exact_out[out] = nan;
-            if (counts_out) counts_out[out] = nd;
-        }
+        tomog_members_poisoned(grp, m0, m1, lane, 64, b * des.m, n_shots, expect_out, counts_out, std_err_out, exact_out);
         if (lane < d) {
-            if (prob_out) prob_out[cell] = nan;
+            if (prob_out) prob_out[cell] = __builtin_nan("");
             if (hist_out) hist_out[cell] = 0u;
         }
         return;
@@ -146,8 +161,6 @@ tomog_sim_kernel(DesignDev des, GroupingDev grp, long long B, const double* __re
     const unsigned long long gid = (unsigned long long)(first_item + b);
     const uint32_t g0 = (uint32_t)gid, g1 = (uint32_t)(gid >> 32);
     const uint32_t k0 = (uint32_t)seed ^ TOMOG_KEY_TAG, k1 = (uint32_t)(seed >> 32);
-    const uint32_t full = n_shots >> 2, tail = n_shots & 3u;
-    const bool has_tail = tail && (full & 63u) == (uint32_t)lane;      // the last block of a shot count that is no multiple of 4
     if constexpr (NQ > 0) {
         constexpr int DD = 1 << NQ;
         uint32_t tlo[DD - 1], thi[DD - 1], reach[DD - 1];              // reach[o]: words with thr[o] <= word, i.e. outcome > o
@@ -156,76 +169,34 @@ tomog_sim_kernel(DesignDev des, GroupingDev grp, long long B, const double* __re
             const unsigned long long t = thr[o];
             tlo[o] = (uint32_t)uniform((int)(uint32_t)t); thi[o] = (uint32_t)uniform((int)(uint32_t)(t >> 32)); reach[o] = 0u;
         }
-        auto count_word = [&](uint32_t w) {
+        sim_walk(g0, g1, (uint32_t)g, k0, k1, (uint32_t)lane, 64u, n_shots, [&](uint32_t w, uint32_t) {
 #pragma unroll
             for (int o = 0; o < DD - 1; ++o) reach[o] += (uint32_t)(thi[o] == 0u && tlo[o] <= w);      // (thi = 1: the threshold is 2^32)
-        };
-        for (uint32_t j = (uint32_t)lane; j < full; j += 64u) {
-            uint32_t c[4] = {g0, g1, (uint32_t)g, j};
-            philox4x32_10(c, k0, k1);
-            count_word(c[0]); count_word(c[1]); count_word(c[2]); count_word(c[3]);
-        }
-        if (has_tail) {
-            uint32_t c[4] = {g0, g1, (uint32_t)g, full};
-            philox4x32_10(c, k0, k1);
-            count_word(c[0]);
-            if (tail > 1) count_word(c[1]);
-            if (tail > 2) count_word(c[2]);
-        }
-        uint32_t above = n_shots;                                       // shots with outcome >= o
+        });
+        uint32_t h[DD];
+        sim_histogram<DD, false>(reach, n_shots, h);
 #pragma unroll
-        for (int o = 0; o < DD - 1; ++o) {
-            const uint32_t next = (uint32_t)wave_sum((double)reach[o]);  // integers below 2^32: exact
-            if (lane == o) hist[o] = above - next;
-            above = next;
-        }
-        if (lane == DD - 1) hist[DD - 1] = above;
+        for (int o = 0; o < DD; ++o) if (lane == o) hist[o] = h[o];
     } else {
         __shared__ uint32_t cnt_all[TOMOG_WAVES][TOMOG_MAX_OUTCOMES * 64];
         uint32_t* cnt = cnt_all[wave];
         for (int o = 0; o < d; ++o) cnt[o * 64 + lane] = 0u;
         FBX_WAVE_SYNC();
         // the outcome of a word = the number of thresholds <= the word: n steps of a search (thr is non-decreasing)
-        auto count_word = [&](uint32_t w) {
+        sim_walk(g0, g1, (uint32_t)g, k0, k1, (uint32_t)lane, 64u, n_shots, [&](uint32_t w, uint32_t) {
             int lo = 0;
             for (int step = d >> 1; step; step >>= 1)
                 if (thr[lo + step - 1] <= (unsigned long long)w) lo += step;
             cnt[lo * 64 + lane] += 1u;
-        };
-        for (uint32_t j = (uint32_t)lane; j < full; j += 64u) {
-            uint32_t c[4] = {g0, g1, (uint32_t)g, j};
-            philox4x32_10(c, k0, k1);
-            count_word(c[0]); count_word(c[1]); count_word(c[2]); count_word(c[3]);
-        }
-        if (has_tail) {
-            uint32_t c[4] = {g0, g1, (uint32_t)g, full};
-            philox4x32_10(c, k0, k1);
-            count_word(c[0]);
-            if (tail > 1) count_word(c[1]);
-            if (tail > 2) count_word(c[2]);
-        }
+        });
         FBX_WAVE_SYNC();
-        if (lane < d) {
-            uint32_t h = 0;
-            for (int l = 0; l < 64; ++l) h += cnt[lane * 64 + ((l + lane) & 63)];     // (rotated: the lanes read different banks)
-            hist[lane] = h;
-        }
+        sim_column_sum(cnt, d, lane, hist);
     }
     FBX_WAVE_SYNC();
     if (hist_out && lane < d) hist_out[cell] = hist[lane];
     FBX_WAVE_SYNC();
     if (!(expect_out || counts_out || std_err_out)) return;
-    for (int j = m0 + lane; j < m1; j += 64) {
-        const int z = grp.mmask[j];
-        const double coef = grp.mcoef[j];
-        unsigned long long k_plus = 0;
-        for (int o = 0; o < d; ++o) if (!(__popc(o & z) & 1)) k_plus += hist[o];
-        const unsigned long long k_minus = n_shots - k_plus;
-        const long long out = b * des.m + grp.mk[j];
-        if (expect_out) expect_out[out] = coef * ((double)((long long)k_plus - (long long)k_minus) / nd);
-        if (counts_out) counts_out[out] = nd;
-        if (std_err_out) std_err_out[out] = fabs(coef) * sqrt((double)(k_plus * k_minus) * 4.0 / nd) / nd;
-    }
+    tomog_members_sampled(grp, m0, m1, lane, 64, b * des.m, hist, d, n_shots, expect_out, counts_out, std_err_out);
 }
 
 // the lane-per-unit split (1..3 qubits, from FBX_TOMOG_LANE_MIN_UNITS units on): the status pass ...
@@ -257,20 +228,12 @@ tomog_sim_lane_kernel(DesignDev des, GroupingDev grp, long long B, const double*
     const long long b = u / grp.G;
     const int g = (int)(u - b * grp.G);
     const int m0 = grp.mptr[g], m1 = grp.mptr[g + 1];
-    const double nd = (double)n_shots;
     const long long cell = (b * grp.G + g) * DD;
     if (status[b]) {
-        const double nan = __builtin_nan("");
-        for (int j = m0; j < m1; ++j) {
-            const long long out = b * des.m + grp.mk[j];
-            if (expect_out) expect_out[out] = nan;
-            if (std_err_out) std_err_out[out] = nan;
-            if (exact_out) exact_out[out] = nan;
-            if (counts_out) counts_out[out] = nd;
-        }
+        tomog_members_poisoned(grp, m0, m1, 0, 1, b * des.m, n_shots, expect_out, counts_out, std_err_out, exact_out);
 #pragma unroll
         for (int o = 0; o < DD; ++o) {
-            if (prob_out) prob_out[cell + o] = nan;
+            if (prob_out) prob_out[cell + o] = __builtin_nan("");
             if (hist_out) hist_out[cell + o] = 0u;
         }
         return;
@@ -289,20 +252,15 @@ tomog_sim_lane_kernel(DesignDev des, GroupingDev grp, long long B, const double*
     }
     if (!sampled) return;
     uint32_t tlo[DD - 1], reach[DD - 1];
-    bool live[DD - 1];                                                   // (a threshold of 2^32 is reached by no word)
-#pragma unroll
-    for (int o = 0; o < DD - 1; ++o) {
-        const unsigned long long t = (unsigned long long)(c[o] / c[DD - 1] * 0x1p32);
-        tlo[o] = (uint32_t)t; live[o] = (t >> 32) == 0; reach[o] = 0u;
-    }
+    bool live[DD - 1];
+    sim_thresholds<DD>(c, tlo, live, reach);
     const unsigned long long gid = (unsigned long long)(first_item + b);
     const uint32_t g0 = (uint32_t)gid, g1 = (uint32_t)(gid >> 32);
     const uint32_t k0 = (uint32_t)seed ^ TOMOG_KEY_TAG, k1 = (uint32_t)(seed >> 32);
+    // This kernel keeps the walk of sim_walk(.., 0, 1, ..) spelled out: through the helper the loop is the same instructions in
+    // other registers and 0.9 % slower at 65536 x 324 units.
     const uint32_t full = n_shots >> 2, tail = n_shots & 3u;
-    auto count_word = [&](uint32_t w) {
-#pragma unroll
-        for (int o = 0; o < DD - 1; ++o) reach[o] += (uint32_t)(live[o] && tlo[o] <= w);
-    };
+    auto count_word = [&](uint32_t w) { (void)sim_count_word<DD>(w, tlo, live, reach); };
     for (uint32_t j = 0; j < full; ++j) {
         uint32_t x[4] = {g0, g1, (uint32_t)g, j};
         philox4x32_10(x, k0, k1);
@@ -316,43 +274,26 @@ tomog_sim_lane_kernel(DesignDev des, GroupingDev grp, long long B, const double*
         if (tail > 2) count_word(x[2]);
     }
     uint32_t hist[DD];
-    uint32_t above = n_shots;                                            // shots with outcome >= o
-#pragma unroll
-    for (int o = 0; o < DD - 1; ++o) { hist[o] = above - reach[o]; above = reach[o]; }
-    hist[DD - 1] = above;
+    sim_histogram<DD, true>(reach, n_shots, hist);
     if (hist_out) {
 #pragma unroll
         for (int o = 0; o < DD; ++o) hist_out[cell + o] = hist[o];
     }
     if (!(expect_out || counts_out || std_err_out)) return;
-    for (int j = m0; j < m1; ++j) {
-        const int z = grp.mmask[j];
-        const double coef = grp.mcoef[j];
-        unsigned long long k_plus = 0;
-#pragma unroll
-        for (int o = 0; o < DD; ++o) if (!(__popc(o & z) & 1)) k_plus += hist[o];
-        const unsigned long long k_minus = n_shots - k_plus;
-        const long long out = b * des.m + grp.mk[j];
-        if (expect_out) expect_out[out] = coef * ((double)((long long)k_plus - (long long)k_minus) / nd);
-        if (counts_out) counts_out[out] = nd;
-        if (std_err_out) std_err_out[out] = fabs(coef) * sqrt((double)(k_plus * k_minus) * 4.0 / nd) / nd;
-    }
+    tomog_members_sampled(grp, m0, m1, 0, 1, b * des.m, hist, DD, n_shots, expect_out, counts_out, std_err_out);
 }
 
 static int tomog_check(const fbx_design* design, const fbx_grouping* grouping, int64_t B, const void* truth, int64_t n_shots,
                        int64_t first_item, const void* expect, const void* counts, const void* std_err, const void* exact,
                        const void* prob, const void* hist) {
     const char* who = "fbx_tomo_simulate_grouped";
-    FBX_REQUIRE(B >= 0 && n_shots >= 0 && first_item >= 0, "fbx_tomo_simulate_grouped: need B >= 0, n_shots >= 0 and first_item >= 0");
-    FBX_REQUIRE(n_shots < ((int64_t)1 << 32), "fbx_tomo_simulate_grouped: n_shots must be below 2^32");
+    FBX_TRY(sim_check_batch(who, B, n_shots, first_item));
     FBX_REQUIRE(truth != nullptr, "fbx_tomo_simulate_grouped: NULL truth");
     FBX_REQUIRE(expect || counts || std_err || exact || prob || hist, "fbx_tomo_simulate_grouped: every output is NULL");
     FBX_REQUIRE(n_shots > 0 || !(expect || counts || std_err || hist),
                 "fbx_tomo_simulate_grouped: n_shots == 0 gives exact_out and prob_out only (the sampled outputs must be NULL)");
     FBX_TRY(check_design(design, who));
-    FBX_TRY(check_grouping(grouping, design, who));
-    FBX_REQUIRE(B <= INT64_MAX / 65536 / 4096, "fbx_tomo_simulate_grouped: B * m overflows");
-    return FBX_OK;
+    return check_grouping(grouping, design, who);
 }
 
 }  // namespace fbx
@@ -453,10 +394,10 @@ int fbx_tomo_simulate_grouped_dev(const fbx_design* design, const fbx_grouping* 
     if (B == 0) return FBX_OK;
     const DesignDev& des = design->dev;
     const GroupingDev& grp = grouping->dev;
-    const int truth_len = tomog_truth_len(des);
-    DevBuf scratch;                                  // the status when the caller does not want it (stream order protects it)
-    int32_t* status = d_status_out;
-    if (!status) { FBX_TRY(scratch.alloc(sizeof(int32_t) * (size_t)B)); status = scratch.as<int32_t>(); }
+    const int truth_len = tomo_truth_len(des);
+    StatusBuf status_buf;
+    FBX_TRY(status_buf.take(d_status_out, B));
+    int32_t* status = status_buf.p;
     FBX_TRY(tomo_poison_launch(B, truth_len, 2 * des.n, d_truth, d_readout_flip, status));
     const int64_t units = B * grp.G;
     const bool lane = des.n <= 3 && units >= FBX_TOMOG_LANE_MIN_UNITS;       // (4 and 5 qubits: the wavefront form at any size)
@@ -500,17 +441,14 @@ int fbx_tomo_simulate_grouped(const fbx_design* design, const fbx_grouping* grou
     FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const size_t n = (size_t)B, m = (size_t)design->dev.m, cells = (size_t)grouping->dev.G << design->dev.n;
-    HostIO io; double *dt, *df = nullptr, *de, *dc, *ds, *dx, *dp; uint32_t* dh; int32_t* dst;
-    FBX_TRY(io.in(truth, n * (size_t)tomog_truth_len(design->dev), &dt));
+    HostIO io; SimOut o; double *dt, *df = nullptr, *dp; uint32_t* dh;
+    FBX_TRY(io.in(truth, n * (size_t)tomo_truth_len(design->dev), &dt));
     if (readout_flip) FBX_TRY(io.in(readout_flip, n * 2 * (size_t)design->dev.n, &df));
-    FBX_TRY(io.out_opt(expect_out, n * m, &de));
-    FBX_TRY(io.out_opt(counts_out, n * m, &dc));
-    FBX_TRY(io.out_opt(std_err_out, n * m, &ds));
-    FBX_TRY(io.out_opt(exact_out, n * m, &dx));
+    FBX_TRY(o.stage(io, n, n * m, expect_out, counts_out, std_err_out, exact_out, status_out));
     FBX_TRY(io.out_opt(prob_out, n * cells, &dp));
     FBX_TRY(io.out_opt(hist_out, n * cells, &dh));
-    FBX_TRY(io.out_opt(status_out, n, &dst));
-    FBX_TRY(fbx_tomo_simulate_grouped_dev(design, grouping, B, dt, n_shots, df, seed, first_item, de, dc, ds, dx, dp, dh, dst));
+    FBX_TRY(fbx_tomo_simulate_grouped_dev(design, grouping, B, dt, n_shots, df, seed, first_item, o.expect, o.counts, o.std_err, o.exact,
+                                          dp, dh, o.status));
     return io.finish();
 }
 

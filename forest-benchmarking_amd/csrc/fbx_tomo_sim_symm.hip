@@ -92,24 +92,12 @@ toms_kernel(DesignDev des, GroupingDev grp, const int* __restrict__ cal_mask, in
     if constexpr (STATUS) {
         if (status[b]) return;                                  // (a neighbour's 1 or the truth's: nothing to add)
     } else if (status[b]) {
-        const double nan = __builtin_nan("");
         if constexpr (CAL) {
-            if (lane == 0) {
-                const long long o = b * n_cal + g;
-                if (out.expect) out.expect[o] = nan;
-                if (out.std_err) out.std_err[o] = nan;
-                if (out.exact) out.exact[o] = nan;
-                if (out.counts) out.counts[o] = nd;
-            }
+            if (lane == 0) sim_write_poisoned(out.expect, out.counts, out.std_err, out.exact, b * n_cal + g, N);
         } else {
-            for (int j = m0 + lane; j < m1; j += 64) {
-                const long long o = b * des.m + grp.mk[j];
-                if (out.expect) out.expect[o] = nan;
-                if (out.std_err) out.std_err[o] = nan;
-                if (out.exact) out.exact[o] = nan;
-                if (out.counts) out.counts[o] = nd;
-            }
-            if (out.prob) for (int i = lane; i < dd; i += 64) out.prob[cell * d + i] = nan;
+            for (int j = m0 + lane; j < m1; j += 64)
+                sim_write_poisoned(out.expect, out.counts, out.std_err, out.exact, b * des.m + grp.mk[j], N);
+            if (out.prob) for (int i = lane; i < dd; i += 64) out.prob[cell * d + i] = __builtin_nan("");
             if (out.hist && lane < d) out.hist[cell + lane] = 0u;
         }
         return;
@@ -222,11 +210,7 @@ toms_kernel(DesignDev des, GroupingDev grp, const int* __restrict__ cal_mask, in
         if (j >= nb) { const uint32_t adv = j / nb; pi += adv; j -= adv * nb; }
     }
     FBX_WAVE_SYNC();
-    if (lane < d) {
-        uint32_t h = 0;
-        for (int l = 0; l < 64; ++l) h += cnt[lane * 64 + ((l + lane) & 63)];      // (rotated: the lanes read different banks)
-        hist[lane] = h;
-    }
+    sim_column_sum(cnt, d, lane, hist);
     FBX_WAVE_SYNC();
     if (!CAL && out.hist && lane < d) out.hist[cell + lane] = hist[lane];
     // 5. the members
@@ -245,14 +229,8 @@ toms_kernel(DesignDev des, GroupingDev grp, const int* __restrict__ cal_mask, in
         }
     } else {
         if (!(out.expect || out.counts || out.std_err)) return;
-        for (int jm = m0 + lane; jm < m1; jm += 64) {
-            const double coef = grp.mcoef[jm];
-            const unsigned long long k_plus = k_plus_of(grp.mmask[jm]), k_minus = N - k_plus;
-            const long long o = b * des.m + grp.mk[jm];
-            if (out.expect) out.expect[o] = coef * ((double)((long long)k_plus - (long long)k_minus) / nd);
-            if (out.counts) out.counts[o] = nd;
-            if (out.std_err) out.std_err[o] = fabs(coef) * sqrt((double)(k_plus * k_minus) * 4.0 / nd) / nd;
-        }
+        for (int jm = m0 + lane; jm < m1; jm += 64)
+            sim_write_pm1(out.expect, out.counts, out.std_err, b * des.m + grp.mk[jm], grp.mcoef[jm], k_plus_of(grp.mmask[jm]), N);
     }
 }
 
@@ -291,8 +269,7 @@ static int toms_calibrations(const fbx_design* design) {
 static int toms_check_common(const char* who, const fbx_design* design, int64_t B, const void* confusion, int symm_type,
                              int64_t n_shots, int64_t first_item) {
     const std::string w(who);
-    FBX_REQUIRE(B >= 0 && n_shots >= 0 && first_item >= 0, w + ": need B >= 0, shots >= 0 and first_item >= 0");
-    FBX_REQUIRE(n_shots < ((int64_t)1 << 32), w + ": the shots of a unit must be below 2^32");
+    FBX_TRY(sim_check_batch(who, B, n_shots, first_item, true));
     FBX_REQUIRE(confusion != nullptr, w + ": NULL confusion");
     FBX_REQUIRE(symm_type >= -1 && symm_type <= 3, w + ": symm_type must be -1 (exhaustive), 0 (none) or an orthogonal-array strength 1..3");
     FBX_TRY(check_design(design, who));
@@ -300,7 +277,6 @@ static int toms_check_common(const char* who, const fbx_design* design, int64_t 
         set_error(w + ": orthogonal-array symmetrization (symm_type 1, 2, 3) is not implemented; use -1 (exhaustive) or 0 (none)");
         return FBX_ERR_UNSUPPORTED;
     }
-    FBX_REQUIRE(B <= INT64_MAX / 65536 / 4096, w + ": B * m overflows");
     return FBX_OK;
 }
 
@@ -354,10 +330,10 @@ static int toms_launch(const fbx_design* design, const GroupingDev& grp, const i
                        const double* d_truth, const double* d_confusion, int symm_type, int64_t n_shots, uint64_t seed,
                        int64_t first_item, const SymmOut& out, int32_t* d_status_out, const char* who) {
     const DesignDev& des = design->dev;
-    const int truth_len = CAL ? 0 : tomog_truth_len(des);
-    DevBuf scratch;                                  // the status when the caller does not want it (stream order protects it)
-    int32_t* status = d_status_out;
-    if (!status) { FBX_TRY(scratch.alloc(sizeof(int32_t) * (size_t)B)); status = scratch.as<int32_t>(); }
+    const int truth_len = CAL ? 0 : tomo_truth_len(des);
+    StatusBuf status_buf;
+    FBX_TRY(status_buf.take(d_status_out, B));
+    int32_t* status = status_buf.p;
     if (CAL) FBX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)B, stream()));
     else FBX_TRY(tomo_poison_launch(B, truth_len, 0, d_truth, nullptr, status));
     const int64_t units = B * (CAL ? n_cal : grp.G), blocks = (units + TOMS_WAVES - 1) / TOMS_WAVES;
@@ -412,18 +388,14 @@ int fbx_tomo_simulate_symmetrized(const fbx_design* design, const fbx_grouping* 
     FBX_TRY(ensure_device());
     if (B == 0) return FBX_OK;
     const size_t n = (size_t)B, m = (size_t)design->dev.m, d = (size_t)1 << design->dev.n, cells = (size_t)grouping->dev.G * d;
-    HostIO io; double *dt, *dcf, *de, *dc, *ds, *dx, *dp; uint32_t* dh; int32_t* dst;
-    FBX_TRY(io.in(truth, n * (size_t)tomog_truth_len(design->dev), &dt));
+    HostIO io; SimOut o; double *dt, *dcf, *dp; uint32_t* dh;
+    FBX_TRY(io.in(truth, n * (size_t)tomo_truth_len(design->dev), &dt));
     FBX_TRY(io.in(confusion, n * d * d, &dcf));
-    FBX_TRY(io.out_opt(expect_out, n * m, &de));
-    FBX_TRY(io.out_opt(counts_out, n * m, &dc));
-    FBX_TRY(io.out_opt(std_err_out, n * m, &ds));
-    FBX_TRY(io.out_opt(exact_out, n * m, &dx));
+    FBX_TRY(o.stage(io, n, n * m, expect_out, counts_out, std_err_out, exact_out, status_out));
     FBX_TRY(io.out_opt(prob_out, n * cells * d, &dp));
     FBX_TRY(io.out_opt(hist_out, n * cells, &dh));
-    FBX_TRY(io.out_opt(status_out, n, &dst));
-    FBX_TRY(fbx_tomo_simulate_symmetrized_dev(design, grouping, B, dt, dcf, symm_type, n_shots, seed, first_item, de, dc, ds, dx, dp,
-                                              dh, dst));
+    FBX_TRY(fbx_tomo_simulate_symmetrized_dev(design, grouping, B, dt, dcf, symm_type, n_shots, seed, first_item, o.expect, o.counts,
+                                              o.std_err, o.exact, dp, dh, o.status));
     return io.finish();
 }
 

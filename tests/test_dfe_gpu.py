@@ -11,6 +11,7 @@ import pytest
 import dfe_cases as dc
 from fbx import _lib, clifford_circuit as cc, direct_fidelity_estimation as dfe, synthetic
 from fbx.observable_estimation import calibrate_expectations_batch
+from tomo_sim_cases import TAIL_SHOTS, TAIL_SHOTS_LANE
 
 pytestmark = pytest.mark.gpu
 
@@ -263,6 +264,37 @@ def test_both_sides_of_the_lane_wavefront_switch_give_the_same_bits(gpu):
         assert np.array_equal(a[:4228], b)
     we, _, wse, _ = synthetic.restate_dfe_counts(lane[3][4200:], signs(expt), 7, 99, first_item=4200)
     assert np.array_equal(lane[0][4200:], we) and np.array_equal(lane[2][4200:], wse)
+
+
+def _tail_call(batch, shots):
+    """the smallest experiment (one qubit, m = 1 exhaustive state setting, one noise class) with flips: the device's outputs and
+    the restatement of items [lo, hi)"""
+    gates = circuit(1, 6, seed=3)
+    expt = dfe.generate_exhaustive_state_dfe_experiment(None, gates, [0])
+    assert expt.m == 1
+    rng = np.random.default_rng(17)
+    p, f = rng.uniform(0.0, 0.1, size=(batch, 1)), rng.uniform(0.0, 0.3, size=(batch, 1))
+    got = dfe.simulate_dfe_batch(expt, p, shots, noise_class=np.zeros(len(gates), dtype=np.uint8), readout_flip=f, seed=2024,
+                                 first_item=5, return_std_errs=True, return_exact=True)
+    return got, lambda lo, hi: synthetic.restate_dfe_counts(got[3][lo:hi], signs(expt), shots, 2024, first_item=5 + lo)
+
+
+@pytest.mark.parametrize("shots", TAIL_SHOTS)
+def test_tail_block_on_the_wavefront_split(gpu, shots):
+    """who owns the last, partial Philox block (tomo_sim_cases.TAIL_SHOTS): 3 x 1 units, a wavefront each"""
+    (e, c, se, _), restate = _tail_call(3, shots)
+    we, wc, wse, _ = restate(0, 3)
+    assert np.array_equal(e, we) and np.array_equal(c, wc) and np.array_equal(se, wse)
+
+
+@pytest.mark.parametrize("shots", TAIL_SHOTS_LANE)
+def test_tail_block_on_the_lane_split(gpu, shots):
+    """... and 131072 x 1 units, a lane each: the first and the last items against the restatement"""
+    (e, c, se, _), restate = _tail_call(131072, shots)
+    for lo, hi in ((0, 200), (131072 - 200, 131072)):
+        we, wc, wse, kp = restate(lo, hi)
+        assert np.array_equal(e[lo:hi], we) and np.array_equal(c[lo:hi], wc) and np.array_equal(se[lo:hi], wse)
+        assert len(np.unique(kp)) > 2                        # (counts that vary: the comparison is not of constants)
 
 
 def test_a_later_call_repeats_the_items_of_an_earlier_one(gpu):

@@ -18,6 +18,7 @@ import rpe_cases
 import rpe_sim_cases as cases
 from fbx import robust_phase_estimation as rpe
 from fbx import synthetic
+from tomo_sim_cases import TAIL_SHOTS, TAIL_SHOTS_LANE
 
 pytestmark = pytest.mark.gpu
 
@@ -172,6 +173,43 @@ def test_both_sides_of_the_lane_switch(gpu, two_qubits):
             np.testing.assert_array_equal(big[2][lo:lo + 100], small[2])
             np.testing.assert_array_equal(big[3][lo:lo + 100], small[3])
         assert big[3].sum() == B * 2 * int(np.sum(np.broadcast_to(shots, (K,))))
+
+
+def _tail_call(batch, shots):
+    """the smallest experiment (one qubit, one depth) with flips, with and without records -- two instantiations of the shot
+    kernel, and the records take the shot index from the walk"""
+    rng = np.random.RandomState(10)
+    angles = rng.uniform(0, 2 * math.pi, batch)
+    c, s = np.cos(angles), np.sin(angles)
+    gate = np.zeros((batch, 4, 4))                              # a shrunk turn about z, another one per item
+    gate[:, 0, 0] = gate[:, 3, 3] = 1.0
+    gate[:, 1, 1] = 0.9 * c; gate[:, 1, 2] = -0.9 * s; gate[:, 2, 1] = 0.9 * s; gate[:, 2, 2] = 0.9 * c
+    kw = dict(flips=rng.uniform(0, 0.2, (batch, 1, 2)))
+    moments, _, probs, hist = simulate(gate, 1, kw, num_shots=shots, seed=SEED, first_item=3, return_probabilities=True,
+                                       return_histograms=True)
+    want_hist, want_moments = synthetic.restate_rpe_counts(probs, shots, SEED, first_item=3)
+    np.testing.assert_array_equal(hist.astype(np.int64), want_hist)
+    np.testing.assert_array_equal(moments, want_moments)
+    m2, _, h2, xb, yb = simulate(gate, 1, kw, num_shots=shots, seed=SEED, first_item=3, return_histograms=True, return_records=True)
+    np.testing.assert_array_equal(h2, hist)
+    np.testing.assert_array_equal(m2, moments)
+    assert xb.shape == yb.shape == (batch, 1, shots, 1)
+    for basis, bits in enumerate((xb, yb)):
+        np.testing.assert_array_equal(bits[..., 0].astype(np.int64).sum(axis=2), want_hist[:, :, basis, 1])
+    return want_hist
+
+
+@pytest.mark.parametrize("shots", TAIL_SHOTS)
+def test_tail_block_on_the_wavefront_split(gpu, shots):
+    """who owns the last, partial Philox block (tomo_sim_cases.TAIL_SHOTS): 3 x 1 x 2 units, a wavefront each"""
+    _tail_call(3, shots)
+
+
+@pytest.mark.parametrize("shots", TAIL_SHOTS_LANE)
+def test_tail_block_on_the_lane_split(gpu, shots):
+    """... and lane_min_units() units = B x 1 x 2, a lane each"""
+    hist = _tail_call(lane_min_units() // 2, shots)
+    assert len(np.unique(hist[..., 1])) > 2                  # (counts that vary: the comparison is not of constants)
 
 
 # ------------------------------------------------------------------------------------------------ poison, limits

@@ -123,6 +123,33 @@ def test_both_sides_of_the_lane_switch(gpu):
     check_counts(lane, synthetic.restate_tomography_counts(lane[3], des.coefs, shots, SEED, FIRST), des.coefs, shots)
 
 
+def _tail_call(batch, shots, first_item):
+    """the smallest design (one-qubit SIC, 12 settings) with flips: the device's outputs and the restatement of the same items"""
+    from fbx import synthetic, tomography as t
+    des = design_of("1q-sic")
+    got = t.simulate_process_tomography_batch(des, tc.unitaries(1, batch), shots, rep="unitary", seed=SEED, first_item=first_item,
+                                              readout_flip=sc.asymmetric_flips(1, batch, seed=7), return_std_errs=True,
+                                              return_exact=True)
+    return des, got, lambda lo, hi: synthetic.restate_tomography_counts(got[3][lo:hi], des.coefs, shots, SEED, first_item + lo)
+
+
+@pytest.mark.parametrize("shots", tc.TAIL_SHOTS)
+def test_tail_block_on_the_wavefront_split(gpu, shots):
+    """who owns the last, partial Philox block (tomo_sim_cases.TAIL_SHOTS): 3 x 12 units, a wavefront each"""
+    des, got, restate = _tail_call(3, shots, FIRST)
+    check_counts(got, restate(0, 3), des.coefs, shots)
+
+
+@pytest.mark.parametrize("shots", tc.TAIL_SHOTS_LANE)
+def test_tail_block_on_the_lane_split(gpu, shots):
+    """... and 10923 x 12 >= LANE_MIN_UNITS units, a lane each: the first and the last items against the restatement"""
+    big = LANE_MIN_UNITS // 12 + 1
+    des, got, restate = _tail_call(big, shots, FIRST)
+    assert des.m == 12 and big * des.m >= LANE_MIN_UNITS > (big - 1) * des.m
+    for lo, hi in ((0, 40), (big - 40, big)):
+        check_counts([a[lo:hi] for a in got], restate(lo, hi), des.coefs, shots)
+
+
 # ------------------------------------------------------------------------------------------------ 4. (seed, g, k) only
 def test_a_value_depends_on_seed_item_and_setting_only(gpu):
     from fbx import _lib, sampling, tomography as t

@@ -306,6 +306,37 @@ def test_both_sides_of_the_lane_switch(gpu, case):
         assert np.array_equal(np.delete(a, 7, axis=0), np.delete(b, 7, axis=0))
 
 
+def _tail_call(case, batch, shots):
+    """`batch` items of a case with flips: the device's outputs and the restatement of items [lo, hi)"""
+    from fbx import synthetic
+    des, g = design_of(case), grouping_of(case)
+    n = des.n_qubits
+    truth = dict(truth=tc.mixed_states(n, batch)) if case.startswith("state") else dict(truth=tc.unitaries(n, batch), rep="unitary")
+    got = simulate(case, True, shots, readout_flip=sc.asymmetric_flips(n, batch, seed=7), seed=SEED, first_item=FIRST,
+                   return_std_errs=True, return_exact=True, return_probabilities=True, return_histograms=True, **truth)
+    return got, lambda lo, hi: synthetic.restate_grouped_tomography_counts(got[4][lo:hi], g, des.paulis, des.coefs, shots, SEED,
+                                                                           FIRST + lo)
+
+
+@pytest.mark.parametrize("shots", tc.TAIL_SHOTS)
+@pytest.mark.parametrize("case", ("1q-sic", "state-4"))
+def test_tail_block_on_the_wavefront_split(gpu, case, shots):
+    """who owns the last, partial Philox block (tomo_sim_cases.TAIL_SHOTS), B = 3 and a wavefront per (item, group): the
+    smallest design (one-qubit SIC, 12 groups) counts in registers, four qubits in LDS -- two calls of the walk"""
+    got, restate = _tail_call(case, 3, shots)
+    check_counts(got, restate(0, 3), shots)
+
+
+@pytest.mark.parametrize("shots", tc.TAIL_SHOTS_LANE)
+def test_tail_block_on_the_lane_split(gpu, shots):
+    """... and 10923 x 12 >= LANE_MIN_UNITS units, a lane each: the first and the last items against the restatement"""
+    big = LANE_MIN_UNITS // 12 + 1
+    assert grouping_of("1q-sic").n_groups == 12 and big * 12 >= LANE_MIN_UNITS > (big - 1) * 12
+    got, restate = _tail_call("1q-sic", big, shots)
+    for lo, hi in ((0, 20), (big - 20, big)):
+        check_counts([a[lo:hi] for a in got], restate(lo, hi), shots)
+
+
 # ------------------------------------------------------------------------------------------------ 7. poison
 @pytest.mark.parametrize("what", ("nan-truth", "flip-1.5", "overflowing-group"))
 def test_poisoned_item(gpu, what):

@@ -16,6 +16,12 @@ from fbx_oracle.acquisition import philox4x32_10
 
 SEED = 0x5EED0123456789AB            # both key words in use
 B, FIRST, SHOTS = 5, 3, 4099         # ids that do not start at 0; a shot count that spans many blocks and leaves a tail
+# The last Philox block of a shot count that is no multiple of 4 is owned by one walker of sim_walk (csrc/fbx_sim_shared.hpp),
+# lane (N // 4) % 64 of a wavefront: no full block (lane 0), every residue, N // 4 = 64 (back at lane 0) and N // 4 = 5 (lane 5).
+# Every simulator that draws its shots this way is run at these counts on its wavefront split, and at 5 and 7 on its lane split,
+# where one lane owns every block.
+TAIL_SHOTS = (1, 2, 3, 4, 5, 6, 7, 256, 257, 258, 259, 22)
+TAIL_SHOTS_LANE = (5, 7)
 KEY_TAG = 0x544F4D4F
 EPS = 2.0 ** -53
 COEF_VALUES = (1.0, -1.0, 0.5, -2.0)  # powers of two: exact / coef is exact

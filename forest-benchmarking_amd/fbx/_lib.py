@@ -381,6 +381,11 @@ def iptr(a):
     return None if a is None else a.ctypes.data_as(_ip)
 
 
+def devptr(buf, offset=0):
+    """Device pointer ``offset`` bytes into an optional ``DeviceBuffer`` (None stays None)."""
+    return None if buf is None else buf.at(offset)
+
+
 def ptr(a, ctype):
     """Pointer to a contiguous array as ``POINTER(ctype)`` (None stays None)."""
     return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
@@ -467,8 +472,19 @@ class DeviceBuffer:
     def from_array(cls, arr):
         arr = np.ascontiguousarray(arr)
         buf = cls(arr.nbytes)
-        check(lib().fbx_memcpy_h2d(buf.ptr, arr.ctypes.data_as(_vp), arr.nbytes))
+        try:
+            check(lib().fbx_memcpy_h2d(buf.ptr, arr.ctypes.data_as(_vp), arr.nbytes))
+        except BaseException:
+            buf.free()
+            raise
         return buf
+
+    def at(self, offset):
+        """Pointer ``offset`` bytes into the allocation (one past its end is a valid position, as in C)."""
+        offset = int(offset)
+        if not 0 <= offset <= self.nbytes:
+            raise ValueError(f"offset {offset} is outside a device buffer of {self.nbytes} bytes")
+        return _vp(self.ptr.value + offset)
 
     def to_array(self, dtype, shape):
         out = np.empty(shape, dtype=dtype)
@@ -486,3 +502,32 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class DeviceScope:
+    """Owner of the device buffers of one resident chain (upload, several ``_dev`` calls, download):
+    ``with _lib.DeviceScope() as dev: ...`` frees every buffer ``dev`` handed out when the block ends, however it ends.
+    Allocate inside the block only; a buffer whose allocation raised was never handed out and is not recorded."""
+
+    def __init__(self):
+        self._bufs = []
+
+    def __enter__(self):
+        return self
+
+    def upload(self, arr):
+        """``DeviceBuffer.from_array(arr)`` owned by the scope; None stays None (an optional input)."""
+        if arr is None:
+            return None
+        self._bufs.append(DeviceBuffer.from_array(arr))
+        return self._bufs[-1]
+
+    def alloc(self, nbytes):
+        """An uninitialised buffer of ``nbytes`` (at least 16: an empty output still gets a pointer the library accepts)."""
+        self._bufs.append(DeviceBuffer(max(int(nbytes), 16)))
+        return self._bufs[-1]
+
+    def __exit__(self, *exc):
+        for buf in self._bufs:
+            buf.free()
+        return False

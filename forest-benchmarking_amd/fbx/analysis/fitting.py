@@ -213,18 +213,17 @@ def curve_fit_batch(model: int, x, y, weights=None, param_guesses=None, vary=Non
 def curve_fit_resident(model: int, x, d_y, d_weights, d_guess, B: int, K: int, vary=None, ftol: float = DEFAULT_FTOL,
                        xtol: float = DEFAULT_XTOL, max_iters: int = DEFAULT_MAX_ITERS) -> FitBatch:
     """The same for data that already sit in device memory (``_lib.DeviceBuffer`` of y[B, K], weights[B, K] or None and
-    guess[B, P]; ``x`` [K] on the host): fbx_curve_fit_dev, then one copy of every result back."""
+    guess[B, P], which stay the caller's; ``x`` [K] on the host): fbx_curve_fit_dev, then one copy of every result back."""
     mask = _vary_mask(model, vary)
     P = len(MODELS[model][2])
     x = np.ascontiguousarray(x, dtype=np.float64)
     if x.shape != (K,):
         raise ValueError("Lengths of x and y arrays must be equal.")
-    DB = _lib.DeviceBuffer
-    d_x = DB.from_array(x)
-    outs = [DB(8 * B * P), DB(8 * B * P * P), DB(8 * B), DB(8 * B), DB(4 * B), DB(4 * B), DB(8 * B)]
-    try:
+    with _lib.DeviceScope() as dev:
+        d_x = dev.upload(x)
+        outs = [dev.alloc(n) for n in (8 * B * P, 8 * B * P * P, 8 * B, 8 * B, 4 * B, 4 * B, 8 * B)]
         _lib.check(_lib.lib().fbx_curve_fit_dev(
-            model, B, K, d_x.ptr, 0, d_y.ptr, None if d_weights is None else d_weights.ptr, d_guess.ptr, mask, float(ftol),
+            model, B, K, d_x.ptr, 0, d_y.ptr, _lib.devptr(d_weights), d_guess.ptr, mask, float(ftol),
             float(xtol), int(max_iters), *[o.ptr for o in outs]))
         _lib.synchronize()
         params, covar = outs[0].to_array(np.float64, (B, P)), outs[1].to_array(np.float64, (B, P, P))
@@ -234,9 +233,6 @@ def curve_fit_resident(model: int, x, d_y, d_weights, d_guess, B: int, K: int, v
         y = d_y.to_array(np.float64, (B, K))
         w = None if d_weights is None else d_weights.to_array(np.float64, (B, K))
         g = d_guess.to_array(np.float64, (B, P))
-    finally:
-        for o in outs + [d_x]:
-            o.free()
     return FitBatch(model, x, y, w, g, mask, params, covar, chisqr, redchi, iters, status, gnorm)
 
 

@@ -164,38 +164,17 @@ def measure_graph_state(graph, focal_node, theta=-math.pi / 2):
 
 
 # ------------------------------------------------------------------ resident chains: circuit -> reference -> shots -> statistics
-class _Resident:
-    """Device buffers of one chain, freed together."""
-
-    def __init__(self):
-        from . import _lib
-        self._lib, self.bufs = _lib, []
-
-    def upload(self, arr):
-        if arr is None:
-            return None
-        self.bufs.append(self._lib.DeviceBuffer.from_array(arr))
-        return self.bufs[-1].ptr
-
-    def alloc(self, nbytes):
-        self.bufs.append(self._lib.DeviceBuffer(max(int(nbytes), 16)))
-        return self.bufs[-1]
-
-    def free(self):
-        for b in self.bufs:
-            b.free()
-
-
 def _sample_resident(res, n, gates, B, K, d_ce, cls, d_flips, shots, key):
     """reference -> shots on the device for one circuit: the ``DeviceBuffer`` of the bit records [B, shots, n] and of the status."""
     from . import clifford_circuit as cc
-    lib, check = res._lib.lib(), res._lib.check
+    from . import _lib
+    lib, ptr = _lib.lib(), _lib.devptr
     words = cc.encode_gates(gates, n)
     d_gates, d_cls = res.upload(words if words.size else np.zeros(1, dtype=np.uint32)), res.upload(cls)
     d_ref, d_bits, d_status = res.alloc(8), res.alloc(B * shots * n), res.alloc(4 * B)
-    check(lib.fbx_clifford_reference_sample_dev(n, words.size, d_gates, d_ref.ptr))
-    check(lib.fbx_clifford_sample_shots_dev(n, words.size, d_gates, d_cls, K, d_ref.ptr, B, shots, d_ce, d_flips, key, 0, d_bits.ptr,
-                                            None, d_status.ptr))
+    _lib.check(lib.fbx_clifford_reference_sample_dev(n, words.size, d_gates.ptr, d_ref.ptr))
+    _lib.check(lib.fbx_clifford_sample_shots_dev(n, words.size, d_gates.ptr, ptr(d_cls), K, d_ref.ptr, B, shots, ptr(d_ce), ptr(d_flips),
+                                                 key, 0, d_bits.ptr, None, d_status.ptr))
     return d_bits, d_status
 
 
@@ -222,15 +201,12 @@ def simulate_ghz_statistics_batch(tree, shots, class_error=None, noise_class=Non
     shots, key = int(shots), _stream_seed(seed)
     if shots < 1:
         raise ValueError("need shots >= 1")
-    res = _Resident()
-    try:
+    with _lib.DeviceScope() as res:
         d_bits, d_status = _sample_resident(res, n, gates, B, K, res.upload(ce), cls, res.upload(flips), shots, key)
         d_counts = res.alloc(8 * B * (n + 1))
         _lib.check(_lib.lib().fbx_bit_histogram_dev(n, B, shots, d_bits.ptr, n, None, 1, None, _lib.HIST_WEIGHT, d_counts.ptr))
         counts = d_counts.to_array(np.int64, (B, n + 1))
         _raise_poisoned(d_status.to_array(np.int32, (B,)), "simulate_ghz_statistics_batch")
-    finally:
-        res.free()
     return {"bell": counts[:, 0] + counts[:, n], "total": np.full(B, shots, dtype=np.int64)}
 
 
@@ -253,8 +229,7 @@ def simulate_graph_state_parities_batch(graph, shots, class_error=None, noise_cl
     if shots < 1:
         raise ValueError("need shots >= 1")
     out = np.zeros((B, n))
-    res = _Resident()
-    try:
+    with _lib.DeviceScope() as res:
         d_ce, d_flips = res.upload(ce), res.upload(flips)
         d_mean, d_var = res.alloc(8 * B * n), res.alloc(8 * B * n)
         status = []
@@ -265,12 +240,10 @@ def simulate_graph_state_parities_batch(graph, shots, class_error=None, noise_cl
                                                 (key + i) & (2 ** 64 - 1))
             mask = np.zeros((B, n), dtype=np.uint8)
             mask[:, measured] = 1
-            _lib.check(_lib.lib().fbx_shots_to_moments_dev(n, B, shots, d_bits.ptr, res.upload(mask), None, 0,
-                                                           _lib._vp(d_mean.ptr.value + 8 * B * i), _lib._vp(d_var.ptr.value + 8 * B * i)))
+            _lib.check(_lib.lib().fbx_shots_to_moments_dev(n, B, shots, d_bits.ptr, res.upload(mask).ptr, None, 0,
+                                                           d_mean.at(8 * B * i), d_var.at(8 * B * i)))
             status.append(d_status)
         out[:] = d_mean.to_array(np.float64, (n, B)).T
         for d_status in status:
             _raise_poisoned(d_status.to_array(np.int32, (B,)), "simulate_graph_state_parities_batch")
-    finally:
-        res.free()
     return out

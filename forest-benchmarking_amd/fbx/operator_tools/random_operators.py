@@ -176,10 +176,9 @@ def rand_map_with_BCSZ_dist_batch(dim: int, kraus_rank: int, batch: int, seed: O
     n = _qubits_of(dim)
     B, K, D = int(batch), int(kraus_rank), dim * dim
     lib = _lib.lib()
-    d_k, d_c = _lib.DeviceBuffer(max(16, B * K * D * 16)), _lib.DeviceBuffer(max(16, B * D * D * 16))
-    _lib.check(lib.fbx_random_kraus_dev(n, B, K, _stream_seed(seed), int(first_item), d_k.ptr))
-    _lib.check(lib.fbx_convert_dev(_lib.REP_KRAUS, _lib.REP_CHOI, n, B, d_k.ptr, K, d_c.ptr))
-    _lib.synchronize()
-    out = d_c.to_array(np.complex128, (B, D, D))
-    d_k.free(); d_c.free()
-    return out
+    with _lib.DeviceScope() as dev:
+        d_k, d_c = dev.alloc(B * K * D * 16), dev.alloc(B * D * D * 16)
+        _lib.check(lib.fbx_random_kraus_dev(n, B, K, _stream_seed(seed), int(first_item), d_k.ptr))
+        _lib.check(lib.fbx_convert_dev(_lib.REP_KRAUS, _lib.REP_CHOI, n, B, d_k.ptr, K, d_c.ptr))
+        _lib.synchronize()
+        return d_c.to_array(np.complex128, (B, D, D))

@@ -287,16 +287,13 @@ class RcclComm:
         """Equal-shaped host array per rank -> stacked ``[world, *arr.shape]`` on every rank."""
         _lib = self._lib
         a = np.ascontiguousarray(arr)
-        send = _lib.DeviceBuffer.from_array(a) if a.nbytes else None
-        recv = _lib.DeviceBuffer(max(16, a.nbytes * self.world))
-        if a.nbytes:
-            self.allgather_dev(send.ptr, recv.ptr, a.nbytes)
-        _lib.synchronize()
-        out = recv.to_array(a.dtype, (self.world,) + a.shape) if a.nbytes else np.empty((self.world,) + a.shape, a.dtype)
-        recv.free()
-        if send is not None:
-            send.free()
-        return out
+        with _lib.DeviceScope() as dev:
+            send = dev.upload(a) if a.nbytes else None
+            recv = dev.alloc(a.nbytes * self.world)
+            if a.nbytes:
+                self.allgather_dev(send.ptr, recv.ptr, a.nbytes)
+            _lib.synchronize()
+            return recv.to_array(a.dtype, (self.world,) + a.shape) if a.nbytes else np.empty((self.world,) + a.shape, a.dtype)
 
     def allreduce(self, vec, op="sum"):
         v = np.ascontiguousarray(np.array(vec, dtype=np.float64, copy=True))

@@ -133,11 +133,10 @@ def unpack_heavy_mask(mask, n_qubits: int) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------------------------------ heavy outputs
-def heavy_outputs_flat(n_qubits: int, pairs, gates, probabilities=True, median=True, mask=True, heavy_prob=True, heavy_count=True):
-    """``fbx_qv_heavy_outputs`` on flat gate lists: ``pairs [B, L, 2]`` (q0, q1) and ``gates [B, L, 4, 4]``, applied in order.
-    Returns a dict with the outputs asked for: ``probabilities [B, 2^n]``, ``median [B]``, ``mask [B, W]`` (uint64), ``heavy_prob [B]``,
-    ``heavy_count [B]`` (int32)."""
-    n = int(n_qubits)
+def _heavy_outputs(entry, n, pairs, gates, probabilities, median, mask, heavy_prob, heavy_count, tile_bits=None):
+    """Validation and marshalling of ``heavy_outputs_flat`` (``entry`` = "fbx_qv_heavy_outputs") and of ``heavy_outputs_flat_wide``
+    past 13 qubits ("fbx_qv_heavy_outputs_wide", which takes ``tile_bits`` after the gates)."""
+    wide = tile_bits is not None
     pairs = np.asarray(pairs)
     gates = np.asarray(gates)
     if pairs.ndim != 3 or pairs.shape[2] != 2:
@@ -147,19 +146,21 @@ def heavy_outputs_flat(n_qubits: int, pairs, gates, probabilities=True, median=T
         raise ValueError(f"gates must be [B, L, 4, 4] = {(B, L, 4, 4)}, not {gates.shape}")
     if not (probabilities or median or mask or heavy_prob or heavy_count):
         raise ValueError("no output asked for")
-    if pairs.size and (pairs.min() < 0 or pairs.max() > 255):
-        raise ValueError("qubit indices must be 0..255")
-    pairs = np.ascontiguousarray(pairs, dtype=np.uint8)
+    if not wide:                                         # the narrow path casts first: its checks see what the library will
+        if pairs.size and (pairs.min() < 0 or pairs.max() > 255):
+            raise ValueError("qubit indices must be 0..255")
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint8)
     if n >= 1 and pairs.size:
-        if pairs.max() >= n:
+        if pairs.min() < 0 or pairs.max() >= n:
             raise ValueError(f"a qubit index is out of range for {n} qubits")
         if np.any(pairs[..., 0] == pairs[..., 1]):
             raise ValueError("a gate needs two different qubits")
+    pairs = np.ascontiguousarray(pairs, dtype=np.uint8)
     from . import _lib
     import ctypes as C
     gates = _lib.c128(gates)
     N, W = 1 << max(n, 0), _mask_words(max(n, 0))
-    ok = MIN_WIDTH <= n <= MAX_WIDTH                     # (outside, the library refuses before it touches a buffer)
+    ok = wide or MIN_WIDTH <= n <= MAX_WIDTH             # (outside, the library refuses before it touches a buffer)
     out = {}
     if probabilities:
         out["probabilities"] = np.empty((B, N if ok else 0))
@@ -171,12 +172,19 @@ def heavy_outputs_flat(n_qubits: int, pairs, gates, probabilities=True, median=T
         out["heavy_prob"] = np.empty(B)
     if heavy_count:
         out["heavy_count"] = np.empty(B, dtype=np.int32)
-    _lib.check(_lib.lib().fbx_qv_heavy_outputs(
-        n, B, L, pairs.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(gates.view(np.float64)),
+    _lib.check(getattr(_lib.lib(), entry)(
+        n, B, L, pairs.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(gates.view(np.float64)), *((tile_bits,) if wide else ()),
         _lib.dptr(out.get("probabilities")), _lib.dptr(out.get("median")),
         out["mask"].ctypes.data_as(C.POINTER(C.c_uint64)) if mask else None,
         _lib.dptr(out.get("heavy_prob")), _lib.iptr(out.get("heavy_count"))))
     return out
+
+
+def heavy_outputs_flat(n_qubits: int, pairs, gates, probabilities=True, median=True, mask=True, heavy_prob=True, heavy_count=True):
+    """``fbx_qv_heavy_outputs`` on flat gate lists: ``pairs [B, L, 2]`` (q0, q1) and ``gates [B, L, 4, 4]``, applied in order.
+    Returns a dict with the outputs asked for: ``probabilities [B, 2^n]``, ``median [B]``, ``mask [B, W]`` (uint64), ``heavy_prob [B]``,
+    ``heavy_count [B]`` (int32)."""
+    return _heavy_outputs("fbx_qv_heavy_outputs", int(n_qubits), pairs, gates, probabilities, median, mask, heavy_prob, heavy_count)
 
 
 def _flatten_circuits(permutations, gates, pairing):
@@ -191,6 +199,16 @@ def _flatten_circuits(permutations, gates, pairing):
     return width, pairs.reshape(B, depth * (width // 2), 2), gates.reshape(B, depth * (width // 2), 4, 4)
 
 
+def _collected(r, width, return_probabilities, return_stats):
+    """What ``collect_heavy_outputs_batch`` returns, from the dict ``r`` of ``heavy_outputs_flat``."""
+    res = [unpack_heavy_mask(r["mask"], width)]
+    if return_probabilities:
+        res.append(r["probabilities"])
+    if return_stats:
+        res.append({k: r[k] for k in ("median", "heavy_prob", "heavy_count")})
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 def collect_heavy_outputs_batch(permutations, gates, pairing: str = "reference", return_probabilities: bool = False,
                                 return_stats: bool = False):
     """The heavy outputs of B model circuits of one width in one launch: ``permutations [B, depth, width]``,
@@ -199,12 +217,7 @@ def collect_heavy_outputs_batch(permutations, gates, pairing: str = "reference",
     width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
     r = heavy_outputs_flat(width, pairs, flat, probabilities=return_probabilities, median=return_stats, mask=True,
                            heavy_prob=return_stats, heavy_count=return_stats)
-    res = [unpack_heavy_mask(r["mask"], width)]
-    if return_probabilities:
-        res.append(r["probabilities"])
-    if return_stats:
-        res.append({k: r[k] for k in ("median", "heavy_prob", "heavy_count")})
-    return res[0] if len(res) == 1 else tuple(res)
+    return _collected(r, width, return_probabilities, return_stats)
 
 
 def ideal_heavy_output_probability_batch(permutations, gates, pairing: str = "reference") -> np.ndarray:
@@ -224,32 +237,29 @@ def collect_heavy_outputs(wfn_sim, permutations, gates) -> List[int]:
 
 
 # ------------------------------------------------------------------------------------------------ counts
-def count_heavy_hitters_sampled_batch(bitarrays, heavy) -> np.ndarray:
-    """``bitarrays [B, shots, n]`` (0/1, first column = qubit 0, as ``qc.run`` returns them) and ``heavy`` -- the boolean table
-    ``[B, 2^n]`` or the packed masks ``[B, W]`` (uint64) -- -> the number of heavy shots of every circuit, ``[B]`` int64."""
+def _count_heavy_hitters(entry, bitarrays, heavy) -> np.ndarray:
+    """Validation and marshalling of the heavy-hitter count: ``entry`` = "fbx_qv_count_heavy" or "fbx_qv_count_heavy_wide"."""
     bits = np.asarray(bitarrays)
     if bits.ndim != 3:
         raise ValueError("bitarrays must be [B, shots, n_qubits]")
     B, shots, n = bits.shape
-    heavy = np.asarray(heavy)
-    if heavy.dtype == np.uint64:
-        mask = np.ascontiguousarray(heavy)
-        if mask.shape != (B, _mask_words(n)):
-            raise ValueError(f"masks must be [B, W] = {(B, _mask_words(n))}, not {mask.shape}")
-    else:
-        if heavy.shape != (B, 1 << n):
-            raise ValueError(f"heavy must be a boolean table [B, 2^n] = {(B, 1 << n)}, not {heavy.shape}")
-        mask = pack_heavy_mask(heavy)
+    mask = _heavy_masks(heavy, B, n)
     if bits.size and (bits.min() < 0 or bits.max() > 1):
         raise ValueError("bitarrays must hold 0 / 1")
     bits = np.ascontiguousarray(bits, dtype=np.uint8)
     from . import _lib
     import ctypes as C
     counts = np.zeros(B, dtype=np.int64)
-    _lib.check(_lib.lib().fbx_qv_count_heavy(n, B, shots, bits.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                             mask.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                             counts.ctypes.data_as(C.POINTER(C.c_int64))))
+    _lib.check(getattr(_lib.lib(), entry)(n, B, shots, bits.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          mask.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                          counts.ctypes.data_as(C.POINTER(C.c_int64))))
     return counts
+
+
+def count_heavy_hitters_sampled_batch(bitarrays, heavy) -> np.ndarray:
+    """``bitarrays [B, shots, n]`` (0/1, first column = qubit 0, as ``qc.run`` returns them) and ``heavy`` -- the boolean table
+    ``[B, 2^n]`` or the packed masks ``[B, W]`` (uint64) -- -> the number of heavy shots of every circuit, ``[B]`` int64."""
+    return _count_heavy_hitters("fbx_qv_count_heavy", bitarrays, heavy)
 
 
 def count_heavy_hitters_sampled(qc_results: Iterator[np.ndarray], heavy_hitters: Iterator[List[int]]) -> Iterator[int]:
@@ -342,42 +352,7 @@ def heavy_outputs_flat_wide(n_qubits: int, pairs, gates, probabilities=True, med
     tile_bits = _check_wide(n, tile_bits, "heavy_outputs_flat_wide")
     if n <= MAX_WIDTH:
         return heavy_outputs_flat(n, pairs, gates, probabilities, median, mask, heavy_prob, heavy_count)
-    pairs = np.asarray(pairs)
-    gates = np.asarray(gates)
-    if pairs.ndim != 3 or pairs.shape[2] != 2:
-        raise ValueError("pairs must be [B, L, 2]")
-    B, L = pairs.shape[:2]
-    if gates.shape != (B, L, 4, 4):
-        raise ValueError(f"gates must be [B, L, 4, 4] = {(B, L, 4, 4)}, not {gates.shape}")
-    if not (probabilities or median or mask or heavy_prob or heavy_count):
-        raise ValueError("no output asked for")
-    if pairs.size:
-        if pairs.min() < 0 or pairs.max() >= n:
-            raise ValueError(f"a qubit index is out of range for {n} qubits")
-        if np.any(pairs[..., 0] == pairs[..., 1]):
-            raise ValueError("a gate needs two different qubits")
-    pairs = np.ascontiguousarray(pairs, dtype=np.uint8)
-    from . import _lib
-    import ctypes as C
-    gates = _lib.c128(gates)
-    N, W = 1 << n, _mask_words(n)
-    out = {}
-    if probabilities:
-        out["probabilities"] = np.empty((B, N))
-    if median:
-        out["median"] = np.empty(B)
-    if mask:
-        out["mask"] = np.zeros((B, W), dtype=np.uint64)
-    if heavy_prob:
-        out["heavy_prob"] = np.empty(B)
-    if heavy_count:
-        out["heavy_count"] = np.empty(B, dtype=np.int32)
-    _lib.check(_lib.lib().fbx_qv_heavy_outputs_wide(
-        n, B, L, pairs.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.dptr(gates.view(np.float64)), tile_bits,
-        _lib.dptr(out.get("probabilities")), _lib.dptr(out.get("median")),
-        out["mask"].ctypes.data_as(C.POINTER(C.c_uint64)) if mask else None,
-        _lib.dptr(out.get("heavy_prob")), _lib.iptr(out.get("heavy_count"))))
-    return out
+    return _heavy_outputs("fbx_qv_heavy_outputs_wide", n, pairs, gates, probabilities, median, mask, heavy_prob, heavy_count, tile_bits)
 
 
 def collect_heavy_outputs_wide_batch(permutations, gates, pairing: str = "reference", return_probabilities: bool = False,
@@ -386,12 +361,7 @@ def collect_heavy_outputs_wide_batch(permutations, gates, pairing: str = "refere
     width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
     r = heavy_outputs_flat_wide(width, pairs, flat, probabilities=return_probabilities, median=return_stats, mask=True,
                                 heavy_prob=return_stats, heavy_count=return_stats, tile_bits=tile_bits)
-    res = [unpack_heavy_mask(r["mask"], width)]
-    if return_probabilities:
-        res.append(r["probabilities"])
-    if return_stats:
-        res.append({k: r[k] for k in ("median", "heavy_prob", "heavy_count")})
-    return res[0] if len(res) == 1 else tuple(res)
+    return _collected(r, width, return_probabilities, return_stats)
 
 
 def ideal_heavy_output_probability_wide_batch(permutations, gates, pairing: str = "reference", tile_bits: int = 0) -> np.ndarray:
@@ -407,32 +377,58 @@ def count_heavy_hitters_sampled_wide_batch(bitarrays, heavy, tile_bits: int = 0)
     bits = np.asarray(bitarrays)
     if bits.ndim != 3:
         raise ValueError("bitarrays must be [B, shots, n_qubits]")
-    B, shots, n = bits.shape
+    n = bits.shape[2]
     _check_wide(n, tile_bits, "count_heavy_hitters_sampled_wide_batch")
     if n <= MAX_WIDTH:
         return count_heavy_hitters_sampled_batch(bits, heavy)
-    heavy = np.asarray(heavy)
-    if heavy.dtype == np.uint64:
-        mask = np.ascontiguousarray(heavy)
-        if mask.shape != (B, _mask_words(n)):
-            raise ValueError(f"masks must be [B, W] = {(B, _mask_words(n))}, not {mask.shape}")
-    else:
-        if heavy.shape != (B, 1 << n):
-            raise ValueError(f"heavy must be a boolean table [B, 2^n] = {(B, 1 << n)}, not {heavy.shape}")
-        mask = pack_heavy_mask(heavy)
-    if bits.size and (bits.min() < 0 or bits.max() > 1):
-        raise ValueError("bitarrays must hold 0 / 1")
-    bits = np.ascontiguousarray(bits, dtype=np.uint8)
-    from . import _lib
-    import ctypes as C
-    counts = np.zeros(B, dtype=np.int64)
-    _lib.check(_lib.lib().fbx_qv_count_heavy_wide(n, B, shots, bits.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                  mask.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                  counts.ctypes.data_as(C.POINTER(C.c_int64))))
-    return counts
+    return _count_heavy_hitters("fbx_qv_count_heavy_wide", bits, heavy)
 
 
 # ------------------------------------------------------------------------------------------------ simulated runs
+def _simulate_counts_resident(wide, width, pairs, flat, shots, depolarizing, readout_flip, seed, tile_bits=0, max_resident_mib=None):
+    """The resident chain of ``simulate_heavy_output_counts_batch`` and, with ``wide``, of its wide twin past 13 qubits: heavy
+    outputs -> shots -> counts in slices of circuits whose probabilities (8 B x 2^n per circuit) and shot bytes stay under
+    ``max_resident_mib`` (None: one slice, the narrow chain).  The slice that starts at circuit k is sampled with
+    ``first_item = k``.  Only the wide heavy-outputs entry point takes ``tile_bits``; an item that cannot be sampled is reported
+    under the wide function's name there and as the sampler reports it (the default of ``sampling._raise_poisoned``) here."""
+    from . import _lib
+    from .sampling import _noise, _raise_poisoned
+    lib = _lib.lib()
+    if wide:
+        heavy_outputs, sample = lib.fbx_qv_heavy_outputs_wide_dev, lib.fbx_sample_bitstrings_wide_dev
+        count = lib.fbx_qv_count_heavy_wide_dev
+        tile, who = (tile_bits,), ("simulate_heavy_output_counts_wide_batch",)
+    else:
+        heavy_outputs, sample = lib.fbx_qv_heavy_outputs_dev, lib.fbx_sample_bitstrings_dev
+        count = lib.fbx_qv_count_heavy_dev
+        tile, who = (), ()
+    B, L = pairs.shape[:2]
+    N, W = 1 << width, _mask_words(width)
+    shots, lam, flips, _ = _noise(B, width, shots, depolarizing, readout_flip)
+    key = _stream_seed(seed)
+    if B == 0:
+        return np.zeros(0, dtype=np.int64), {"heavy_prob": np.zeros(0), "heavy_count": np.zeros(0, dtype=np.int32)}
+    cut = B if max_resident_mib is None else int(max(1, min(B, max_resident_mib * 1048576.0 // (8 * N + shots * width))))
+    with _lib.DeviceScope() as dev:
+        d_pairs, d_gates = dev.upload(pairs), dev.upload(_lib.c128(flat))
+        d_lam, d_flips = dev.upload(lam), dev.upload(flips)
+        d_probs, d_mask = dev.alloc(8 * cut * N), dev.alloc(8 * cut * W)
+        d_bits = dev.alloc(cut * shots * width)
+        d_hp, d_hc, d_status, d_counts = dev.alloc(8 * B), dev.alloc(4 * B), dev.alloc(4 * B), dev.alloc(8 * B)
+        for k in range(0, B, cut):
+            cb = min(cut, B - k)
+            _lib.check(heavy_outputs(width, cb, L, d_pairs.at(2 * L * k), d_gates.at(256 * L * k), *tile, d_probs.ptr, None,
+                                     d_mask.ptr, d_hp.at(8 * k), d_hc.at(4 * k)))
+            _lib.check(sample(width, cb, shots, d_probs.ptr, _lib.devptr(d_lam, 8 * k), _lib.devptr(d_flips, 16 * width * k), key, k,
+                              d_bits.ptr, d_status.at(4 * k)))
+            _lib.check(count(width, cb, shots, d_bits.ptr, d_mask.ptr, d_counts.at(8 * k)))
+        counts = d_counts.to_array(np.int64, (B,))
+        stats = {"heavy_prob": d_hp.to_array(np.float64, (B,)), "heavy_count": d_hc.to_array(np.int32, (B,))}
+        if shots:
+            _raise_poisoned(d_status.to_array(np.int32, (B,)), 0, *who)
+    return counts, stats
+
+
 def simulate_heavy_output_counts_batch(permutations, gates, shots: int, depolarizing=0.0, readout_flip=None,
                                        seed: Optional[int] = None, pairing: str = "reference"):
     """A simulated quantum-volume run of B model circuits of one width, resident on the device: ideal output distributions
@@ -446,43 +442,11 @@ def simulate_heavy_output_counts_batch(permutations, gates, shots: int, depolari
     Circuit b draws from item b of the Philox stream keyed by ``seed`` (``None``: a fresh key, the rule of ``random_operators``),
     so the counts equal those of the composed host calls on the same seed."""
     from . import _lib
-    from .sampling import _noise, _raise_poisoned
     width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
-    B, L = pairs.shape[:2]
     if not MIN_WIDTH <= width <= MAX_WIDTH:
         raise _lib.FbxError(_lib.FBX_ERR_UNSUPPORTED, f"simulate_heavy_output_counts_batch: width must be {MIN_WIDTH}..{MAX_WIDTH} "
                                                       f"(got {width}); there is no host fallback")
-    N, W = 1 << width, _mask_words(width)
-    shots, lam, flips, _ = _noise(B, width, shots, depolarizing, readout_flip)
-    key = _stream_seed(seed)
-    if B == 0:
-        return np.zeros(0, dtype=np.int64), {"heavy_prob": np.zeros(0), "heavy_count": np.zeros(0, dtype=np.int32)}
-    DB = _lib.DeviceBuffer
-    lib = _lib.lib()
-    bufs = []
-
-    def dev(x):
-        bufs.append(x)
-        return x
-    try:
-        d_pairs, d_gates = dev(DB.from_array(pairs)), dev(DB.from_array(_lib.c128(flat)))
-        d_lam = dev(DB.from_array(lam)) if lam is not None else None
-        d_flips = dev(DB.from_array(flips)) if flips is not None else None
-        d_probs, d_mask, d_hp, d_hc = dev(DB(8 * B * N)), dev(DB(8 * B * W)), dev(DB(8 * B)), dev(DB(4 * B))
-        d_bits, d_status, d_counts = dev(DB(max(B * shots * width, 16))), dev(DB(4 * B)), dev(DB(8 * B))
-        _lib.check(lib.fbx_qv_heavy_outputs_dev(width, B, L, d_pairs.ptr, d_gates.ptr, d_probs.ptr, None, d_mask.ptr, d_hp.ptr,
-                                                d_hc.ptr))
-        _lib.check(lib.fbx_sample_bitstrings_dev(width, B, shots, d_probs.ptr, d_lam.ptr if d_lam else None,
-                                                 d_flips.ptr if d_flips else None, key, 0, d_bits.ptr, d_status.ptr))
-        _lib.check(lib.fbx_qv_count_heavy_dev(width, B, shots, d_bits.ptr, d_mask.ptr, d_counts.ptr))
-        counts = d_counts.to_array(np.int64, (B,))
-        stats = {"heavy_prob": d_hp.to_array(np.float64, (B,)), "heavy_count": d_hc.to_array(np.int32, (B,))}
-        if shots:
-            _raise_poisoned(d_status.to_array(np.int32, (B,)), 0)
-    finally:
-        for b in bufs:
-            b.free()
-    return counts, stats
+    return _simulate_counts_resident(False, width, pairs, flat, shots, depolarizing, readout_flip, seed)
 
 
 def simulate_heavy_output_counts_wide_batch(permutations, gates, shots: int, depolarizing=0.0, readout_flip=None,
@@ -497,55 +461,14 @@ def simulate_heavy_output_counts_wide_batch(permutations, gates, shots: int, dep
     ``sampling.sample_bitstrings_wide_batch`` -> ``count_heavy_hitters_sampled_wide_batch``) on the same seed.
 
     Returns ``(counts [B] int64, stats)`` as the narrow function does."""
-    import ctypes as C
-    from . import _lib
-    from .sampling import _noise, _raise_poisoned
     width, pairs, flat = _flatten_circuits(permutations, gates, pairing)
     tile_bits = _check_wide(width, tile_bits, "simulate_heavy_output_counts_wide_batch")
     if not float(max_resident_mib) > 0.0:
         raise ValueError("simulate_heavy_output_counts_wide_batch: max_resident_mib must be positive")
     if width <= MAX_WIDTH:
         return simulate_heavy_output_counts_batch(permutations, gates, shots, depolarizing, readout_flip, seed, pairing)
-    B, L = pairs.shape[:2]
-    N, W = 1 << width, _mask_words(width)
-    shots, lam, flips, _ = _noise(B, width, shots, depolarizing, readout_flip)
-    key = _stream_seed(seed)
-    if B == 0:
-        return np.zeros(0, dtype=np.int64), {"heavy_prob": np.zeros(0), "heavy_count": np.zeros(0, dtype=np.int32)}
-    per = 8 * N + shots * width
-    cut = int(max(1, min(B, float(max_resident_mib) * 1048576.0 // per)))
-    DB = _lib.DeviceBuffer
-    lib = _lib.lib()
-    bufs = []
-
-    def dev(x):
-        bufs.append(x)
-        return x
-
-    def at(buf, offset):
-        return None if buf is None else C.c_void_p(buf.ptr.value + offset)
-    try:
-        d_pairs, d_gates = dev(DB.from_array(pairs)), dev(DB.from_array(_lib.c128(flat)))
-        d_lam = dev(DB.from_array(lam)) if lam is not None else None
-        d_flips = dev(DB.from_array(flips)) if flips is not None else None
-        d_probs, d_mask = dev(DB(8 * cut * N)), dev(DB(8 * cut * W))
-        d_bits = dev(DB(max(cut * shots * width, 16)))
-        d_hp, d_hc, d_status, d_counts = dev(DB(8 * B)), dev(DB(4 * B)), dev(DB(4 * B)), dev(DB(8 * B))
-        for k in range(0, B, cut):
-            cb = min(cut, B - k)
-            _lib.check(lib.fbx_qv_heavy_outputs_wide_dev(width, cb, L, at(d_pairs, 2 * L * k), at(d_gates, 256 * L * k), tile_bits,
-                                                         d_probs.ptr, None, d_mask.ptr, at(d_hp, 8 * k), at(d_hc, 4 * k)))
-            _lib.check(lib.fbx_sample_bitstrings_wide_dev(width, cb, shots, d_probs.ptr, at(d_lam, 8 * k),
-                                                          at(d_flips, 16 * width * k), key, k, d_bits.ptr, at(d_status, 4 * k)))
-            _lib.check(lib.fbx_qv_count_heavy_wide_dev(width, cb, shots, d_bits.ptr, d_mask.ptr, at(d_counts, 8 * k)))
-        counts = d_counts.to_array(np.int64, (B,))
-        stats = {"heavy_prob": d_hp.to_array(np.float64, (B,)), "heavy_count": d_hc.to_array(np.int32, (B,))}
-        if shots:
-            _raise_poisoned(d_status.to_array(np.int32, (B,)), 0, "simulate_heavy_output_counts_wide_batch")
-    finally:
-        for b in bufs:
-            b.free()
-    return counts, stats
+    return _simulate_counts_resident(True, width, pairs, flat, shots, depolarizing, readout_flip, seed, tile_bits,
+                                     float(max_resident_mib))
 
 
 # ------------------------------------------------------------------------------------------------ gate noise
@@ -708,23 +631,17 @@ def simulate_noisy_heavy_output_counts_batch(permutations, gates, shots: int, ga
     if B == 0:
         return np.zeros(0, dtype=np.int64), {"heavy_prob": np.zeros(0), "heavy_count": np.zeros(0, dtype=np.int32),
                                              "noisy_heavy_prob": np.zeros(0), "noisy_heavy_prob_err": np.zeros(0)}
-    DB = _lib.DeviceBuffer
     lib = _lib.lib()
-    bufs = []
-
-    def dev(x):
-        bufs.append(x)
-        return x
-    try:
-        d_pairs, d_gates, d_ge = dev(DB.from_array(pairs)), dev(DB.from_array(_lib.c128(flat))), dev(DB.from_array(ge))
-        d_flips = dev(DB.from_array(flips)) if flips is not None else None
-        d_probs, d_mask, d_hp, d_hc = dev(DB(8 * B * N)), dev(DB(8 * B * W)), dev(DB(8 * B)), dev(DB(4 * B))
-        d_traj, d_tstatus = dev(DB(8 * B * T)), dev(DB(4 * B))
-        d_bits, d_status, d_counts = dev(DB(max(B * shots * width, 16))), dev(DB(4 * B)), dev(DB(8 * B))
+    with _lib.DeviceScope() as dev:
+        d_pairs, d_gates, d_ge = dev.upload(pairs), dev.upload(_lib.c128(flat)), dev.upload(ge)
+        d_flips = dev.upload(flips)
+        d_probs, d_mask, d_hp, d_hc = dev.alloc(8 * B * N), dev.alloc(8 * B * W), dev.alloc(8 * B), dev.alloc(4 * B)
+        d_traj, d_tstatus = dev.alloc(8 * B * T), dev.alloc(4 * B)
+        d_bits, d_status, d_counts = dev.alloc(B * shots * width), dev.alloc(4 * B), dev.alloc(8 * B)
         _lib.check(lib.fbx_qv_heavy_outputs_dev(width, B, L, d_pairs.ptr, d_gates.ptr, None, None, d_mask.ptr, d_hp.ptr, d_hc.ptr))
         _lib.check(lib.fbx_qv_noisy_trajectories_dev(width, B, L, T, d_pairs.ptr, d_gates.ptr, d_ge.ptr, d_mask.ptr, key, 0,
                                                      d_probs.ptr, d_traj.ptr, None, d_tstatus.ptr))
-        _lib.check(lib.fbx_sample_bitstrings_dev(width, B, shots, d_probs.ptr, None, d_flips.ptr if d_flips else None, key, 0,
+        _lib.check(lib.fbx_sample_bitstrings_dev(width, B, shots, d_probs.ptr, None, _lib.devptr(d_flips), key, 0,
                                                  d_bits.ptr, d_status.ptr))
         _lib.check(lib.fbx_qv_count_heavy_dev(width, B, shots, d_bits.ptr, d_mask.ptr, d_counts.ptr))
         counts = d_counts.to_array(np.int64, (B,))
@@ -735,9 +652,6 @@ def simulate_noisy_heavy_output_counts_batch(permutations, gates, shots: int, ga
         _raise_poisoned_circuit(d_tstatus.to_array(np.int32, (B,)), 0, "simulate_noisy_heavy_output_counts_batch")
         if shots:
             _raise_poisoned(d_status.to_array(np.int32, (B,)), 0, "simulate_noisy_heavy_output_counts_batch")
-    finally:
-        for b in bufs:
-            b.free()
     return counts, stats
 
 

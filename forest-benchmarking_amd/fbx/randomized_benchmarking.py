@@ -101,10 +101,14 @@ def z_obs_stats_to_survival_statistics(expectations: Sequence[float], std_errs: 
     return float(surv[0]), float(var[0])
 
 
-def _resident_decay_fit(kind, depths, d_values, d_errors, errors_are_variances, B, K, param_guesses, fit_kw):
-    DB = _lib.DeviceBuffer
-    d_w, d_g, d_has = DB(8 * B * K), DB(8 * B * 3), DB(4 * B)
-    try:
+def _fit_decays_resident(statistics, kind, depths, e, s, errors_are_variances, param_guesses, fit_kw):
+    """upload -> statistics kernel -> ``fbx_fit_prepare_dev`` -> resident decay fit, for expectations / std_errs [B, K, ...]:
+    ``statistics(d_e, d_s, d_values, d_errors)`` issues the kernel that turns them into the [B, K] values to fit and their errors."""
+    B, K = e.shape[:2]
+    with _lib.DeviceScope() as dev:
+        d_e, d_s, d_values, d_errors = dev.upload(e), dev.upload(s), dev.alloc(8 * B * K), dev.alloc(8 * B * K)
+        _lib.check(statistics(d_e.ptr, d_s.ptr, d_values.ptr, d_errors.ptr))
+        d_w, d_g, d_has = dev.alloc(8 * B * K), dev.alloc(8 * B * 3), dev.alloc(4 * B)
         _lib.check(_lib.lib().fbx_fit_prepare_dev(kind, B, K, d_values.ptr, d_errors.ptr, int(errors_are_variances),
                                                   d_w.ptr, d_g.ptr, d_has.ptr))
         if param_guesses is not None:
@@ -112,9 +116,6 @@ def _resident_decay_fit(kind, depths, d_values, d_errors, errors_are_variances, 
             _lib.check(_lib.lib().fbx_memcpy_h2d(d_g.ptr, g.ctypes.data, g.nbytes))
         batch = fitting.curve_fit_resident(_lib.FIT_BASE_DECAY, depths, d_values, d_w, d_g, B, K, **fit_kw)
         batch.has_weights = d_has.to_array(np.int32, (B,)).astype(bool)
-    finally:
-        for b in (d_w, d_g, d_has):
-            b.free()
     return batch
 
 
@@ -130,14 +131,9 @@ def fit_rb_results_batch(depths: Sequence[int], z_expectations, z_std_errs, num_
     assert len(depths) == K, 'There should be one expectation per sequence and depths should give the depth of each sequence.'
     assert _is_pos_pow_two(dim)
     shots = _shots_for_covariance(dim, num_shots, False)
-    DB = _lib.DeviceBuffer
-    d_e, d_s, d_surv, d_var = DB.from_array(e), DB.from_array(s), DB(8 * B * K), DB(8 * B * K)
-    try:
-        _lib.check(_lib.lib().fbx_rb_survival_dev(dim, B * K, d_e.ptr, d_s.ptr, shots, d_surv.ptr, d_var.ptr))
-        return _resident_decay_fit(_lib.FIT_PREPARE_RB, depths, d_surv, d_var, True, B, K, param_guesses, fit_kw)
-    finally:
-        for b in (d_e, d_s, d_surv, d_var):
-            b.free()
+    lib = _lib.lib()
+    return _fit_decays_resident(lambda d_e, d_s, d_surv, d_var: lib.fbx_rb_survival_dev(dim, B * K, d_e, d_s, shots, d_surv, d_var),
+                                _lib.FIT_PREPARE_RB, depths, e, s, True, param_guesses, fit_kw)
 
 
 def fit_rb_results(depths: Sequence[int], z_expectations: Sequence[Sequence[float]], z_std_errs: Sequence[Sequence[float]],
@@ -194,14 +190,9 @@ def fit_unitarity_results_batch(depths: Sequence[int], expectations, std_errs, p
     B, K = e.shape[:2]
     assert len(depths) == K, 'There should be one group of 4**(num_qubits) - 1 expectations per sequence and depths should ' \
                              'give the depth of each sequence.'
-    DB = _lib.DeviceBuffer
-    d_e, d_s, d_pur, d_err = DB.from_array(e), DB.from_array(s), DB(8 * B * K), DB(8 * B * K)
-    try:
-        _lib.check(_lib.lib().fbx_rb_purity_dev(dim, B * K, d_e.ptr, d_s.ptr, 1, d_pur.ptr, d_err.ptr))
-        return _resident_decay_fit(_lib.FIT_PREPARE_UNITARITY, depths, d_pur, d_err, False, B, K, param_guesses, fit_kw)
-    finally:
-        for b in (d_e, d_s, d_pur, d_err):
-            b.free()
+    lib = _lib.lib()
+    return _fit_decays_resident(lambda d_e, d_s, d_pur, d_err: lib.fbx_rb_purity_dev(dim, B * K, d_e, d_s, 1, d_pur, d_err),
+                                _lib.FIT_PREPARE_UNITARITY, depths, e, s, False, param_guesses, fit_kw)
 
 
 def fit_unitarity_results(depths: Sequence[int], expectations: Sequence[Sequence[float]], std_errs: Sequence[Sequence[float]],

@@ -311,37 +311,28 @@ def phase_variance_batch(x, y, x_err, y_err, num_shots, n_resamples: int = 200, 
     if not prior_counts > 0:
         raise ValueError("prior_counts must be positive")
     from . import _lib
-    import ctypes as C
-    lib, DB = _lib.lib(), _lib.DeviceBuffer
+    lib = _lib.lib()
     seed = int(seed) & (2 ** 64 - 1)
     seed_y = (seed ^ 0x9E3779B97F4A7C15) & (2 ** 64 - 1)              # X and Y are independent draws
-    bufs = [DB.from_array(a) for a in (x, y, counts)]
-    d_x, d_y, d_c = bufs
-    # item-major [B][R][K]: item b is redrawn by a launch of its own, so its streams do not know b
-    d_xe = DB.from_array(np.ascontiguousarray(np.broadcast_to(xe[:, None, :], (B, R, K))))
-    d_ye = DB.from_array(np.ascontiguousarray(np.broadcast_to(ye[:, None, :], (B, R, K))))
-    d_xr, d_yr = DB(B * R * K * 8), DB(B * R * K * 8)
-    d_phase, d_mean, d_std, d_nan = DB(B * R * 8), DB(B * 8), DB(B * 8), DB(B * 4)
-    bufs += [d_xe, d_ye, d_xr, d_yr, d_phase, d_mean, d_std, d_nan]
-
-    def at(buf, offset):
-        return C.c_void_p(buf.ptr.value + offset)
-    try:
+    with _lib.DeviceScope() as dev:
+        d_x, d_y, d_c = dev.upload(x), dev.upload(y), dev.upload(counts)
+        # item-major [B][R][K]: item b is redrawn by a launch of its own, so its streams do not know b
+        d_xe = dev.upload(np.ascontiguousarray(np.broadcast_to(xe[:, None, :], (B, R, K))))
+        d_ye = dev.upload(np.ascontiguousarray(np.broadcast_to(ye[:, None, :], (B, R, K))))
+        d_xr, d_yr = dev.alloc(B * R * K * 8), dev.alloc(B * R * K * 8)
+        d_phase, d_mean, d_std, d_nan = dev.alloc(B * R * 8), dev.alloc(B * 8), dev.alloc(B * 8), dev.alloc(B * 4)
         for b in range(B):
             for src, dst, s in ((d_x, d_xr, seed), (d_y, d_yr, seed_y)):
-                _lib.check(lib.fbx_beta_resample_dev(K, R, at(src, b * K * 8), at(d_c, b * K * 8), float(prior_counts), s,
-                                                     at(dst, b * R * K * 8), None))
+                _lib.check(lib.fbx_beta_resample_dev(K, R, src.at(b * K * 8), d_c.at(b * K * 8), float(prior_counts), s,
+                                                     dst.at(b * R * K * 8), None))
         _lib.check(lib.fbx_rpe_phase_dev(B * R, K, d_xr.ptr, d_yr.ptr, d_xe.ptr, d_ye.ptr, 0, None, None, None, None, 0,
                                          d_phase.ptr, None, None))
         for b in range(B):
-            _lib.check(lib.fbx_circular_stats_dev(R, 1, at(d_phase, b * R * 8), at(d_mean, b * 8), at(d_std, b * 8), at(d_nan, b * 4)))
+            _lib.check(lib.fbx_circular_stats_dev(R, 1, d_phase.at(b * R * 8), d_mean.at(b * 8), d_std.at(b * 8), d_nan.at(b * 4)))
         _lib.synchronize()
         mean, std = d_mean.to_array(np.float64, (B,)), d_std.to_array(np.float64, (B,))
         skipped = d_nan.to_array(np.int32, (B,))
         samples = d_phase.to_array(np.float64, (B, R)) if return_samples else None
-    finally:
-        for buf in bufs:
-            buf.free()
     return (mean, std ** 2, skipped, samples) if return_samples else (mean, std ** 2, skipped)
 
 
@@ -561,7 +552,6 @@ def simulate_and_estimate_rpe_batch(rotations, prep=None, pre_meas=None, init=No
     [B])`` and, with ``true_phases [B]``, the circular distance ``|phase - true|`` in [0, pi] as a third array.  An item that
     cannot be simulated has a NaN phase."""
     from . import _lib
-    import ctypes as C
     if post_select not in (0, 1):
         raise ValueError("post_select must be 0 or 1")
     a = _RpeSimCall(rotations, prep, pre_meas, init, xy_qubit, z_qubit, num_depths, num_shots, multiplicative_factor, additive_error,
@@ -572,32 +562,19 @@ def simulate_and_estimate_rpe_batch(rotations, prep=None, pre_meas=None, init=No
         truth = np.asarray(true_phases, dtype=np.float64)
         if truth.shape != (B,):
             raise ValueError(f"true_phases must be [B] = {(B,)}, not {truth.shape}")
-    lib, DB = _lib.lib(), _lib.DeviceBuffer
-    bufs = []
-
-    def up(arr):
-        if arr is None:
-            return None
-        bufs.append(DB.from_array(arr))
-        return bufs[-1].ptr
-
-    def new(nbytes):
-        bufs.append(DB(max(int(nbytes), 16)))
-        return bufs[-1]
-    try:
-        d_gate, d_prep, d_meas, d_init, d_flips = (up(x) for x in (a.gate, a.prep, a.meas, a.init, a.flips))
-        d_mom, d_phase, d_depth = new(8 * B * K * 8), new(B * 8), new(B * 4)
-        _lib.check(lib.fbx_rpe_simulate_dev(a.n, B, K, d_gate, d_prep, d_meas, a.per_item, d_init, a.xy, a.zq, d_flips,
-                                            _lib.iptr(a.shots), a.seed, a.first_item, None, None, d_mom.ptr, None, None, None))
-        plane = [C.c_void_p(d_mom.ptr.value + i * B * K * 8) for i in range(8)]
+    lib, ptr = _lib.lib(), _lib.devptr
+    with _lib.DeviceScope() as dev:
+        d_gate, d_prep, d_meas, d_init, d_flips = (dev.upload(x) for x in (a.gate, a.prep, a.meas, a.init, a.flips))
+        d_mom, d_phase, d_depth = dev.alloc(8 * B * K * 8), dev.alloc(B * 8), dev.alloc(B * 4)
+        _lib.check(lib.fbx_rpe_simulate_dev(a.n, B, K, ptr(d_gate), ptr(d_prep), ptr(d_meas), a.per_item, ptr(d_init), a.xy, a.zq,
+                                            ptr(d_flips), _lib.iptr(a.shots), a.seed, a.first_item, None, None, d_mom.ptr, None, None,
+                                            None))
+        plane = [d_mom.at(i * B * K * 8) for i in range(8)]
         partner = [plane[i] if a.zq >= 0 else None for i in (2, 3, 6, 7)]
         _lib.check(lib.fbx_rpe_phase_dev(B, K, plane[0], plane[1], plane[4], plane[5], 1, partner[0], partner[1], partner[2],
                                          partner[3], int(post_select), d_phase.ptr, d_depth.ptr, None))
         _lib.synchronize()
         phases, depth = d_phase.to_array(np.float64, (B,)), d_depth.to_array(np.int32, (B,))
-    finally:
-        for buf in bufs:
-            buf.free()
     if truth is None:
         return phases, depth
     delta = np.abs(phases - truth) % (2 * pi)

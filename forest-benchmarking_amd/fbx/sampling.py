@@ -49,6 +49,28 @@ def _raise_poisoned(status, first_item, who="sample_bitstrings_batch"):
                          f"value outside [0, 1] ({bad.size} such item(s) in the batch)")
 
 
+def _sample_bitstrings(wide, probabilities, shots, depolarizing, readout_flip, seed, first_item, return_status):
+    """The body of ``sample_bitstrings_batch`` (``fbx_sample_bitstrings``) and, with ``wide``, of ``sample_bitstrings_wide_batch`` past
+    13 qubits (``fbx_sample_bitstrings_wide``)."""
+    from . import _lib
+    p = np.ascontiguousarray(probabilities, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] < 2 or p.shape[1] & (p.shape[1] - 1):
+        raise ValueError("probabilities must be [B, 2^n] with n >= 1")
+    B, N = p.shape
+    n = N.bit_length() - 1
+    shots, lam, flips, first_item = _noise(B, n, shots, depolarizing, readout_flip, first_item)
+    ok = wide or MIN_WIDTH <= n <= MAX_WIDTH             # (outside, the library refuses before it touches a buffer)
+    bits = np.zeros((B, shots, n) if ok else (0, 0, n), dtype=np.uint8)
+    status = np.zeros(B, dtype=np.int32)
+    entry = _lib.lib().fbx_sample_bitstrings_wide if wide else _lib.lib().fbx_sample_bitstrings
+    _lib.check(entry(n, B, shots, _lib.dptr(p), _lib.dptr(lam), _lib.dptr(flips), _stream_seed(seed), first_item,
+                     bits.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.iptr(status)))
+    if return_status:
+        return bits, status
+    _raise_poisoned(status, first_item, *(("sample_bitstrings_wide_batch",) if wide else ()))
+    return bits
+
+
 def sample_bitstrings_batch(probabilities, shots, depolarizing=None, readout_flip=None, seed=None, first_item=0,
                             return_status=False):
     """``probabilities [B, 2^n]`` (non-negative weights, not necessarily normalised; outcome index i has qubit 0 as its most
@@ -62,22 +84,7 @@ def sample_bitstrings_batch(probabilities, shots, depolarizing=None, readout_fli
     An item that cannot be sampled (a negative or non-finite weight, no positive finite sum, a probability outside [0, 1]) raises
     ``ValueError`` naming the first one; with ``return_status=True`` nothing is raised and ``(bits, status [B] int32)`` comes back,
     status 1 and a record of zeros for such an item, its neighbours untouched."""
-    from . import _lib
-    p = np.ascontiguousarray(probabilities, dtype=np.float64)
-    if p.ndim != 2 or p.shape[1] < 2 or p.shape[1] & (p.shape[1] - 1):
-        raise ValueError("probabilities must be [B, 2^n] with n >= 1")
-    B, N = p.shape
-    n = N.bit_length() - 1
-    shots, lam, flips, first_item = _noise(B, n, shots, depolarizing, readout_flip, first_item)
-    ok = MIN_WIDTH <= n <= MAX_WIDTH                     # (outside, the library refuses before it touches a buffer)
-    bits = np.zeros((B, shots, n) if ok else (0, 0, n), dtype=np.uint8)
-    status = np.zeros(B, dtype=np.int32)
-    _lib.check(_lib.lib().fbx_sample_bitstrings(n, B, shots, _lib.dptr(p), _lib.dptr(lam), _lib.dptr(flips), _stream_seed(seed),
-                                                first_item, bits.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.iptr(status)))
-    if return_status:
-        return bits, status
-    _raise_poisoned(status, first_item)
-    return bits
+    return _sample_bitstrings(False, probabilities, shots, depolarizing, readout_flip, seed, first_item, return_status)
 
 
 def sample_bitstrings_wide_batch(probabilities, shots, depolarizing=None, readout_flip=None, seed=None, first_item=0,
@@ -97,17 +104,7 @@ def sample_bitstrings_wide_batch(probabilities, shots, depolarizing=None, readou
     if n > MAX_WIDE_WIDTH:
         raise _lib.FbxError(_lib.FBX_ERR_UNSUPPORTED, f"sample_bitstrings_wide_batch: width must be {MIN_WIDTH}..{MAX_WIDE_WIDTH} "
                                                       f"(got {n}); there is no host fallback")
-    p = np.ascontiguousarray(p, dtype=np.float64)
-    B = p.shape[0]
-    shots, lam, flips, first_item = _noise(B, n, shots, depolarizing, readout_flip, first_item)
-    bits = np.zeros((B, shots, n), dtype=np.uint8)
-    status = np.zeros(B, dtype=np.int32)
-    _lib.check(_lib.lib().fbx_sample_bitstrings_wide(n, B, shots, _lib.dptr(p), _lib.dptr(lam), _lib.dptr(flips), _stream_seed(seed),
-                                                     first_item, bits.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.iptr(status)))
-    if return_status:
-        return bits, status
-    _raise_poisoned(status, first_item, "sample_bitstrings_wide_batch")
-    return bits
+    return _sample_bitstrings(True, p, shots, depolarizing, readout_flip, seed, first_item, return_status)
 
 
 def sample_clifford_circuit_batch(gates, n_qubits, shots, class_error=None, noise_class=None, readout_flip=None, seed=None,

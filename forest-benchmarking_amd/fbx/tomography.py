@@ -396,6 +396,51 @@ def _grad_cost(A, n, estimate, eps=1e-6):
     return cost_and_gradient_batch(A, np.asarray(n).reshape(1, -1), np.asarray(estimate)[None], eps)[1][0]
 
 
+def _resampled(dev, e, c, R, seed, prior_counts):
+    """Front of every bootstrap chain: upload (expectations, counts) [B, m] and draw ``R`` Beta resamples of each on the device.
+    Returns the buffers of the resampled expectations and counts, [R, B, m] each, owned by the scope ``dev``."""
+    d_e, d_c = dev.upload(e), dev.upload(c)
+    d_er, d_cr = dev.alloc(R * e.size * 8), dev.alloc(R * e.size * 8)
+    _lib.check(_lib.lib().fbx_beta_resample_dev(e.size, R, d_e.ptr, d_c.ptr, float(prior_counts), int(seed) & (2 ** 64 - 1),
+                                                d_er.ptr, d_cr.ptr))
+    return d_er, d_cr
+
+
+def _resampled_pgdb(dev, design, e, c, R, seed, prior_counts, trace_preserving, mode, max_iters):
+    """resample -> PGDB: the buffer of the [R, B, D, D] Choi matrices of the resampled process tomographies."""
+    d_er, d_cr = _resampled(dev, e, c, R, seed, prior_counts)
+    RB, D = R * e.shape[0], design.dim ** 2
+    d_choi = dev.alloc(RB * D * D * 16)
+    _lib.check(_lib.lib().fbx_pgdb_process_dev(design.handle, RB, d_er.ptr, d_cr.ptr, int(bool(trace_preserving)),
+                                               _lib.MODE_FIXED if mode == "fixed" else _lib.MODE_CONVERGE, int(max_iters),
+                                               d_choi.ptr, None, None, None, None, None))
+    return d_choi
+
+
+def _resampled_states(dev, design, e, c, R, seed, estimator, project_to_physical):
+    """resample -> state estimate ("mle": the reference's defaults; "linv") -> optional physical projection: the buffer of the
+    [R, B, d, d] estimates of the resampled state tomographies."""
+    lib = _lib.lib()
+    d_er, d_cr = _resampled(dev, e, c, R, seed, 1.0)
+    RB, d = R * e.shape[0], design.dim
+    d_est = dev.alloc(RB * d * d * 16)
+    if estimator == "mle":
+        _lib.check(lib.fbx_mle_state_dev(design.handle, RB, d_er.ptr, d_cr.ptr, .1, 0.0, 0.0, 1e-9, 10_000, d_est.ptr, None, None))
+    else:
+        _lib.check(lib.fbx_linv_state_dev(design.handle, RB, d_er.ptr, d_est.ptr))
+    if not project_to_physical:
+        return d_est
+    d_phys = dev.alloc(RB * d * d * 16)
+    _lib.check(lib.fbx_proj_state_physical_dev(design.n_qubits, RB, d_est.ptr, d_phys.ptr))
+    return d_phys
+
+
+def _bootstrap_stats(samples, return_samples):
+    """(mean[B], var[B]) over the resamples of ``samples`` [R, B], and the samples themselves on request."""
+    stats = samples.mean(axis=0), samples.var(axis=0)
+    return stats + (samples,) if return_samples else stats
+
+
 def process_fidelity_variance_batch(design: Design, expectations, total_counts, target_ptm,
                                     n_resamples: int = 40, seed: int = 0, prior_counts=1,
                                     trace_preserving=True, mode="converge", max_iters=0,
@@ -410,7 +455,7 @@ def process_fidelity_variance_batch(design: Design, expectations, total_counts, 
     if mode not in ("converge", "fixed"):
         raise ValueError("mode must be 'converge' or 'fixed'")
     e, c = _batch_arrays(design, expectations, total_counts)
-    B, m, n, D = e.shape[0], design.m, design.n_qubits, design.dim ** 2
+    B, n, D = e.shape[0], design.n_qubits, design.dim ** 2
     R = int(n_resamples)
     tgt = np.asarray(target_ptm, dtype=np.complex128)
     if tgt.shape == (D, D):
@@ -419,26 +464,17 @@ def process_fidelity_variance_batch(design: Design, expectations, total_counts, 
         raise ValueError("target_ptm must be [D, D] or [B, D, D]")
     if R < 1 or B == 0:
         raise ValueError("need n_resamples >= 1 and a non-empty batch")
-    lib, DB = _lib.lib(), _lib.DeviceBuffer
-    d_e, d_c = DB.from_array(e), DB.from_array(c)
-    d_er, d_cr = DB(R * B * m * 8), DB(R * B * m * 8)
-    _lib.check(lib.fbx_beta_resample_dev(B * m, R, d_e.ptr, d_c.ptr, float(prior_counts),
-                                         int(seed) & (2 ** 64 - 1), d_er.ptr, d_cr.ptr))
-    d_choi, d_ptm = DB(R * B * D * D * 16), DB(R * B * D * D * 16)
-    _lib.check(lib.fbx_pgdb_process_dev(design.handle, R * B, d_er.ptr, d_cr.ptr, int(bool(trace_preserving)),
-                                        _lib.MODE_FIXED if mode == "fixed" else _lib.MODE_CONVERGE, int(max_iters),
-                                        d_choi.ptr, None, None, None, None, None))
-    _lib.check(lib.fbx_convert_dev(_lib.REP_CHOI, _lib.REP_PAULI_LIOUVILLE, n, R * B, d_choi.ptr, 0, d_ptm.ptr))
-    d_tgt = DB.from_array(np.ascontiguousarray(np.broadcast_to(tgt, (R, B, D, D))))
-    d_f = DB(R * B * 8)
-    _lib.check(lib.fbx_process_fidelity_dev(n, R * B, d_tgt.ptr, d_ptm.ptr, None, d_f.ptr))
-    _lib.synchronize()
-    fid = d_f.to_array(np.float64, (R, B))
-    for buf in (d_e, d_c, d_er, d_cr, d_choi, d_ptm, d_tgt, d_f):
-        buf.free()
-    if return_samples:
-        return fid.mean(axis=0), fid.var(axis=0), fid
-    return fid.mean(axis=0), fid.var(axis=0)
+    lib = _lib.lib()
+    with _lib.DeviceScope() as dev:
+        d_choi = _resampled_pgdb(dev, design, e, c, R, seed, prior_counts, trace_preserving, mode, max_iters)
+        d_ptm = dev.alloc(R * B * D * D * 16)
+        _lib.check(lib.fbx_convert_dev(_lib.REP_CHOI, _lib.REP_PAULI_LIOUVILLE, n, R * B, d_choi.ptr, 0, d_ptm.ptr))
+        d_tgt = dev.upload(np.ascontiguousarray(np.broadcast_to(tgt, (R, B, D, D))))
+        d_f = dev.alloc(R * B * 8)
+        _lib.check(lib.fbx_process_fidelity_dev(n, R * B, d_tgt.ptr, d_ptm.ptr, None, d_f.ptr))
+        _lib.synchronize()
+        fid = d_f.to_array(np.float64, (R, B))
+    return _bootstrap_stats(fid, return_samples)
 
 
 def process_diamond_distance_variance_batch(design: Design, expectations, total_counts, target_choi,
@@ -454,34 +490,23 @@ def process_diamond_distance_variance_batch(design: Design, expectations, total_
     if mode not in ("converge", "fixed"):
         raise ValueError("mode must be 'converge' or 'fixed'")
     e, c = _batch_arrays(design, expectations, total_counts)
-    B, m, n, D = e.shape[0], design.m, design.n_qubits, design.dim ** 2
+    B, n, D = e.shape[0], design.n_qubits, design.dim ** 2
     R = int(n_resamples)
     tgt = np.asarray(target_choi, dtype=np.complex128)
     if tgt.shape not in ((D, D), (B, D, D)):
         raise ValueError("target_choi must be [D, D] or [B, D, D]")
     if R < 1 or B == 0:
         raise ValueError("need n_resamples >= 1 and a non-empty batch")
-    lib, DB = _lib.lib(), _lib.DeviceBuffer
-    d_e, d_c = DB.from_array(e), DB.from_array(c)
-    d_er, d_cr = DB(R * B * m * 8), DB(R * B * m * 8)
-    _lib.check(lib.fbx_beta_resample_dev(B * m, R, d_e.ptr, d_c.ptr, float(prior_counts),
-                                         int(seed) & (2 ** 64 - 1), d_er.ptr, d_cr.ptr))
-    d_choi = DB(R * B * D * D * 16)
-    _lib.check(lib.fbx_pgdb_process_dev(design.handle, R * B, d_er.ptr, d_cr.ptr, int(bool(trace_preserving)),
-                                        _lib.MODE_FIXED if mode == "fixed" else _lib.MODE_CONVERGE, int(max_iters),
-                                        d_choi.ptr, None, None, None, None, None))
-    shared = tgt.ndim == 2
-    d_tgt = DB.from_array(np.ascontiguousarray(tgt if shared else np.broadcast_to(tgt, (R, B, D, D))))
-    d_dist = DB(R * B * 8)
-    _lib.check(lib.fbx_diamond_norm_dev(n, R * B, d_choi.ptr, d_tgt.ptr, int(shared), float(tol), int(diamond_max_iters),
-                                        d_dist.ptr, None, None, None))
-    _lib.synchronize()
-    dist = d_dist.to_array(np.float64, (R, B))
-    for buf in (d_e, d_c, d_er, d_cr, d_choi, d_tgt, d_dist):
-        buf.free()
-    if return_samples:
-        return dist.mean(axis=0), dist.var(axis=0), dist
-    return dist.mean(axis=0), dist.var(axis=0)
+    with _lib.DeviceScope() as dev:
+        d_choi = _resampled_pgdb(dev, design, e, c, R, seed, prior_counts, trace_preserving, mode, max_iters)
+        shared = tgt.ndim == 2
+        d_tgt = dev.upload(np.ascontiguousarray(tgt if shared else np.broadcast_to(tgt, (R, B, D, D))))
+        d_dist = dev.alloc(R * B * 8)
+        _lib.check(_lib.lib().fbx_diamond_norm_dev(n, R * B, d_choi.ptr, d_tgt.ptr, int(shared), float(tol), int(diamond_max_iters),
+                                                   d_dist.ptr, None, None, None))
+        _lib.synchronize()
+        dist = d_dist.to_array(np.float64, (R, B))
+    return _bootstrap_stats(dist, return_samples)
 
 
 def state_chernoff_variance_batch(design: Design, expectations, total_counts, target_state, n_resamples: int = 40,
@@ -497,42 +522,23 @@ def state_chernoff_variance_batch(design: Design, expectations, total_counts, ta
     if estimator not in ("mle", "linv"):
         raise ValueError("estimator must be 'mle' or 'linv'")
     e, c = _batch_arrays(design, expectations, total_counts)
-    B, m, n, d = e.shape[0], design.m, design.n_qubits, design.dim
+    B, n, d = e.shape[0], design.n_qubits, design.dim
     R = int(n_resamples)
     tgt = np.asarray(target_state, dtype=np.complex128)
     if tgt.shape not in ((d, d), (B, d, d)):
         raise ValueError("target_state must be [d, d] or [B, d, d]")
     if R < 1 or B == 0:
         raise ValueError("need n_resamples >= 1 and a non-empty batch")
-    lib, DB = _lib.lib(), _lib.DeviceBuffer
-    d_e, d_c = DB.from_array(e), DB.from_array(c)
-    d_er, d_cr = DB(R * B * m * 8), DB(R * B * m * 8)
-    _lib.check(lib.fbx_beta_resample_dev(B * m, R, d_e.ptr, d_c.ptr, 1.0, int(seed) & (2 ** 64 - 1), d_er.ptr, d_cr.ptr))
-    d_rho = DB(R * B * d * d * 16)
-    if estimator == "mle":
-        _lib.check(lib.fbx_mle_state_dev(design.handle, R * B, d_er.ptr, d_cr.ptr, .1, 0.0, 0.0, 1e-9, 10_000, d_rho.ptr,
-                                         None, None))
-    else:
-        _lib.check(lib.fbx_linv_state_dev(design.handle, R * B, d_er.ptr, d_rho.ptr))
-    bufs = [d_e, d_c, d_er, d_cr, d_rho]
-    if project_to_physical:
-        d_phys = DB(R * B * d * d * 16)
-        _lib.check(lib.fbx_proj_state_physical_dev(n, R * B, d_rho.ptr, d_phys.ptr))
-        bufs.append(d_phys)
-        d_rho = d_phys
-    shared = tgt.ndim == 2
-    d_tgt = DB.from_array(np.ascontiguousarray(tgt if shared else np.broadcast_to(tgt, (R, B, d, d))))
-    d_q = DB(R * B * 8)
-    bufs += [d_tgt, d_q]
-    _lib.check(lib.fbx_chernoff_bound_dev(n, R * B, d_rho.ptr, d_tgt.ptr, int(shared), float(tol), 100, 1e-12, d_q.ptr,
-                                          None, None, None))
-    _lib.synchronize()
-    q = d_q.to_array(np.float64, (R, B))
-    for buf in bufs:
-        buf.free()
-    if return_samples:
-        return q.mean(axis=0), q.var(axis=0), q
-    return q.mean(axis=0), q.var(axis=0)
+    with _lib.DeviceScope() as dev:
+        d_rho = _resampled_states(dev, design, e, c, R, seed, estimator, project_to_physical)
+        shared = tgt.ndim == 2
+        d_tgt = dev.upload(np.ascontiguousarray(tgt if shared else np.broadcast_to(tgt, (R, B, d, d))))
+        d_q = dev.alloc(R * B * 8)
+        _lib.check(_lib.lib().fbx_chernoff_bound_dev(n, R * B, d_rho.ptr, d_tgt.ptr, int(shared), float(tol), 100, 1e-12, d_q.ptr,
+                                                     None, None, None))
+        _lib.synchronize()
+        q = d_q.to_array(np.float64, (R, B))
+    return _bootstrap_stats(q, return_samples)
 
 
 _STATE_MEASURES = ("purity", "fidelity", "infidelity", "trace_distance", "hs_ip")
@@ -565,46 +571,21 @@ def state_measure_variance_batch(design: Design, expectations, total_counts, tar
         if tgt.ndim not in (2, 3) or tgt.shape[-2:] != (d, d):
             raise ValueError("target_state must be [d, d] or [B, d, d]")
     e, c = _batch_arrays(design, expectations, total_counts)
-    B, m, n = e.shape[0], design.m, design.n_qubits
+    B, n = e.shape[0], design.n_qubits
     if B == 0:
         raise ValueError("need a non-empty batch")
     if tgt is not None and tgt.ndim == 3 and tgt.shape[0] != B:
         raise ValueError("target_state must be [d, d] or [B, d, d]")
-    lib, DB = _lib.lib(), _lib.DeviceBuffer
-    d_e, d_c = DB.from_array(e), DB.from_array(c)
-    d_er, d_cr = DB(R * B * m * 8), DB(R * B * m * 8)
-    _lib.check(lib.fbx_beta_resample_dev(B * m, R, d_e.ptr, d_c.ptr, 1.0, int(seed) & (2 ** 64 - 1), d_er.ptr, d_cr.ptr))
-    d_est = DB(R * B * d * d * 16)
-    if estimator == "mle":
-        _lib.check(lib.fbx_mle_state_dev(design.handle, R * B, d_er.ptr, d_cr.ptr, .1, 0.0, 0.0, 1e-9, 10_000, d_est.ptr,
-                                         None, None))
-    else:
-        _lib.check(lib.fbx_linv_state_dev(design.handle, R * B, d_er.ptr, d_est.ptr))
-    bufs = [d_e, d_c, d_er, d_cr, d_est]
-    if project_to_physical:
-        d_phys = DB(R * B * d * d * 16)
-        _lib.check(lib.fbx_proj_state_physical_dev(n, R * B, d_est.ptr, d_phys.ptr))
-        bufs.append(d_phys)
-        d_est = d_phys
-    d_v = DB(R * B * 8)
-    bufs.append(d_v)
-    key = "fidelity" if measure == "infidelity" else measure
-    if tgt is None:
-        d_rho = d_est
-    else:
-        d_rho = DB.from_array(np.ascontiguousarray(np.broadcast_to(tgt, (R, B, d, d))))
-        bufs.append(d_rho)
-    outs = [d_v.ptr if k == key else None for k in ("purity", "fidelity", "trace_distance", "hs_ip")]
-    _lib.check(lib.fbx_state_measures_dev(n, R * B, d_rho.ptr, d_est.ptr, *outs))
-    _lib.synchronize()
-    v = d_v.to_array(np.float64, (R, B))
-    for buf in bufs:
-        buf.free()
-    if measure == "infidelity":
-        v = 1 - v
-    if return_samples:
-        return v.mean(axis=0), v.var(axis=0), v
-    return v.mean(axis=0), v.var(axis=0)
+    with _lib.DeviceScope() as dev:
+        d_est = _resampled_states(dev, design, e, c, R, seed, estimator, project_to_physical)
+        d_v = dev.alloc(R * B * 8)
+        key = "fidelity" if measure == "infidelity" else measure
+        d_rho = d_est if tgt is None else dev.upload(np.ascontiguousarray(np.broadcast_to(tgt, (R, B, d, d))))
+        outs = [d_v.ptr if k == key else None for k in ("purity", "fidelity", "trace_distance", "hs_ip")]
+        _lib.check(_lib.lib().fbx_state_measures_dev(n, R * B, d_rho.ptr, d_est.ptr, *outs))
+        _lib.synchronize()
+        v = d_v.to_array(np.float64, (R, B))
+    return _bootstrap_stats(1 - v if measure == "infidelity" else v, return_samples)
 
 
 def estimate_by_qubit_groups(results, qubit_groups, kind="process", estimator="pgdb", **kwargs):
@@ -1079,7 +1060,7 @@ def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pa
     shots, flips, seed, first_item = _sim_noise(B, n, shots, readout_flip, seed, first_item)
     if B == 0:
         raise ValueError("need a non-empty batch")
-    lib, DB = _lib.lib(), _lib.DeviceBuffer
+    lib = _lib.lib()
     if confusion is not None:
         if flips is not None:
             raise ValueError("give the readout error as confusion (readout.confusion_from_flips) or as readout_flip, not both")
@@ -1090,22 +1071,19 @@ def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pa
             cal_paulis, cal_index = calibration_list(design)
             n_cal = cal_paulis.shape[0]
             flat_index = _flat_cal_index(cal_index, B, n_cal)
-    d_truth, d_truth_c = DB.from_array(truth), DB.from_array(truth.astype(np.complex128))
-    d_flips = DB.from_array(flips) if flips is not None else None
-    d_e, d_c, d_status = DB(B * m * 8), DB(B * m * 8), DB(B * 4)
-    d_choi, d_ptm, d_f = DB(B * D * D * 16), DB(B * D * D * 16), DB(B * 8)
-    bufs = [b for b in (d_truth, d_truth_c, d_flips, d_e, d_c, d_status, d_choi, d_ptm, d_f) if b is not None]
-    try:
+    with _lib.DeviceScope() as dev:
+        d_truth, d_truth_c = dev.upload(truth), dev.upload(truth.astype(np.complex128))
+        d_flips = dev.upload(flips)
+        d_e, d_c, d_status = dev.alloc(B * m * 8), dev.alloc(B * m * 8), dev.alloc(B * 4)
+        d_choi, d_ptm, d_f = dev.alloc(B * D * D * 16), dev.alloc(B * D * D * 16), dev.alloc(B * 8)
         if confusion is not None:
-            d_conf, d_se = DB.from_array(conf), DB(B * m * 8)
-            bufs += [d_conf, d_se]
+            d_conf, d_se = dev.upload(conf), dev.alloc(B * m * 8)
             _lib.check(lib.fbx_tomo_simulate_symmetrized_dev(design.handle, grouping.handle, B, d_truth.ptr, d_conf.ptr, symm_type,
                                                              shots, seed, first_item, d_e.ptr, d_c.ptr, d_se.ptr, None, None, None,
                                                              d_status.ptr))
             if calibrate:
-                d_cm, d_cv, d_ci = DB(B * n_cal * 8), DB(B * n_cal * 8), DB.from_array(flat_index)
-                d_e2, d_se2, d_cst = DB(B * m * 8), DB(B * m * 8), DB(B * 4)
-                bufs += [d_cm, d_cv, d_ci, d_e2, d_se2, d_cst]
+                d_cm, d_cv, d_ci = dev.alloc(B * n_cal * 8), dev.alloc(B * n_cal * 8), dev.upload(flat_index)
+                d_e2, d_se2, d_cst = dev.alloc(B * m * 8), dev.alloc(B * m * 8), dev.alloc(B * 4)
                 _lib.check(lib.fbx_tomo_simulate_calibration_dev(design.handle, B, d_conf.ptr, symm_type, cal_shots, seed, first_item,
                                                                  d_cm.ptr, d_cv.ptr, None, None, d_cst.ptr))
                 # every (item, setting) has the calibration of its item: one "experiment" of B m settings and B n_cal calibrations
@@ -1113,11 +1091,11 @@ def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pa
                                                               d_e2.ptr, d_se2.ptr))
                 d_e = d_e2
         elif grouping is None:
-            _lib.check(lib.fbx_tomo_simulate_dev(design.handle, B, d_truth.ptr, shots, d_flips.ptr if d_flips else None, seed,
+            _lib.check(lib.fbx_tomo_simulate_dev(design.handle, B, d_truth.ptr, shots, _lib.devptr(d_flips), seed,
                                                  first_item, d_e.ptr, d_c.ptr, None, None, d_status.ptr))
         else:
             _lib.check(lib.fbx_tomo_simulate_grouped_dev(design.handle, grouping.handle, B, d_truth.ptr, shots,
-                                                         d_flips.ptr if d_flips else None, seed, first_item, d_e.ptr, d_c.ptr,
+                                                         _lib.devptr(d_flips), seed, first_item, d_e.ptr, d_c.ptr,
                                                          None, None, None, None, d_status.ptr))
         if estimator == "pgdb":
             _lib.check(lib.fbx_pgdb_process_dev(design.handle, B, d_e.ptr, d_c.ptr,
@@ -1134,9 +1112,6 @@ def simulate_and_estimate_process_batch(design: Design, channels, shots, rep="pa
             status |= d_cst.to_array(np.int32, (B,))
         choi = d_choi.to_array(np.complex128, (B, D, D))
         fid = d_f.to_array(np.float64, (B,))
-    finally:
-        for buf in bufs:
-            buf.free()
     bad = np.flatnonzero(status)
     if bad.size:
         raise ValueError(f"simulate_and_estimate_process_batch: item {int(bad[0])} cannot be simulated: a truth entry that is not "

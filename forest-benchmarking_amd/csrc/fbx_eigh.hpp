@@ -237,6 +237,26 @@ __device__ __forceinline__ JRot jacobi_rotation_beta(double a, double d, double 
     r.c = x * ic; r.sr = f * br; r.si = f * bi; r.an = a + u; r.dn = d - u;
     return r;
 }
+// The same rotation in two steps, for a caller that issues them apart (JacobiWave<16, true>: the exchange of c and s starts
+// before the diagonal's shift u is formed).  Every value is the result of the operation that produces it in
+// jacobi_rotation_beta, on the same operands: c, s, a + u, d - u are the same bits.
+struct JRotCS { double c, sr, si, f, fb, delta; };
+__device__ __forceinline__ JRotCS jacobi_rotation_cs(double a, double d, double br, double bi) {
+    const double beta = fma(br, br, bi * bi);
+    const double delta = 0.5 * (d - a);
+    const double ad = fabs(delta) + 1e-150;
+    const double h2 = fma(ad, ad, beta);
+    const double ih = fast_rsqrt(h2);
+    const double x = fma(0.5 * ad, ih, 0.5);
+    const double ic = fast_rsqrt(x);
+    const double f = (delta >= 0.0 ? 0.5 : -0.5) * ih * ic;
+    JRotCS r;
+    r.c = x * ic; r.sr = f * br; r.si = f * bi; r.f = f; r.fb = f * beta; r.delta = delta;
+    return r;
+}
+__device__ __forceinline__ double jacobi_rotation_u(const JRotCS& r) {
+    return fma(r.f * r.fb, 2.0 * r.delta, -2.0 * r.c * r.fb);
+}
 
 // 2x2 block update  m <- R_I^H m R_J  and eigenvector columns  v <- v R_J
 __device__ __forceinline__ void jacobi_apply_m(double cI, double sIr, double sIi, double cJ, double sJr,
@@ -287,7 +307,8 @@ struct __attribute__((aligned(16))) JRec { double c, sr, si, an, dn, pad; };
 // Every lane derives the two rotations it needs from the pivot blocks in LDS.
 // Single-wavefront version with the eigenvector update software-pipelined one round behind the
 // matrix update: v <- v R_J of round r does not feed the next pivots, so it is issued inside the
-// dependent rsqrt chain of round r + 1, where the wave would otherwise idle.  LDS instructions of
+// dependent rsqrt chain of round r + 1, where the wave would otherwise idle (the full-block form; the
+// two-worker form issues it behind the next round's loads, see there).  LDS instructions of
 // one wavefront execute in program order, so no barrier or wait separates the rounds.
 //
 // Round 5: the EIGENVECTOR block never touches LDS inside the sweeps.  The tournament permutation only moves eigenvector
@@ -322,6 +343,18 @@ template <int N, bool TWO_WORKERS = false> struct JacobiWave;
 // LDS-array cycles per round for the two stores / four loads instead of the 60 / 45 the mirrored seats cost in the plane layout built
 // for full blocks, i.e. the 49.8 % bank conflicts of profiles/r05 gone -- changes nothing in isolation (940 vs 941 cycles per round:
 // the conflicts are not on the dependent chain) and costs the kernel its table look-ups: B = 1024 fixed-100 12.17 -> 12.52 ms.)
+// Round 10: THE ROUND IS SCHEDULED BY HAND around its dependent chain  load pivots -> rotation -> ds_bpermute -> block update ->
+// store -> next round's load.  Left to the scheduler, the eigenvector update of the round before (24 fp64, 16 DPP moves, ~28
+// selects: none of it feeds the stores or the next pivots) stood on that chain -- FMAs in front of the round's loads, DPP moves and
+// selects in front of the stores, the diagonal lanes' an / dn in a branch of their own before the stores.  Now (a) a round's seven
+// loads are issued right behind the two stores of the round before and held there by a sched_barrier (the first round's before the
+// first sweep; the convergence test of a sweep reads those registers instead of loading again); (b) the eigenvector update of a
+// round follows these loads, inside their LDS round trip, in the same round -- no rotation is kept pending across rounds, no flush;
+// (c) the exchange of c and s is issued before the diagonal's shift u is formed (jacobi_rotation_cs / _u, a second sched_barrier);
+// (d) the diagonal lanes take an / dn by selects, so the round is one basic block; (e) between the block update's last FMA and the
+// stores stand only the selects and sign flips of the stored values.  The same operations on the same operands: results are
+// bit-identical (tests/test_pgdb_onewave_bits_gpu.py).  B = 1024 fixed-100: 11.35 -> 11.06 ms (profiles/r10/jacobi_round_step_ab.txt;
+// measured and dropped there: column moves deferred into the next rotation, the row shift folded into the select).
 template <int N>
 struct JacobiWave<N, true> {
 static __device__ int run(cplx* __restrict__ Ms, cplx* __restrict__ Vs, int lane, bool init_identity,
@@ -387,16 +420,20 @@ static __device__ int run(cplx* __restrict__ Ms, cplx* __restrict__ Vs, int lane
     };
     if (lane == 0) { cplx z; z.re = 0.0; z.im = 0.0; Ms[ZERO] = z; }
     FBX_WAVE_SYNC();
-    int ra0 = rd_true[0], ra1 = rd_true[1], ra2 = rd_true[2], ra3 = rd_true[3];
-    double pc = 1.0, psr = 0.0, psi = 0.0;
-    bool pending = false;
+    // operands of the coming round: the pivot of pair pl and the block
+    double aP, dP_; cplx bP, x0, x1, y0, y1;
+    auto load_round = [&](const int (&rd)[4]) __attribute__((always_inline)) {
+        aP = Ms[0 * PS + dP].re; dP_ = Ms[3 * PS + dP].re; bP = Ms[1 * PS + dP];
+        x0 = Ms[rd[0]]; x1 = Ms[rd[1]]; y0 = Ms[rd[2]]; y1 = Ms[rd[3]];
+        __builtin_amdgcn_sched_barrier(0);                     // the seven loads issue here, in front of everything that follows
+    };
+    load_round(rd_true);
     int sweep = 0;
     double n2 = 0.0;
     for (; sweep < FBX_JACOBI_MAX_SWEEPS; ++sweep) {
         {
-            const cplx x0 = Ms[ra0], y0 = Ms[ra2], x1 = Ms[ra1];
             double o2, dg = 0.0;
-            if (diag) { o2 = x1.re * x1.re + x1.im * x1.im; dg = x0.re * x0.re + Ms[3 * PS + dP].re * Ms[3 * PS + dP].re; }   // (0,1) entry; a, d
+            if (diag) { o2 = x1.re * x1.re + x1.im * x1.im; dg = x0.re * x0.re + dP_ * dP_; }   // (0,1) entry; a, d
             else o2 = (x0.re * x0.re + x0.im * x0.im) + (y0.re * y0.re + y0.im * y0.im);
             o2 = 2.0 * uniform(wave_sum(o2));
             if (sweep == 0) n2 = o2 + uniform(wave_sum(dg));
@@ -404,16 +441,11 @@ static __device__ int run(cplx* __restrict__ Ms, cplx* __restrict__ Vs, int lane
             if (!(o2 > tol2 * n2)) break;
         }
         for (int r = 0; r < N - 1; ++r) {
-            const double aP = Ms[0 * PS + dP].re, dP_ = Ms[3 * PS + dP].re;
-            const cplx bP = Ms[1 * PS + dP];
-            const cplx x0 = Ms[ra0], x1 = Ms[ra1], y0 = Ms[ra2], y1 = Ms[ra3];
-            ra0 = rd_zs[0]; ra1 = rd_zs[1]; ra2 = rd_zs[2]; ra3 = rd_zs[3];
-            if (pending) {
-                jacobi_apply_v(pc, psr, psi, v0p, v0q, v1p, v1q);
-                permute(v0p.re, v0q.re); permute(v0p.im, v0q.im); permute(v1p.re, v1q.re); permute(v1p.im, v1q.im);
-            }
-            const JRot rL = jacobi_rotation(aP, dP_, bP.re, bP.im);               // pair pl
+            // the chain: pivots -> rotation -> exchange -> block update -> stores; only the chain is in this region
+            const JRotCS rL = jacobi_rotation_cs(aP, dP_, bP.re, bP.im);          // pair pl
             const double fc = __shfl(rL.c, src_lane), fsr = __shfl(rL.sr, src_lane), fsi = __shfl(rL.si, src_lane);   // pair pf
+            __builtin_amdgcn_sched_barrier(0);                 // the exchange is under way before anything below issues
+            const double u = jacobi_rotation_u(rL), an = aP + u, dn = dP_ - u;    // the rotated diagonal (the diagonal lanes' result)
             // column rotation = pair J (the locally computed one), row rotation = pair I (the fetched one)
             const double cJ = rL.c, sJr = flip(rL.sr, smask), sJi = rL.si;
             cplx t0, t1, n0, n1;
@@ -425,18 +457,20 @@ static __device__ int run(cplx* __restrict__ Ms, cplx* __restrict__ Vs, int lane
             n0.im = fc * t0.im - (fsr * t1.im + fsi * t1.re);
             n1.re = fc * t1.re + (fsr * t0.re + fsi * t0.im);
             n1.im = fc * t1.im + (fsr * t0.im - fsi * t0.re);
-            if (diag) { n0.re = rL.an; n0.im = 0.0; n1.re = rL.dn; n1.im = 0.0; }
+            // the diagonal lanes place the rotated diagonal: selects, not a branch, so that the round stays one scheduling region
+            n0.re = diag ? an : n0.re; n0.im = diag ? 0.0 : n0.im;
+            n1.re = diag ? dn : n1.re; n1.im = diag ? 0.0 : n1.im;
             n0.im = flip(n0.im, cmask[0]); n1.im = flip(n1.im, cmask[1]);
             Ms[wr[0]] = n0; Ms[wr[1]] = n1;
-            // the eigenvector block rotates with its own column pair Jc: the local rotation, for the second worker the fetched one
-            pc = wb ? fc : rL.c; psr = wb ? fsr : rL.sr; psi = wb ? fsi : rL.si; pending = true;
+            load_round(rd_zs);                                 // the next round's operands, right behind the stores they wait for
+            // off the chain, inside the LDS round trip of those loads: the eigenvector block rotates with its own column pair Jc
+            // -- the local rotation, for the second worker the fetched one -- and its columns move to their next seats
+            const double pc = wb ? fc : rL.c, psr = wb ? fsr : rL.sr, psi = wb ? fsi : rL.si;
+            jacobi_apply_v(pc, psr, psi, v0p, v0q, v1p, v1q);
+            permute(v0p.re, v0q.re); permute(v0p.im, v0q.im); permute(v1p.re, v1q.re); permute(v1p.im, v1q.im);
         }
     }
-    if (pending) {
-        jacobi_apply_v(pc, psr, psi, v0p, v0q, v1p, v1q);
-        permute(v0p.re, v0q.re); permute(v0p.im, v0q.im); permute(v1p.re, v1q.re); permute(v1p.im, v1q.im);
-    }
-    if (init_identity || pending) { Vs[0 * PS + me] = v0p; Vs[1 * PS + me] = v0q; Vs[2 * PS + me] = v1p; Vs[3 * PS + me] = v1q; }
+    if (init_identity || sweep > 0) { Vs[0 * PS + me] = v0p; Vs[1 * PS + me] = v0q; Vs[2 * PS + me] = v1p; Vs[3 * PS + me] = v1q; }
     FBX_WAVE_SYNC();
     return sweep;
 }

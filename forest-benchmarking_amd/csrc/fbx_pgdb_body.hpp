@@ -6,6 +6,7 @@
 #pragma once
 #include "fbx_choi.hpp"
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 #define FBX_LEAN_MIN_BATCH 1025     // batch size from which the two-waves-per-SIMD kernel is used (2 qubits): one reconstruction more than
                                     // the chip has SIMDs.  The one-wave kernel is the faster chain (1024 items: 12.7 against 15.3 ms), but item
@@ -234,6 +235,18 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
     // s_set_gpr_idx): unrolled they are 6.4 KB of code per slot -- 58 of the 91 KB of the 540-setting instantiation, against a
     // 64 KB instruction cache that eight wavefronts in eight different phases share.
     constexpr int SLOT_UNROLL = LEAN ? 1 : MAXJ;
+    // One-wave kernels of up to nine slots (SLOT_BATCH): a slot pass is ONE scheduling region -- no branch per slot.  The operands of TRIP slots (table entries, counts,
+    // coefficients) are requested together in front of the first use and held there by a scheduling barrier, so that a pass pays one
+    // LDS round trip, not one per slot, and the dependent chains of different slots (the two divisions, the two logarithms of a slot)
+    // interleave.  Lanes without an outcome in a slot run the same instructions on harmless operands (design word 0, counts 0.0,
+    // pe = 1, pu = 0) and keep their results by SELECTS: a guarded `acc -= x` became `acc = valid ? acc - x : acc`, so a valid lane
+    // sees the operations it saw before and an invalid one sees none -- same bits (tests/test_pgdb_onewave_*_gpu.py).  Up to nine
+    // slots are one trip.  The sixteen-slot instantiation keeps the slot-by-slot passes: as one region they cost it 400 instead of
+    // 156 B of scratch, and still 216 B in trips of two slots (profiles/r11/step_ab.txt).
+    constexpr bool SLOT_BATCH = !LEAN && MAXJ <= 9;
+    constexpr int TRIP = SLOT_BATCH ? MAXJ : 1;
+    typedef std::integral_constant<bool, true> UnitCoefs;
+    typedef std::integral_constant<bool, false> AnyCoefs;
     // states per trip of the table products (predict_table): three in the one-wave kernel -- the 36-state design is three trips per
     // lane, the 16-state one a trip and a single state; the two-waves kernel has no registers for more than one
     constexpr int TABLE_U = LEAN ? 1 : 3;
@@ -377,8 +390,40 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
     }
     // (every slot is assigned -- `missing` for lanes without an outcome -- so that the arrays are dead
     // between two calls and do not occupy registers across the projection)
+    // SLOT_BATCH: the table entries (and, where the design has them, the coefficients) of TRIP slots per round trip, the
+    // wave-uniform `unit_coefs` decided once per pass (two instantiations), `g < m` a select -- table_probs() slot by slot was nine
+    // exposed round trips and eighteen branches per call.  Lanes without a setting read entry [0][0] and coefficient 0.
+    auto slot_valid = [&](int j) __attribute__((always_inline)) -> bool { return lane + 64 * j < m; };
+    auto probs_pass = [&](auto unit, const double* T, double* pp, double* pm, double missing) __attribute__((always_inline)) {
+        constexpr bool UNIT = decltype(unit)::value;
+#pragma unroll
+        for (int j0 = 0; j0 < MAXJ; j0 += TRIP) {
+            double cf[TRIP], tr[TRIP], ex[TRIP];
+            if constexpr (!UNIT) {
+#pragma unroll
+                for (int u = 0; u < TRIP; ++u) { const int g = lane + 64 * (j0 + u); cf[u] = des.coef[g < m ? g : 0]; }
+            }
+#pragma unroll
+            for (int u = 0; u < TRIP; ++u) {
+                const uint32_t dw = spw[j0 + u];
+                const int s = dw >> 16, p = dw & 0xffff;
+                tr[u] = T[s * D]; ex[u] = T[s * D + p];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < TRIP; ++u) {
+                double exc;
+                if constexpr (UNIT) exc = ex[u]; else exc = cf[u] * ex[u];
+                const double a = (tr[u] + exc) * half_dd, b = (tr[u] - exc) * half_dd;
+                const bool valid = slot_valid(j0 + u);
+                pp[j0 + u] = valid ? a : missing; pm[j0 + u] = valid ? b : missing;
+            }
+        }
+    };
     auto load_probs = [&](const double* T, double* pp, double* pm, double missing) __attribute__((always_inline)) {
-        if constexpr (!LEAN) {
+        if constexpr (SLOT_BATCH) {
+            if (unit_coefs) probs_pass(UnitCoefs(), T, pp, pm, missing); else probs_pass(AnyCoefs(), T, pp, pm, missing);
+        } else if constexpr (!LEAN) {
 #pragma unroll
             for (int j = 0; j < MAXJ; ++j) table_probs(T, j, missing, pp[j], pm[j]);
         }
@@ -392,6 +437,25 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
     // negative log-likelihood at est + alpha * update (tomography.py:597-614)
     auto cost_at = [&](double alpha) __attribute__((always_inline)) -> double {
         double acc = 0.0;
+        if constexpr (SLOT_BATCH) {      // the counts of TRIP slots in one round trip; the logarithms of its slots interleave
+#pragma unroll
+            for (int j0 = 0; j0 < MAXJ; j0 += TRIP) {
+                double np_[TRIP], nm_[TRIP];
+#pragma unroll
+                for (int u = 0; u < TRIP; ++u) counts_of(j0 + u, np_[u], nm_[u]);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < TRIP; ++u) {
+                    const int j = j0 + u;
+                    double pp = fma(alpha, pup[j], pep[j]), pm = fma(alpha, pum[j], pem[j]);
+                    pp = pp < PGDB_EPS ? PGDB_EPS : pp;
+                    pm = pm < PGDB_EPS ? PGDB_EPS : pm;
+                    const double next = acc - (np_[u] * fast_log_pos(pp) + nm_[u] * fast_log_pos(pm));
+                    acc = slot_valid(j) ? next : acc;
+                }
+            }
+            return uniform(wave_sum(acc));
+        }
 #pragma unroll SLOT_UNROLL
         for (int j = 0; j < (STREAM ? nslots : MAXJ); ++j) {
             const int g = lane + 64 * j;
@@ -484,22 +548,64 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
         double* Wt = L.Tupd;                        // [S][D]
         for (int idx = lane; idx < D * S; idx += 64) Wt[idx] = 0.0;
         FBX_WAVE_SYNC();
+        // SLOT_BATCH: the counts (and coefficients) of TRIP slots in one round trip, all their weights computed in one region --
+        // the 2 TRIP division chains interleave -- and then the additions, slot ascending, trace weight first as before, under the
+        // lane mask of `g < m` alone.  (pin: the weights stay in front of the masked blocks instead of sinking into them.)
+        auto pin = [](double& v) __attribute__((always_inline)) { __asm__ volatile("" : "+v"(v)); };
+        auto weights_pass = [&](auto unit) __attribute__((always_inline)) {
+            constexpr bool UNIT = decltype(unit)::value;
+#pragma unroll
+            for (int j0 = 0; j0 < MAXJ; j0 += TRIP) {
+                double np_[TRIP], nm_[TRIP], cf[TRIP], w0[TRIP], w1[TRIP];
+#pragma unroll
+                for (int u = 0; u < TRIP; ++u) counts_of(j0 + u, np_[u], nm_[u]);
+                if constexpr (!UNIT) {
+#pragma unroll
+                    for (int u = 0; u < TRIP; ++u) { const int g = lane + 64 * (j0 + u); cf[u] = des.coef[g < m ? g : 0]; }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < TRIP; ++u) {
+                    const int j = j0 + u;
+                    const double pp = pep[j] < PGDB_EPS ? PGDB_EPS : pep[j];
+                    const double pm = pem[j] < PGDB_EPS ? PGDB_EPS : pem[j];
+                    const double ep = np_[u] / pp, em = nm_[u] / pm;
+                    w0[u] = 0.5 * (ep + em);
+                    if constexpr (UNIT) w1[u] = 0.5 * (ep - em); else w1[u] = cf[u] * 0.5 * (ep - em);
+                }
+#pragma unroll
+                for (int u = 0; u < TRIP; ++u) { pin(w0[u]); pin(w1[u]); }
+#pragma unroll
+                for (int u = 0; u < TRIP; ++u) {
+                    if (__builtin_expect(slot_valid(j0 + u), 1)) {       // (likely: the additions stay in line)
+                        const uint32_t dw = spw[j0 + u];
+                        const int st = dw >> 16, p = dw & 0xffff;
+                        atomicAdd(&Wt[st * D], w0[u]);
+                        atomicAdd(&Wt[st * D + p], w1[u]);
+                    }
+                }
+            }
+        };
+        if constexpr (SLOT_BATCH) {
+            if (unit_coefs) weights_pass(UnitCoefs()); else weights_pass(AnyCoefs());
+        } else {
 #pragma unroll SLOT_UNROLL
-        for (int j = 0; j < (STREAM ? nslots : MAXJ); ++j) {
-            const int g = lane + 64 * j;
-            if (g < m) {
-                double ep_, em_;
-                pe_of(j, ep_, em_);
-                const double pp = ep_ < PGDB_EPS ? PGDB_EPS : ep_;
-                const double pm = em_ < PGDB_EPS ? PGDB_EPS : em_;
-                double np_, nm_;
-                counts_of(j, np_, nm_);
-                const double ep = np_ / pp, em = nm_ / pm;
-                const double cf = unit_coefs ? 1.0 : des.coef[g];
-                const uint32_t dw = spw_of(j);
-                const int st = dw >> 16, p = dw & 0xffff;
-                atomicAdd(&Wt[st * D], 0.5 * (ep + em));
-                atomicAdd(&Wt[st * D + p], cf * 0.5 * (ep - em));
+            for (int j = 0; j < (STREAM ? nslots : MAXJ); ++j) {
+                const int g = lane + 64 * j;
+                if (g < m) {
+                    double ep_, em_;
+                    pe_of(j, ep_, em_);
+                    const double pp = ep_ < PGDB_EPS ? PGDB_EPS : ep_;
+                    const double pm = em_ < PGDB_EPS ? PGDB_EPS : em_;
+                    double np_, nm_;
+                    counts_of(j, np_, nm_);
+                    const double ep = np_ / pp, em = nm_ / pm;
+                    const double cf = unit_coefs ? 1.0 : des.coef[g];
+                    const uint32_t dw = spw_of(j);
+                    const int st = dw >> 16, p = dw & 0xffff;
+                    atomicAdd(&Wt[st * D], 0.5 * (ep + em));
+                    atomicAdd(&Wt[st * D + p], cf * 0.5 * (ep - em));
+                }
             }
         }
         FBX_WAVE_SYNC();
@@ -682,10 +788,18 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
             if (!have_sums) {
 #pragma unroll
                 for (int k = 0; k < NS; ++k) Sk[k] = 0.0;
+                double cnp[SLOT_BATCH ? MJ : 1], cnm[SLOT_BATCH ? MJ : 1];      // (SLOT_BATCH) the counts of TRIP slots in one round trip
 #pragma unroll SLOT_UNROLL
                 for (int j = 0; j < (STREAM ? nslots : MAXJ); ++j) {
                     double np_, nm_, ep_, em_, up_, um_;
-                    counts_of(j, np_, nm_);
+                    if constexpr (SLOT_BATCH) {
+                        if (j % TRIP == 0) {
+#pragma unroll
+                            for (int u = 0; u < TRIP; ++u) counts_of(j + u, cnp[j + u], cnm[j + u]);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        np_ = cnp[j]; nm_ = cnm[j];
+                    } else counts_of(j, np_, nm_);
                     pe_of(j, ep_, em_); pu_of(j, up_, um_);
 #pragma unroll
                     for (int sg = 0; sg < 2; ++sg) {

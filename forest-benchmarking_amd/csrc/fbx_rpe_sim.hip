@@ -43,45 +43,6 @@ struct RpeSimIn {
 };
 struct RpeSimSchedule { int32_t n[RPES_MAX_DEPTHS]; };
 
-__device__ __forceinline__ bool rpes_finite(double v) { return fabs(v) < __builtin_inf(); }              // false for NaN
-__device__ __forceinline__ bool rpes_bad_total(double c) { return !(c > 0.0 && c < __builtin_inf()); }   // NaN included
-
-// The outcome distribution of one basis at one depth from four components of the final Pauli vector: vI the identity (1 for a
-// trace-preserving map), vP = <P_a>, vZ = <Z_b>, vPZ = <P_a Z_b>.  Outcome o = 2 s + t with a partner, o = s without.  fa / fb:
-// the flips of the xy qubit / the partner, or NULL.  Returns the clamped sum.
-template <bool PARTNER>
-__device__ __forceinline__ double rpes_distribution(double vI, double vP, double vZ, double vPZ, const double* __restrict__ fa,
-                                                    const double* __restrict__ fb, double (&p)[4]) {
-    if constexpr (PARTNER) {
-        const double a = vI + vP, b = vI - vP;
-        p[0] = ((a + vZ) + vPZ) * 0.25; p[1] = ((a - vZ) - vPZ) * 0.25;
-        p[2] = ((b + vZ) - vPZ) * 0.25; p[3] = ((b - vZ) + vPZ) * 0.25;
-        if (fa) {
-            const double f0 = fa[0], f1 = fa[1], g0 = fb[0], g1 = fb[1];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {                     // the bit s: pairs (t, 2 + t)
-                const double x = p[t], y = p[2 + t];
-                p[t] = fma(1.0 - f0, x, f1 * y); p[2 + t] = fma(1.0 - f1, y, f0 * x);
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {                     // the bit t: pairs (2 s, 2 s + 1)
-                const double x = p[2 * s], y = p[2 * s + 1];
-                p[2 * s] = fma(1.0 - g0, x, g1 * y); p[2 * s + 1] = fma(1.0 - g1, y, g0 * x);
-            }
-        }
-    } else {
-        p[0] = (vI + vP) * 0.5; p[1] = (vI - vP) * 0.5; p[2] = 0.0; p[3] = 0.0;
-        if (fa) {
-            const double f0 = fa[0], f1 = fa[1], x = p[0], y = p[1];
-            p[0] = fma(1.0 - f0, x, f1 * y); p[1] = fma(1.0 - f1, y, f0 * x);
-        }
-    }
-    double run = 0.0;
-#pragma unroll
-    for (int o = 0; o < (PARTNER ? 4 : 2); ++o) run += p[o] < 0.0 ? 0.0 : p[o];
-    return run;
-}
-
 // ------------------------------------------------------------------------------------------------ distributions, one qubit
 // a lane per item: 4 x 4 matrices in registers, every row product one chain of fused multiply-adds in ascending column order
 __device__ __forceinline__ void rpes_matvec4(const double (&A)[16], const double (&x)[4], double (&y)[4]) {

@@ -1,8 +1,9 @@
 // fbx_sim_shared.hpp -- code that several translation units evaluate and whose results the tests pin bit for bit: the shot
 // counting of the simulated experiments (sim_*, tomo_count: fbx_tomo_sim.hip, fbx_tomo_sim_grouped.hip, fbx_tomo_sim_symm.hip,
-// fbx_dfe.hip, fbx_rpe_sim.hip) with the host checks and staging their entry points share, the exact mean of a tomography
-// setting (fbx_tomo_sim.hip, fbx_tomo_sim_grouped.hip), the direct-fidelity formula (fbx_shots.hip, fbx_dfe.hip) and the
-// moments of a robust-phase-estimation record (fbx_rpe.hip, fbx_rpe_sim.hip).
+// fbx_dfe.hip, fbx_rpe_sim.hip, fbx_rb_acquire.hip) with the host checks and staging their entry points share, the exact mean
+// of a tomography setting (fbx_tomo_sim.hip, fbx_tomo_sim_grouped.hip), the direct-fidelity formula (fbx_shots.hip,
+// fbx_dfe.hip), the moments of a robust-phase-estimation record (fbx_rpe.hip, fbx_rpe_sim.hip, fbx_rb_acquire.hip) and the
+// outcome distribution of a measured Pauli vector (fbx_rpe_sim.hip, fbx_rb_acquire.hip).
 //
 // Three compare loops stay where they are, different on purpose: tomog_sim_kernel<NQ> tests `thi == 0 && tlo <= w` on
 // wave-uniform operands (fbx_tomo_sim_grouped.hip); the lane forms test `live && tlo <= w` (sim_count_word below); and
@@ -235,6 +236,46 @@ __device__ inline double tomo_mean(const DesignDev& des, const double* __restric
         if (T == 0) break;
     }
     return mu;
+}
+
+// ... and of the simulators that measure a final Pauli vector (fbx_rpe_sim.hip, fbx_rb_acquire.hip)
+__device__ __forceinline__ bool rpes_finite(double v) { return fabs(v) < __builtin_inf(); }              // false for NaN
+__device__ __forceinline__ bool rpes_bad_total(double c) { return !(c > 0.0 && c < __builtin_inf()); }   // NaN included
+
+// The outcome distribution of one basis at one depth from four components of the final Pauli vector: vI the identity (1 for a
+// trace-preserving map), vP = <P_a>, vZ = <Z_b>, vPZ = <P_a Z_b>.  Outcome o = 2 s + t with a partner, o = s without.  fa / fb:
+// the flips of the xy qubit / the partner, or NULL.  Returns the clamped sum.
+template <bool PARTNER>
+__device__ __forceinline__ double rpes_distribution(double vI, double vP, double vZ, double vPZ, const double* __restrict__ fa,
+                                                    const double* __restrict__ fb, double (&p)[4]) {
+    if constexpr (PARTNER) {
+        const double a = vI + vP, b = vI - vP;
+        p[0] = ((a + vZ) + vPZ) * 0.25; p[1] = ((a - vZ) - vPZ) * 0.25;
+        p[2] = ((b + vZ) - vPZ) * 0.25; p[3] = ((b - vZ) + vPZ) * 0.25;
+        if (fa) {
+            const double f0 = fa[0], f1 = fa[1], g0 = fb[0], g1 = fb[1];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {                     // the bit s: pairs (t, 2 + t)
+                const double x = p[t], y = p[2 + t];
+                p[t] = fma(1.0 - f0, x, f1 * y); p[2 + t] = fma(1.0 - f1, y, f0 * x);
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {                     // the bit t: pairs (2 s, 2 s + 1)
+                const double x = p[2 * s], y = p[2 * s + 1];
+                p[2 * s] = fma(1.0 - g0, x, g1 * y); p[2 * s + 1] = fma(1.0 - g1, y, g0 * x);
+            }
+        }
+    } else {
+        p[0] = (vI + vP) * 0.5; p[1] = (vI - vP) * 0.5; p[2] = 0.0; p[3] = 0.0;
+        if (fa) {
+            const double f0 = fa[0], f1 = fa[1], x = p[0], y = p[1];
+            p[0] = fma(1.0 - f0, x, f1 * y); p[1] = fma(1.0 - f1, y, f0 * x);
+        }
+    }
+    double run = 0.0;
+#pragma unroll
+    for (int o = 0; o < (PARTNER ? 4 : 2); ++o) run += p[o] < 0.0 ? 0.0 : p[o];
+    return run;
 }
 
 // counts of -1 outcomes -> mean of the +-1 values and the variance of that mean, fbx_shots_to_moments' formulas with coef = 1

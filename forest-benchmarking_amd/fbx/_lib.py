@@ -28,6 +28,8 @@ HIST_MAX_SHOTS = 2 ** 31 - 1
 HIST_WAVE_BYTES = 16384         # records below this many bytes get a wavefront each (csrc/fbx_histogram.hip)
 CLIFFORD_NONE = 0xFFFFFFFF      # no element: "no interleaved gate" / "no such index" (include/fbx.h)
 RB_MAX_NOISE_PTMS = 16
+RB_STANDARD, RB_UNITARITY = 0, 1        # modes of fbx_rb_acquire
+RB_ACQUIRE_MAX_DEPTHS = 256
 DFE_MAX_CLASSES = 16
 DFE_NOISELESS = 255             # noise class of a gate without noise (include/fbx.h)
 RPE_SIM_LANE_MIN_UNITS = 131072 # from this many (item, depth, basis) units on a lane takes a unit (csrc/fbx_rpe_sim.hip)
@@ -215,6 +217,12 @@ PROTOTYPES = {
     "fbx_rb_sequences_dev": [C.c_int, _i64, _vp, C.c_uint64, C.c_uint32, C.c_int, _vp, _vp],
     "fbx_rb_simulate": [C.c_int, _i64, _i64p, _u32p, _u8p, C.c_int, _dp, _dp, _dp],
     "fbx_rb_simulate_dev": [C.c_int, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp],
+    "fbx_rb_acquire": [C.c_int, _i64, C.c_int, _ip, C.c_int, C.c_int, C.c_uint32, C.c_int, _dp, _dp, _dp, _i64, C.c_uint64, _i64,
+                       _dp, _dp, _u32p, _dp, _dp, _ip],
+    "fbx_rb_acquire_dev": [C.c_int, _i64, C.c_int, _ip, C.c_int, C.c_int, C.c_uint32, C.c_int, _vp, _vp, _vp, _i64, C.c_uint64, _i64,
+                           _vp, _vp, _vp, _vp, _vp, _vp],
+    "fbx_rb_depth_means": [_i64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp],
+    "fbx_rb_depth_means_dev": [_i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
     "fbx_clifford_conjugate": [C.c_int, _i64, _u32p, C.c_int, _i64, _u64p, _u64p, _u8p, _u64p, _u64p, _u8p],
     "fbx_clifford_conjugate_dev": [C.c_int, _i64, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     "fbx_dfe_settings": [C.c_int, C.c_int, _i64, C.c_uint64, _i64, _u32p, _i64, _u64p, _u64p, _u64p, _u64p, _u64p, _u8p],

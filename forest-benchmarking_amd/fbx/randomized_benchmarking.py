@@ -10,8 +10,11 @@ Sequence generation (``generate_rb_sequence``, ``generate_rb_experiment_sequence
 needs no quilc: a Clifford is an element word of ``fbx.clifford`` (include/fbx.h, "Clifford elements"), a sequence an array of
 words drawn, composed and inverted on the device (fbx_rb_sequences); ``clifford.to_gates`` turns a word into native gates.
 ``simulate_rb_sequences_batch`` runs sequences under Pauli-transfer-matrix noise (fbx_rb_simulate), ``simulate_rb_experiment_batch``
-turns that into the arrays ``fit_rb_results_batch`` takes.  Data acquisition on a QuantumComputer (``acquire_*``, ``do_rb``) needs
-pyquil and is not part of this package.
+turns that into the arrays ``fit_rb_results_batch`` takes.  ``simulate_rb_acquisition_batch`` /
+``simulate_unitarity_acquisition_batch`` are the acquisition itself in one device call per batch of experiments (fbx_rb_acquire:
+sequences drawn on the fly, per-experiment noise and readout error, shots counted on the device, IZ / ZI / ZZ from the same
+shots), ``simulate_and_fit_rb_batch`` / ``simulate_and_fit_unitarity_batch`` the chains from channels to fitted decays that stay
+on the device.  Data acquisition on a QuantumComputer (``acquire_*``, ``do_rb``) needs pyquil and is not part of this package.
 """
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -430,3 +433,273 @@ def simulate_rb_experiment_batch(n_qubits: int, depths: Sequence[int], num_seque
         e_out[x] = z.mean(axis=1)
         s_out[x] = np.sqrt(z.var(axis=1, ddof=1) / K) if K > 1 else np.sqrt(shot_var + np.zeros_like(e_out[x]))
     return e_out, s_out
+
+
+# ---------------------------------------------------------------- acquisition on the device: channels to expectations (fbx_rb_acquire)
+_DEPTH_MESSAGE = "Sequence depth must be at least 2 for rb sequences, or at least 1 for unitarity sequences."
+
+
+def generate_unitarity_experiment_sequences(benchmarker, qubits: Sequence[int], depths: Sequence[int], num_sequences: int,
+                                            random_seed: Optional[int] = None) -> List[np.ndarray]:
+    """The sequences of a unitarity experiment (generate_unitarity_experiments, randomized_benchmarking.py:441-487, before the
+    grouping into programs): ``num_sequences`` sequences of ``depth`` random Cliffords for every entry of ``depths``, NOT
+    self-inverting, as a list of uint32 arrays of element words in the order depth 0 repetition 0, 1, ..., depth 1 repetition 0,
+    ....  One device call (fbx_rb_sequences with self_inverting = 0); sequence b depends on ``(random_seed, b)`` only, and these are
+    the sequences ``simulate_unitarity_acquisition_batch`` measures for the experiment whose seed + index is ``random_seed``.
+    ``benchmarker`` is accepted for the reference's signature and ignored."""
+    n = _n_qubits(len(qubits))
+    if int(num_sequences) < 1:
+        raise ValueError("num_sequences must be positive")
+    offsets, elems, _ = generate_rb_sequences_batch(n, depths, int(num_sequences), None, random_seed, self_inverting=False)
+    return [elems[offsets[b]:offsets[b + 1]].copy() for b in range(offsets.size - 1)]
+
+
+def predicted_rb_decay(ptm):
+    """The RB decay (tr L - 1) / (d^2 - 1) of gate-independent noise with Pauli transfer matrix ``ptm [..., d^2, d^2]``."""
+    ptm = np.asarray(ptm, dtype=np.float64)
+    return (np.trace(ptm, axis1=-2, axis2=-1) - 1.0) / (ptm.shape[-1] - 1)
+
+
+def predicted_unitarity(ptm):
+    """The unitarity of a channel: the squared Frobenius norm of the unital block of ``ptm [..., d^2, d^2]`` (rows and columns
+    1..d^2 - 1) divided by d^2 - 1 (Wallman et al., New J. Phys. 17, 113020 (2015))."""
+    ptm = np.asarray(ptm, dtype=np.float64)
+    return np.sum(ptm[..., 1:, 1:] ** 2, axis=(-2, -1)) / (ptm.shape[-1] - 1)
+
+
+def unitarity_basis_of_pauli(n_qubits: int, pauli: int) -> int:
+    """The one measured basis of a unitarity acquisition that Pauli index ``pauli`` (1 .. 4^n - 1) is read from: its non-identity
+    factors, and Z on every qubit where it has the identity.  Basis index in base 3, digits X, Y, Z = 0, 1, 2, qubit 0 most
+    significant (include/fbx.h, fbx_rb_acquire step 5)."""
+    n = _n_qubits(n_qubits)
+    if not 1 <= int(pauli) < 4 ** n:
+        raise ValueError("pauli must be a non-identity Pauli index")
+    basis = 0
+    for t in reversed(range(n)):
+        digit = (int(pauli) >> (2 * t)) & 3
+        basis = 3 * basis + (digit - 1 if digit else 2)
+    return basis
+
+
+class _Acquisition:
+    """Validated arguments of one fbx_rb_acquire call."""
+
+    def __init__(self, n_qubits, depths, num_sequences, noise_ptms, interleaved_gate, shots, flips, prep, seed, first_item, unitarity):
+        n = self.n = _n_qubits(n_qubits)
+        D = self.D = 4 ** n
+        self.depths = np.array([int(d) for d in depths], dtype=np.int32)
+        self.S, self.K = self.depths.size, int(num_sequences)
+        if self.S < 1:
+            raise ValueError("depths must not be empty")
+        if self.depths.min() < (1 if unitarity else 2):
+            raise ValueError(_DEPTH_MESSAGE)
+        if self.S > _lib.RB_ACQUIRE_MAX_DEPTHS:
+            raise ValueError(f"at most {_lib.RB_ACQUIRE_MAX_DEPTHS} depths per call")
+        if self.K < 1:
+            raise ValueError("num_sequences must be positive")
+        if unitarity and interleaved_gate is not None:
+            raise ValueError("a unitarity experiment takes no interleaved gate")
+        self.inter = _interleaved_word(n, interleaved_gate)
+        self.G = 2 if interleaved_gate is not None else 1
+        ptms = np.asarray(noise_ptms, dtype=np.float64)
+        if ptms.ndim == 2:
+            ptms = ptms[None]
+        if ptms.ndim == 3:
+            ptms = ptms[None]
+        if ptms.ndim != 4 or ptms.shape[2:] != (D, D):
+            raise ValueError(f"noise_ptms must be [G, {D}, {D}] or [E, G, {D}, {D}]")
+        if ptms.shape[1] < self.G:
+            raise ValueError("an interleaved experiment needs two noise PTMs: [0] after the random Cliffords, [1] after the gate")
+        self.ptms = np.ascontiguousarray(ptms[:, :self.G])
+        self.E = self.ptms.shape[0]
+        self.flips = None
+        if flips is not None:
+            f = np.asarray(flips, dtype=np.float64)
+            if f.shape not in ((n, 2), (self.E, n, 2)):
+                raise ValueError(f"flips must be [{n}, 2] or [E, {n}, 2]")
+            self.flips = np.ascontiguousarray(np.broadcast_to(f, (self.E, n, 2)))
+        self.prep = None
+        if prep is not None:
+            self.prep = np.ascontiguousarray(prep, dtype=np.float64)
+            if self.prep.shape != (D,):
+                raise ValueError(f"prep must be a Pauli vector of {D} components")
+        self.shots = 0 if shots is None else int(shots)
+        if not 0 <= self.shots < 2 ** 31:
+            raise ValueError("shots must be in 0 .. 2^31 - 1 (None or 0: exact expectations)")
+        self.first_item = int(first_item)
+        if self.first_item < 0:
+            raise ValueError("first_item must not be negative")
+        self.seed = _seed64(seed)
+        self.mode = _lib.RB_UNITARITY if unitarity else _lib.RB_STANDARD
+        self.M = 2 ** n
+        self.NB = 3 ** n if unitarity else 1
+        self.C = D - 1 if unitarity else self.M - 1
+        if self.S * self.K * self.NB >= 2 ** 32:
+            raise ValueError("len(depths) * num_sequences * bases must be below 2^32")
+
+    def launch(self, dev, vectors=False, probabilities=False, histograms=False):
+        """Enqueue the acquisition on buffers owned by ``dev``; returns the device buffers (None where not asked for) as
+        ``(expect, std_err, status, vec, prob, hist)``."""
+        if histograms and self.shots == 0:
+            raise ValueError("histograms need shots >= 1")
+        seqs = self.E * self.S * self.K
+        d_ptms, d_prep, d_flips = dev.upload(self.ptms), dev.upload(self.prep), dev.upload(self.flips)
+        d_e, d_s, d_st = dev.alloc(8 * seqs * self.C), dev.alloc(8 * seqs * self.C), dev.alloc(4 * self.E)
+        d_vec = dev.alloc(8 * seqs * self.D) if vectors else None
+        d_prob = dev.alloc(8 * seqs * self.NB * self.M) if probabilities else None
+        d_hist = dev.alloc(4 * seqs * self.NB * self.M) if histograms else None
+        _lib.check(_lib.lib().fbx_rb_acquire_dev(
+            self.n, self.E, self.S, self.depths.ctypes.data_as(_lib._ip), self.K, self.mode, self.inter, self.G, d_ptms.ptr,
+            _lib.devptr(d_prep), _lib.devptr(d_flips), self.shots, self.seed, self.first_item, _lib.devptr(d_vec), _lib.devptr(d_prob),
+            _lib.devptr(d_hist), d_e.ptr, d_s.ptr, d_st.ptr))
+        return d_e, d_s, d_st, d_vec, d_prob, d_hist
+
+    def status(self, d_status, return_status):
+        status = d_status.to_array(np.int32, (self.E,))
+        if not return_status and status.any():
+            raise ValueError(f"experiment {int(np.flatnonzero(status)[0])} is poisoned: a non-finite noise PTM or prep entry, a flip "
+                             "probability outside [0, 1], or an outcome distribution without a positive finite sum")
+        return status
+
+
+def _acquisition_batch(a, per_sequence, return_vectors, return_probabilities, return_histograms, return_status):
+    seqs = a.S * a.K
+    with _lib.DeviceScope() as dev:
+        d_e, d_s, d_st, d_vec, d_prob, d_hist = a.launch(dev, return_vectors, return_probabilities, return_histograms)
+        if per_sequence:
+            e, s = d_e.to_array(np.float64, (a.E, seqs, a.C)), d_s.to_array(np.float64, (a.E, seqs, a.C))
+        else:
+            d_m, d_err = dev.alloc(8 * a.E * a.S * a.C), dev.alloc(8 * a.E * a.S * a.C)
+            _lib.check(_lib.lib().fbx_rb_depth_means_dev(a.E, a.S, a.K, a.C, d_e.ptr, d_s.ptr, d_m.ptr, d_err.ptr))
+            e, s = d_m.to_array(np.float64, (a.E, a.S, a.C)), d_err.to_array(np.float64, (a.E, a.S, a.C))
+        status = a.status(d_st, return_status)
+        out = (e, s)
+        if return_vectors:
+            out += (d_vec.to_array(np.float64, (a.E, seqs, a.D)),)
+        if return_probabilities:
+            out += (d_prob.to_array(np.float64, (a.E, seqs, a.NB, a.M)),)
+        if return_histograms:
+            out += (d_hist.to_array(np.uint32, (a.E, seqs, a.NB, a.M)),)
+    return out + ((status,) if return_status else ())
+
+
+def simulate_rb_acquisition_batch(n_qubits: int, depths: Sequence[int], num_sequences: int, noise_ptms,
+                                  interleaved_gate: Optional[int] = None, shots: Optional[int] = None, flips=None, prep=None,
+                                  seed: Optional[int] = None, first_item: int = 0, per_sequence: bool = False,
+                                  return_vectors: bool = False, return_probabilities: bool = False,
+                                  return_histograms: bool = False, return_status: bool = False):
+    """E RB (or, with ``interleaved_gate``, IRB) experiments from noise channels to measured expectations in one device call
+    (fbx_rb_acquire): ``noise_ptms [E, G, 4^n, 4^n]`` (lower ranks broadcast as in ``simulate_rb_experiment_batch``; matrix 0
+    follows every random Clifford and the inverse, matrix 1 the interleaved gate), ``flips [E, n, 2]`` or ``[n, 2]`` the readout
+    errors (P(read 1 | 0), P(read 0 | 1)) per qubit, ``shots`` per sequence (None or 0: exact expectations).  Experiment x is the
+    global item ``first_item + x``; it runs the sequences ``generate_rb_sequences_batch(..., seed + first_item + x)`` -- those of
+    ``simulate_rb_experiment_batch`` -- and IZ, ZI, ZZ are read off the SAME shots, as ``fit_rb_results_batch(..., num_shots)``
+    assumes.  Returns ``(z_expectations, z_std_errs)``, both ``[E, S, 2^n - 1]`` in the order of ``z_product_indices``: the mean
+    over the ``num_sequences`` sequences of a depth and the standard error of that mean (fbx_rb_depth_means; for one sequence
+    per depth the sequence's own standard error).  ``per_sequence`` gives ``[E, S K, 2^n - 1]`` instead, sequence ``i K + s`` at
+    depth ``np.repeat(depths, K)[i K + s]``: what the reference's ``fit_rb_results`` is fed.  ``return_vectors`` /
+    ``return_probabilities`` / ``return_histograms`` append the final Pauli vectors ``[E, S K, 4^n]``, the outcome distributions
+    and the counts ``[E, S K, 1, 2^n]``; ``return_status`` appends the status ``[E]`` instead of raising for a poisoned experiment
+    (NaN outputs, zero counts)."""
+    a = _Acquisition(n_qubits, depths, num_sequences, noise_ptms, interleaved_gate, shots, flips, prep, seed, first_item, False)
+    return _acquisition_batch(a, per_sequence, return_vectors, return_probabilities, return_histograms, return_status)
+
+
+def simulate_unitarity_acquisition_batch(n_qubits: int, depths: Sequence[int], num_sequences: int, noise_ptms,
+                                         shots: Optional[int] = None, flips=None, prep=None, seed: Optional[int] = None,
+                                         first_item: int = 0, return_vectors: bool = False, return_probabilities: bool = False,
+                                         return_histograms: bool = False, return_status: bool = False):
+    """E unitarity experiments in one device call: sequences of ``depth`` random Cliffords without the inverse
+    (``generate_unitarity_experiment_sequences`` under the seed ``seed + first_item + x``), measured in all 3^n products of X, Y,
+    Z with ``shots`` shots per sequence and basis; every Pauli is estimated from the one basis
+    ``unitarity_basis_of_pauli`` names.  Returns ``(expectations, std_errs)`` of shape ``[E, S K, 4^n - 1]`` (Pauli indices
+    1 .. 4^n - 1), as ``fit_unitarity_results_batch(np.repeat(depths, K), ...)`` and ``purity_statistics_batch`` take them; the
+    other arguments and the appended outputs are those of ``simulate_rb_acquisition_batch`` (distributions and counts
+    ``[E, S K, 3^n, 2^n]``)."""
+    a = _Acquisition(n_qubits, depths, num_sequences, noise_ptms, None, shots, flips, prep, seed, first_item, True)
+    return _acquisition_batch(a, True, return_vectors, return_probabilities, return_histograms, return_status)
+
+
+def depth_means_batch(values, seq_std_errs=None):
+    """Mean over the K sequences of a depth and the standard error of that mean for ``values [E, S, K, C]`` (fbx_rb_depth_means):
+    ``sqrt(var(ddof=1) / K)``, or for K = 1 the sequence's own ``seq_std_errs [E, S, 1, C]`` (None: 0).  Returns two ``[E, S, C]``."""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    if v.ndim != 4:
+        raise ValueError("values must be [E, S, K, C]")
+    E, S, K, C = v.shape
+    se = None
+    if seq_std_errs is not None:
+        se = np.ascontiguousarray(seq_std_errs, dtype=np.float64)
+        if se.shape != v.shape:
+            raise ValueError("seq_std_errs must have the shape of values")
+    mean, err = np.empty((E, S, C)), np.empty((E, S, C))
+    _lib.check(_lib.lib().fbx_rb_depth_means(E, S, K, C, _lib.dptr(v), _lib.dptr(se) if K == 1 else None, _lib.dptr(mean), _lib.dptr(err)))
+    return mean, err
+
+
+def _fit_points(a, points):
+    if points not in ("depth", "sequence"):
+        raise ValueError("points must be 'depth' or 'sequence'")
+    P = a.S if points == "depth" else a.S * a.K
+    if not 2 <= P <= _lib.FIT_MAX_POINTS:
+        raise ValueError(f"a fit takes 2..{_lib.FIT_MAX_POINTS} points (got {P}); use points='depth' or fewer sequences")
+    return P, (a.depths.astype(np.float64) if points == "depth" else np.repeat(a.depths, a.K).astype(np.float64))
+
+
+def _fit_resident(dev, kind, x, d_values, d_errors, errors_are_variances, B, P, param_guesses, fit_kw):
+    d_w, d_g, d_has = dev.alloc(8 * B * P), dev.alloc(8 * B * 3), dev.alloc(4 * B)
+    _lib.check(_lib.lib().fbx_fit_prepare_dev(kind, B, P, d_values.ptr, d_errors.ptr, int(errors_are_variances), d_w.ptr, d_g.ptr,
+                                              d_has.ptr))
+    if param_guesses is not None:
+        g = fitting._guess_array(_lib.FIT_BASE_DECAY, param_guesses, B)
+        _lib.check(_lib.lib().fbx_memcpy_h2d(d_g.ptr, g.ctypes.data, g.nbytes))
+    batch = fitting.curve_fit_resident(_lib.FIT_BASE_DECAY, x, d_values, d_w, d_g, B, P, **fit_kw)
+    batch.has_weights = d_has.to_array(np.int32, (B,)).astype(bool)
+    return batch
+
+
+def simulate_and_fit_rb_batch(n_qubits: int, depths: Sequence[int], num_sequences: int, noise_ptms,
+                              interleaved_gate: Optional[int] = None, shots: Optional[int] = None, flips=None, prep=None,
+                              seed: Optional[int] = None, first_item: int = 0, points: str = "depth", param_guesses=None,
+                              **fit_kw) -> "fitting.FitBatch":
+    """``simulate_rb_acquisition_batch`` followed by ``fit_rb_results_batch(..., num_shots=shots)`` without leaving the device:
+    fbx_rb_acquire_dev -> (``points="depth"``: fbx_rb_depth_means_dev over the sequences of a depth) -> fbx_rb_survival_dev ->
+    fbx_fit_prepare_dev -> fbx_curve_fit_dev, bit for bit what the two public calls return.  ``points="sequence"`` fits every
+    sequence as a point of its own (``per_sequence=True``; S K <= 256).  Without shots the covariance term of IZ, ZI, ZZ is left
+    out (it vanishes).  Returns the FitBatch of E decays; a poisoned experiment raises ``ValueError``."""
+    a = _Acquisition(n_qubits, depths, num_sequences, noise_ptms, interleaved_gate, shots, flips, prep, seed, first_item, False)
+    P, x = _fit_points(a, points)
+    num_shots = a.shots if a.M > 2 else 0                      # exact expectations (shots None or 0) have no covariance term
+    with _lib.DeviceScope() as dev:
+        d_e, d_s, d_st = a.launch(dev)[:3]
+        if points == "depth":
+            d_m, d_err = dev.alloc(8 * a.E * a.S * a.C), dev.alloc(8 * a.E * a.S * a.C)
+            _lib.check(_lib.lib().fbx_rb_depth_means_dev(a.E, a.S, a.K, a.C, d_e.ptr, d_s.ptr, d_m.ptr, d_err.ptr))
+            d_e, d_s = d_m, d_err
+        d_surv, d_var = dev.alloc(8 * a.E * P), dev.alloc(8 * a.E * P)
+        _lib.check(_lib.lib().fbx_rb_survival_dev(a.M, a.E * P, d_e.ptr, d_s.ptr, num_shots, d_surv.ptr, d_var.ptr))
+        a.status(d_st, False)
+        return _fit_resident(dev, _lib.FIT_PREPARE_RB, x, d_surv, d_var, True, a.E, P, param_guesses, fit_kw)
+
+
+def simulate_and_fit_unitarity_batch(n_qubits: int, depths: Sequence[int], num_sequences: int, noise_ptms,
+                                     shots: Optional[int] = None, flips=None, prep=None, seed: Optional[int] = None,
+                                     first_item: int = 0, points: str = "depth", param_guesses=None, **fit_kw) -> "fitting.FitBatch":
+    """``simulate_unitarity_acquisition_batch`` followed by the unitarity fit without leaving the device: fbx_rb_acquire_dev ->
+    fbx_rb_purity_dev -> (``points="depth"``: fbx_rb_depth_means_dev of the purities, C = 1) -> fbx_fit_prepare_dev ->
+    fbx_curve_fit_dev.  ``points="sequence"`` is ``fit_unitarity_results_batch(np.repeat(depths, K), ...)`` bit for bit (S K <=
+    256); ``points="depth"`` is ``purity_statistics_batch`` -> ``depth_means_batch`` -> the same preparation and fit.  The
+    unitarities are ``batch.value('decay')``."""
+    a = _Acquisition(n_qubits, depths, num_sequences, noise_ptms, None, shots, flips, prep, seed, first_item, True)
+    P, x = _fit_points(a, points)
+    seqs = a.E * a.S * a.K
+    with _lib.DeviceScope() as dev:
+        d_e, d_s, d_st = a.launch(dev)[:3]
+        d_pur, d_err = dev.alloc(8 * seqs), dev.alloc(8 * seqs)
+        _lib.check(_lib.lib().fbx_rb_purity_dev(a.M, seqs, d_e.ptr, d_s.ptr, 1, d_pur.ptr, d_err.ptr))
+        if points == "depth":
+            d_m, d_me = dev.alloc(8 * a.E * a.S), dev.alloc(8 * a.E * a.S)
+            _lib.check(_lib.lib().fbx_rb_depth_means_dev(a.E, a.S, a.K, 1, d_pur.ptr, d_err.ptr, d_m.ptr, d_me.ptr))
+            d_pur, d_err = d_m, d_me
+        a.status(d_st, False)
+        return _fit_resident(dev, _lib.FIT_PREPARE_UNITARITY, x, d_pur, d_err, False, a.E, P, param_guesses, fit_kw)

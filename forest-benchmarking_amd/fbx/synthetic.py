@@ -713,3 +713,122 @@ def restate_rpe_counts(probs, n_shots, seed, first_item=0):
             moments[2 * which + basis] = mean
             moments[4 + 2 * which + basis] = (1.0 - mean * mean) / Nf
     return hist, moments
+
+
+# --------------------------------------------------------------------------------------------------
+# fbx_rb_acquire (include/fbx.h) on the host: the distributions mirrored in numpy, the shots restated in integers.
+# --------------------------------------------------------------------------------------------------
+RB_ACQUIRE_KEY_TAG = 0x52424151          # "RBAQ": the shots of fbx_rb_acquire
+
+
+def rb_measured_bases(n_qubits, mode):
+    """The measured bases of ``fbx_rb_acquire`` in basis-index order, each a tuple of Pauli digits (1, 2, 3 = X, Y, Z), one per
+    qubit: ``mode`` "standard" (Z on every qubit) or "unitarity" (all 3^n products, qubit 0 most significant)."""
+    if mode not in ("standard", "unitarity"):
+        raise ValueError("mode must be 'standard' or 'unitarity'")
+    n = int(n_qubits)
+    return [(3,) * n] if mode == "standard" else list(itertools.product((1, 2, 3), repeat=n))
+
+
+def rb_pauli_assignment(n_qubits, mode):
+    """``[(pauli index, basis index, outcome mask)]`` for the columns of ``expect_out`` in order: column c is read from the
+    histogram of that ONE basis as the parity of the outcome bits in the mask (bit n - 1 - q of an outcome belongs to qubit q).
+    Standard: the I/Z products in the order of ``randomized_benchmarking.z_product_indices``, all from basis 0.  Unitarity: Pauli
+    indices 1 .. 4^n - 1; a Pauli is read from the basis with its own non-identity factors and Z on every idle qubit."""
+    n = int(n_qubits)
+    bases = rb_measured_bases(n, mode)
+    if mode == "standard":
+        paulis = [sum(3 << (2 * t) for t in range(n) if (z >> t) & 1) for z in range(1, 1 << n)]
+    else:
+        paulis = list(range(1, 4 ** n))
+    out = []
+    for k in paulis:
+        digits = [(k >> (2 * (n - 1 - q))) & 3 for q in range(n)]
+        mask = sum(1 << (n - 1 - q) for q in range(n) if digits[q])
+        out.append((k, bases.index(tuple(d if d else 3 for d in digits)), mask))
+    return out
+
+
+def rb_outcome_distributions(vectors, n_qubits, mode, flips=None):
+    """Step 3 of the contract of ``fbx_rb_acquire``: final Pauli vectors ``[..., 4^n]`` -> outcome distributions ``[..., NB, 2^n]``,
+    p(o) = 2^-n sum_T (-1)^|o & T| v[P_T] per measured basis, then the confusion matrix of every qubit's ``flips`` (``[n, 2]``, or
+    ``[E, n, 2]`` with E the first axis of ``vectors``; [q][0] = P(read 1 | 0), [q][1] = P(read 0 | 1)).  The arithmetic runs in the
+    dtype of ``vectors`` when that is ``numpy.longdouble`` and in float64 otherwise; the sums are numpy's, so the device agrees
+    within rounding, not bit for bit."""
+    v = np.asarray(vectors)
+    dt = np.longdouble if v.dtype == np.longdouble else np.float64
+    v = v.astype(dt)
+    n = int(n_qubits)
+    D, M = 4 ** n, 2 ** n
+    if v.shape[-1] != D:
+        raise ValueError(f"vectors must be [..., {D}]")
+    bases = rb_measured_bases(n, mode)
+    out = np.empty(v.shape[:-1] + (len(bases), M), dtype=dt)
+    for bi, digits in enumerate(bases):
+        for o in range(M):
+            acc = np.zeros(v.shape[:-1], dtype=dt)
+            for T in range(M):
+                idx = sum(digits[q] << (2 * (n - 1 - q)) for q in range(n) if (T >> (n - 1 - q)) & 1)
+                term = v[..., idx]
+                acc = acc - term if bin(o & T).count("1") & 1 else acc + term
+            out[..., bi, o] = acc / dt(M)
+    if flips is not None:
+        f = np.asarray(flips).astype(dt)
+        if f.ndim == 3:
+            f = f.reshape((f.shape[0],) + (1,) * (out.ndim - 2) + f.shape[1:])          # [E, 1.., n, 2] against [E, .., NB, M]
+        p = out.reshape(out.shape[:-1] + (2,) * n)
+        for q in range(n):
+            f0, f1 = f[..., q, 0], f[..., q, 1]
+            f0, f1 = f0.reshape(f0.shape + (1,) * (n - 1)), f1.reshape(f1.shape + (1,) * (n - 1))      # over the other qubits' bits
+            ax = p.ndim - n + q
+            p0, p1 = np.take(p, 0, axis=ax), np.take(p, 1, axis=ax)
+            p = np.stack([(1 - f0) * p0 + f1 * p1, f0 * p0 + (1 - f1) * p1], axis=ax)
+        out = p.reshape(out.shape)
+    return out
+
+
+def restate_rb_counts(probs, shots, mode, seed, first_item=0):
+    """Steps 4-5 of the contract of ``fbx_rb_acquire`` (include/fbx.h) restated on the host, in integers, from the distributions it
+    reports: ``probs [E, Q, NB, M]`` (Q = S K sequences, M = 2 or 4).  Per (experiment, sequence q, basis): c = cumsum(max(p, 0)) in
+    outcome order, thr_o = floor(c_o / c_last 2^32) for every outcome but the last; shot s reads word ``s & 3`` of the
+    Philox4x32-10 block with counter (gid low, gid high, q NB + basis, s >> 2) and key (seed low ^ 0x52424151, seed high), gid =
+    first_item + experiment; its outcome is the number of thresholds <= the word.  Returns ``(hist [E, Q, NB, M] int64,
+    expectations [E, Q, C], std_errs [E, Q, C])``: column c from the basis and parity mask of ``rb_pauli_assignment``, mean =
+    ((N - n_odd) - n_odd) / N and sqrt((1 - mean^2) / N)."""
+    p = np.asarray(probs, dtype=np.float64)
+    if p.ndim != 4 or p.shape[3] not in (2, 4):
+        raise ValueError("need probs [E, Q, NB, M] with M = 2 or 4")
+    E, Q, NB, M = p.shape
+    n = {2: 1, 4: 2}[M]
+    if NB != len(rb_measured_bases(n, mode)):
+        raise ValueError("the number of bases does not match the mode")
+    N, seed, first_item = int(shots), int(seed) & (2 ** 64 - 1), int(first_item)
+    if not 1 <= N < 2 ** 31 or first_item < 0 or Q * NB >= 2 ** 32:
+        raise ValueError("need 1 <= shots < 2^31, first_item >= 0 and Q NB < 2^32")
+    c = np.cumsum(np.where(p < 0.0, 0.0, p), axis=3)                    # one addition per outcome, in outcome order
+    if not np.all((c[..., -1] > 0.0) & np.isfinite(c[..., -1])):
+        raise ValueError("a distribution whose clamped sum is not a positive finite number (a poisoned experiment) cannot be restated")
+    thr = np.floor(c[..., :-1] / c[..., -1:] * 2.0 ** 32).astype(np.uint64).reshape(E, Q * NB, M - 1)
+    k0, k1 = (seed & 0xFFFFFFFF) ^ RB_ACQUIRE_KEY_TAG, seed >> 32
+    blocks = np.arange((N + 3) // 4, dtype=np.uint64)
+    units = np.arange(Q * NB, dtype=np.uint64)
+    rows = max(1, (1 << 20) // len(blocks))                              # units per pass: about 2^20 blocks at a time
+    hist = np.zeros((E, Q * NB, M), dtype=np.int64)
+    for e in range(E):
+        gid = first_item + e
+        for lo in range(0, Q * NB, rows):
+            sl = slice(lo, lo + rows)
+            words = _philox4x32_10(np.uint64(gid & 0xFFFFFFFF), np.uint64(gid >> 32), units[sl, None], blocks[None, :], k0, k1)
+            w = np.stack(np.broadcast_arrays(*words), axis=2).reshape(len(units[sl]), -1)[:, :N]     # shot s = word s & 3 of block s >> 2
+            outcome = (thr[e, sl, None, :] <= w[:, :, None]).sum(axis=2)
+            for o in range(M):
+                hist[e, sl, o] = (outcome == o).sum(axis=1)
+    hist = hist.reshape(E, Q, NB, M)
+    assign = rb_pauli_assignment(n, mode)
+    expect, std_err = np.empty((E, Q, len(assign))), np.empty((E, Q, len(assign)))
+    for col, (_, basis, mask) in enumerate(assign):
+        n_odd = sum(hist[:, :, basis, o] for o in range(M) if bin(o & mask).count("1") & 1)
+        mean = ((N - n_odd).astype(np.float64) - n_odd.astype(np.float64)) / float(N)
+        expect[:, :, col] = mean
+        std_err[:, :, col] = np.sqrt((1.0 - mean * mean) / float(N))
+    return hist, expect, std_err

@@ -1124,6 +1124,85 @@ int fbx_rb_simulate(int n_qubits, int64_t B, const int64_t* offsets, const uint3
 int fbx_rb_simulate_dev(int n_qubits, int64_t B, const int64_t* d_offsets, const uint32_t* d_elems, const uint8_t* d_noise_ids, int G,
                         const double* d_noise_ptms, const double* d_prep, double* d_out);
 
+/* ---------------------------------------------------------------- simulated RB and unitarity experiments: channels to expectations
+ * What generate_rb_experiment_sequences / generate_unitarity_experiment_sequences with acquire_rb_data / acquire_unitarity_data
+ * (randomized_benchmarking.py:129-305, 441-487) get from quilc and a QVM, for E experiments at once and in one launch: every
+ * experiment draws S K sequences, runs them under its own noise and measures them; no element word reaches memory.  n_qubits is 1
+ * or 2, D = 4^n_qubits, M = 2^n_qubits; Pauli order, normalisation and element words are those of fbx_rb_simulate.
+ *
+ * Inputs.  depths [S]: the depth of the sequences q = i K .. i K + K - 1 (depth index i, repetition s = q - i K: the order of
+ * fbx/randomized_benchmarking.py generate_rb_sequences_batch), counted as generate_rb_sequence counts it; a HOST array in both
+ * forms (its S <= 256 numbers travel with the launch).  K: the sequences per depth.  mode: FBX_RB_STANDARD -- self-inverting
+ * sequences measured in Z on every qubit -- or FBX_RB_UNITARITY -- sequences without the inverse, every Pauli measured.
+ * interleaved_elem: as in fbx_rb_sequences, FBX_CLIFFORD_NONE for a plain run.  noise_ptms [E][G][D][D]: G = 1, or 2 with an
+ * interleaved element; matrix 0 follows every random Clifford and the inverse, matrix 1 the interleaved element.  prep [D] or NULL
+ * (|0..0>), shared by the batch, as in fbx_rb_simulate.  flips [E][n_qubits][2] or NULL: [q][0] = P(read 1 | 0), [q][1] =
+ * P(read 0 | 1) of qubit q, independent per bit, as in fbx_tomo_simulate.  n_shots: the shots of every sequence and basis; 0 = the
+ * exact expectations, no shots.  seed, first_item: as in fbx_tomo_simulate; gid = first_item + e.
+ *
+ * Outputs, each may be NULL, not all.  NB bases are measured and C Paulis estimated per sequence:
+ *   FBX_RB_STANDARD    NB = 1 (Z on every qubit), C = M - 1: the I/Z products in the order Z (n = 1) and IZ, ZI, ZZ (n = 2)
+ *   FBX_RB_UNITARITY   NB = 3^n_qubits, C = D - 1: column c is the Pauli with index c + 1.  Basis index in base 3, digits X, Y, Z
+ *                      = 0, 1, 2, qubit 0 most significant.
+ *   vec_out    [E][S K][D] double         the exact final Pauli vectors
+ *   prob_out   [E][S K][NB][M] double     the outcome distributions, flips included, unclamped; outcome o = the measured bits,
+ *                                         qubit 0 most significant, bit value 1 = eigenvalue -1
+ *   hist_out   [E][S K][NB][M] uint32     the counted outcomes (n_shots >= 1 only)
+ *   expect_out, std_err_out [E][S K][C] double          status_out [E] int32
+ *
+ * Per experiment e and sequence q:
+ *  1. SEQUENCE.  The elements are exactly those fbx_rb_sequences writes for sequence b = q under the seed (seed + gid) mod 2^64,
+ *     with the same interleaved_elem, self_inverting = 1 (FBX_RB_STANDARD) or 0 (FBX_RB_UNITARITY) and the length of the depth:
+ *     depth - 1 draws (each followed by the interleaved element, if any) and the inverse, or `depth` draws.  The draws are those
+ *     of its stream (Philox4x32-10, key = that seed, counter (q low, q high, draw, 0x52420000 + attempt)).
+ *  2. FINAL VECTOR.  From prep, each element's signed permutation and then its noise matrix, a row being one chain of fused
+ *     multiply-adds in ascending column order from 0.0: vec_out equals fbx_rb_simulate's out on those sequences bit for bit.
+ *  3. DISTRIBUTION.  For the basis (P_0[, P_1]) and the final vector v, outcome o has
+ *         p(o) = 2^-n sum_T (-1)^|o & T| v[P_T],
+ *     T over the subsets of the qubits, P_T the product of the basis' Paulis on T, v[P_{}] = v_I (1 for a trace-preserving
+ *     map).  Then per bit the confusion matrix of its qubit's flips, exactly as step 2 of fbx_tomo_simulate_grouped.
+ *  4. SHOTS.  c_o = the running sum of max(p(o'), 0) in outcome order; thr_o = floor(c_o / c_last 2^32) for every outcome but
+ *     the last.  Shot s of n_shots reads word s & 3 of the Philox4x32-10 block with counter (gid low, gid high, q NB + basis,
+ *     s >> 2) and key (seed low ^ 0x52424151, seed high); the tag "RBAQ" keeps the stream apart from every other simulator's
+ *     under one seed.  The outcome of a word is the number of thresholds <= the word; hist_out counts the outcomes.
+ *  5. EXPECTATIONS.  Every Pauli is read from exactly ONE basis: the one that measures its non-identity factors and Z on
+ *     every qubit where it has the identity (IX from ZX, YI from YZ).  With n_odd the shots of that basis' histogram whose bits
+ *     on the Pauli's support have odd parity, mean = ((N - n_odd) - n_odd) / N and std_err = sqrt((1 - mean^2) / N), without
+ *     fused multiply-adds (the moments of fbx_rpe_simulate).  In FBX_RB_STANDARD IZ, ZI and ZZ come from the same shots: in
+ *     every shot the ZZ value is the product of the other two, which is what fbx_rb_survival's covariance term assumes.
+ *     n_shots = 0: expect_out holds the exact components of the final vector and std_err_out 0.
+ * A value depends on (seed, gid, q, basis), the experiment's inputs and n_shots only: not on E, the experiment's position in the
+ * batch or the launch shape; a batch is cut with first_item.
+ *
+ * A poisoned experiment -- a non-finite entry of its matrices or of prep, a flip outside [0, 1] or NaN, or a distribution whose
+ * c_last is not a positive finite number (an all-zero matrix, a product that overflows) -- gets status 1, NaN in every double
+ * output and 0 in hist_out, for ALL its sequences; its neighbours are bit-identical to a clean call.
+ * n_qubits >= 3 and S > 256: FBX_ERR_UNSUPPORTED.  FBX_ERR_BAD_ARG before any buffer is touched: n_qubits < 1, E < 0, S < 1,
+ * K < 1, an unknown mode, NULL depths, a depth below 2 (FBX_RB_STANDARD) or 1 (FBX_RB_UNITARITY), an interleaved element that is
+ * no valid word or comes with FBX_RB_UNITARITY, G other than 1 (plain) / 2 (interleaved), first_item < 0, n_shots outside
+ * 0 .. 2^31 - 1, S K NB >= 2^32, every output NULL, hist_out with n_shots = 0, NULL noise_ptms.  E == 0: nothing is done.
+ * The _dev form enqueues on the calling thread's stream and does not synchronise. */
+#define FBX_RB_STANDARD   0
+#define FBX_RB_UNITARITY  1
+int fbx_rb_acquire(int n_qubits, int64_t E, int S, const int32_t* depths, int K, int mode, uint32_t interleaved_elem, int G,
+                   const double* noise_ptms, const double* prep, const double* flips, int64_t n_shots, uint64_t seed,
+                   int64_t first_item, double* vec_out, double* prob_out, uint32_t* hist_out, double* expect_out,
+                   double* std_err_out, int32_t* status_out);
+int fbx_rb_acquire_dev(int n_qubits, int64_t E, int S, const int32_t* depths, int K, int mode, uint32_t interleaved_elem, int G,
+                       const double* d_noise_ptms, const double* d_prep, const double* d_flips, int64_t n_shots, uint64_t seed,
+                       int64_t first_item, double* d_vec_out, double* d_prob_out, uint32_t* d_hist_out, double* d_expect_out,
+                       double* d_std_err_out, int32_t* d_status_out);
+
+/* values [E][S][K][C] -> mean_out [E][S][C], the mean over the K sequences of a depth, and std_err_out [E][S][C], the standard
+ * error of that mean: sqrt(var(ddof = 1) / K) for K > 1; for K = 1 the sequence's own standard error seq_std_errs [E][S][C], or 0
+ * when that is NULL (it is not read for K > 1).  One lane per output cell sums in ascending s, without fused multiply-adds: a
+ * result depends on its K values only.  C is free: the expectations of fbx_rb_acquire (C = M - 1 or D - 1), survival
+ * probabilities or purities (C = 1).  Each output may be NULL, not both.  The _dev form enqueues on the calling thread's stream. */
+int fbx_rb_depth_means(int64_t E, int S, int K, int C, const double* values, const double* seq_std_errs, double* mean_out,
+                       double* std_err_out);
+int fbx_rb_depth_means_dev(int64_t E, int S, int K, int C, const double* d_values, const double* d_seq_std_errs, double* d_mean_out,
+                           double* d_std_err_out);
+
 /* ---------------------------------------------------------------- Clifford circuits and direct fidelity estimation, 1..64 qubits
  * The experiment generators of direct_fidelity_estimation.py:15-182 and the noisy expectations of their settings for a Clifford
  * circuit with Pauli noise, exact in the Heisenberg picture: the observable walks backwards through the circuit as a signed Pauli

@@ -145,6 +145,40 @@ def build_solver_test(verbose=True):
     return out
 
 
+def build_reductions_test(verbose=True):
+    """libfbx_oldred.so: the product sources with the lean wave reductions of the one-wave PGDB kernels (csrc/fbx_common.hpp:
+    wave_sum_lean / wave_sum_n / wave_max_lean) mapped back to wave_sum / wave_max (-DFBX_WAVE_REDUCE_PARENT) -- only loaded by
+    tests/test_pgdb_reductions_ab_gpu.py, which requires bit-identical results.  Only fbx_pgdb.hip differs."""
+    out = os.path.join(HERE, "libfbx_oldred.so")
+    lib = build(verbose=verbose)
+    src = os.path.join(CSRC, "fbx_pgdb.hip")
+    if os.path.exists(out) and os.path.getmtime(out) >= os.path.getmtime(lib):
+        return out
+    obj = os.path.join(HERE, "build", "fbx_pgdb.hip.oldred.o")
+    cmd = [HIPCC] + FLAGS + file_flags(src) + ["-DFBX_WAVE_REDUCE_PARENT", "-c", src, "-o", obj]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    objs = [obj] + [os.path.join(HERE, "build", os.path.basename(s) + ".o") for s in sources() if s != src]
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + MAP, "-ldl"] + objs + ["-o", out])
+    return out
+
+
+def build_wave_reduce_test(verbose=True):
+    """libfbx_wavered.so: csrc/test/fbx_wave_reduce_test.hip alone -- one wavefront that runs the wave reductions of
+    csrc/fbx_common.hpp on the caller's numbers; only loaded by tests/test_wave_reduce_gpu.py."""
+    out = os.path.join(HERE, "libfbx_wavered.so")
+    src = os.path.join(CSRC, "test", "fbx_wave_reduce_test.hip")
+    deps = [src, os.path.join(CSRC, "fbx_common.hpp"), os.path.join(HERE, "..", "include", "fbx.h")]
+    if os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(p) for p in deps):
+        return out
+    cmd = [HIPCC] + FLAGS + ["-shared", src, "-o", out]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return out
+
+
 def build_variant(name, extra_flags, verbose=True):
     """Experiment builds: libfbx_<name>.so = the product objects with fbx_pgdb.hip and fbx_pgdb_lean.hip recompiled with extra
     -D flags (e.g. `python build.py --variant nosmall -DFBX_NO_SMALL_STEP`).  Not shipped, not loaded by tests."""
@@ -175,5 +209,7 @@ if __name__ == "__main__":
         build_guard_test()
         build_barrier_test()
         build_solver_test()
+        build_reductions_test()
+        build_wave_reduce_test()
     else:
         build(force="--force" in sys.argv, profile="--profile" in sys.argv)

@@ -27,6 +27,11 @@ struct ChoiLds {
     static constexpr int LDpt = LEAN ? D : LD;     // leading dimension of the partial-trace staging
     static constexpr bool lean = LEAN;
     static constexpr bool two_workers = TWO_WORKERS && D == 16;
+    // The same tag (for every D) selects the lean wave reductions of fbx_common.hpp (wave_sum_lean / wave_sum_n) in the projections
+    // of this work area: the one-wave PGDB body reaches every one of them with all 64 lanes active (its workgroup is one full
+    // wavefront, every branch around a projection is on a wave-uniform value, and the `lane < ...` guards close in front of
+    // the reductions).  Same tree, same operands: same bits.  Every other work area keeps wave_sum().
+    static constexpr bool lean_reduce = TWO_WORKERS;
     // Every non-LEAN work area belongs to a kernel that runs the projection as ONE wavefront per SIMD or close to it (the
     // one-wave PGDB kernels, proj_choi_kernel): nobody hides that wavefront's LDS round trips, so its projections request the
     // operands of a whole step together (`batched`: the eigenvalue terms of the reconstruction recon_terms per trip, the
@@ -95,7 +100,9 @@ __device__ Blk proj_cp_blk(const Blk& x, LdsT& L, int lane, int& sweeps, bool wa
     // 16 x 16 solver the test rides on its first off-norm reduction (one extra wave reduction here, which
     // overlaps the matrix-core products).
     double hn2 = -1.0;
-    if (warm && check_basis) hn2 = uniform(wave_sum(blk_norm2(h)));
+    if (warm && check_basis) {
+        if constexpr (LdsT::lean_reduce) hn2 = uniform(wave_sum_lean(blk_norm2(h))); else hn2 = uniform(wave_sum(blk_norm2(h)));
+    }
     if (warm) {
         if constexpr (D == 16) jacobi_rotate_into_basis_mfma16(L.Ms, L.Vs, lane);
         else
@@ -115,7 +122,7 @@ __device__ Blk proj_cp_blk(const Blk& x, LdsT& L, int lane, int& sweeps, bool wa
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { const cplx v = L.Ms[e * PS + lane]; mn2 = fma(v.re, v.re, fma(v.im, v.im, mn2)); }
             }
-            mn2 = uniform(wave_sum(mn2));
+            if constexpr (LdsT::lean_reduce) mn2 = uniform(wave_sum_lean(mn2)); else mn2 = uniform(wave_sum(mn2));
             sw = (fabs(mn2 - hn2) <= FBX_BASIS_NORM_TOL * hn2) ? jacobi_eigh_lds<D>(L.Ms, L.Vs, L.rec, lane, false) : -1;
         } else sw = jacobi_eigh_lds<D>(L.Ms, L.Vs, L.rec, lane, !warm);
     }
@@ -445,8 +452,14 @@ __device__ Blk proj_physical_blk(const Blk& x, bool trace_preserving, LdsT& L, i
         double i1r, i1i, i2r, i2i;
         blk_dotc(old_tp, blk_sub(new_state, last_state), i1r, i1i);
         blk_dotc(old_cp, blk_sub(cp, last_cp), i2r, i2i);
-        s1 = wave_sum(s1); s2 = wave_sum(s2);
-        i1r = wave_sum(i1r); i1i = wave_sum(i1i); i2r = wave_sum(i2r); i2i = wave_sum(i2i);
+        if constexpr (LdsT::lean_reduce) {       // the six sums level by level (fbx_common.hpp wave_sum_n): one tree each, as before
+            double r6[6] = {s1, s2, i1r, i1i, i2r, i2i};
+            wave_sum_n(r6);
+            s1 = r6[0]; s2 = r6[1]; i1r = r6[2]; i1i = r6[3]; i2r = r6[4]; i2i = r6[5];
+        } else {
+            s1 = wave_sum(s1); s2 = wave_sum(s2);
+            i1r = wave_sum(i1r); i1i = wave_sum(i1i); i2r = wave_sum(i2r); i2i = wave_sum(i2i);
+        }
         // |z| = |z|^2 rsqrt(|z|^2): the IEEE sqrt expansion is ~40 instructions, twice per iteration
         const double a1 = i1r * i1r + i1i * i1i, a2 = i2r * i2r + i2i * i2i;
         const double m1 = a1 > 1e-300 ? a1 * fast_rsqrt(a1) : 0.0, m2 = a2 > 1e-300 ? a2 * fast_rsqrt(a2) : 0.0;

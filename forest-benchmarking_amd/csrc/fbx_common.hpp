@@ -301,6 +301,78 @@ __device__ __forceinline__ double wave_max(double v) {
     v = fmax(v, dpp_permute<0x140>(v));
     return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
 }
+// The same reductions for code that reaches them with ALL 64 LANES ACTIVE under wave-uniform control flow (the one-wave PGDB
+// kernels: fbx_pgdb_body.hpp !LEAN, and what fbx_choi.hpp / fbx_eigh.hpp instantiate for them).  wave_sum() above costs a lone
+// wavefront ~44 issue slots of one dependent chain: per DPP level two v_mov_b32 that materialise the zero `old` operand, the
+// s_nop of the VALU-write -> DPP-read hazard, two v_mov_b32_dpp and the add; then eight v_readlane_b32, four moves, three adds.
+// Here (a) the DPP moves ask for bound_ctrl -- the four permutations give every lane a source, so `old` is never used and is not
+// materialised; (b) the four row sums meet through two more DPP levels, row_bcast:15 (lane 15 of a row to the row above it:
+// lane 31 = r0 + r1, lane 63 = r2 + r3) and row_bcast:31 (lane 31 to the upper half: lane 63 = (r0 + r1) + (r2 + r3)), and ONE
+// readlane pair of lane 63: 26 slots.  That is wave_sum's tree with wave_sum's operands in wave_sum's order (`partner + own`;
+// lanes without a source add the 0 of bound_ctrl and are never read): the same bits, NaN-ness included.  With a lane switched
+// off the row sums would not pass through lanes 15 / 31 / 47 -- every other caller keeps wave_sum().
+// -DFBX_WAVE_REDUCE_PARENT maps all of it back to wave_sum / wave_max (libfbx_oldred.so, tests/test_pgdb_reductions_ab_gpu.py).
+template <int CTRL>
+__device__ __forceinline__ double dpp_permute_bc(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+// one level of the tree for N values: the N partners first, then the N adds -- the hazard wait and the fp64 latency of one
+// value's chain lie behind the other values' instructions
+template <int CTRL, int N>
+__device__ __forceinline__ void wave_sum_level(double (&v)[N]) {
+    double p[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) p[i] = dpp_permute_bc<CTRL>(v[i]);
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = p[i] + v[i];
+}
+// N sums level by level: every value sees the tree of wave_sum_lean() (N = 1)
+template <int N>
+__device__ __forceinline__ void wave_sum_n(double (&v)[N]) {
+#if defined(FBX_WAVE_REDUCE_PARENT)
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = wave_sum(v[i]);
+#else
+    wave_sum_level<0xB1>(v);            // quad_perm [1,0,3,2]
+    wave_sum_level<0x4E>(v);            // quad_perm [2,3,0,1]
+    wave_sum_level<0x141>(v);           // row_half_mirror
+    wave_sum_level<0x140>(v);           // row_mirror: every lane holds the sum of its row of 16
+    wave_sum_level<0x142>(v);           // row_bcast:15: lane 31 holds r0 + r1, lane 63 r2 + r3
+    wave_sum_level<0x143>(v);           // row_bcast:31: lane 63 holds (r0 + r1) + (r2 + r3)
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = readlane_f64(v[i], 63);
+#endif
+}
+__device__ __forceinline__ double wave_sum_lean(double v) {
+    double a[1] = {v};
+    wave_sum_n(a);
+    return a[0];
+}
+// the form chosen by a compile-time tag (a body shared by the one-wave and the two-waves kernels)
+template <bool LEAN_FORM>
+__device__ __forceinline__ double wave_sum_as(double v) {
+    if constexpr (LEAN_FORM) return wave_sum_lean(v); else return wave_sum(v);
+}
+// (the serial form of wave_sum_n: instantiations that would pay for the N live partners with scratch)
+template <int N>
+__device__ __forceinline__ void wave_sum_each(double (&v)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = wave_sum_lean(v[i]);
+}
+// wave_max's tree as written (and so its +-0 behaviour), the DPP moves with bound_ctrl
+__device__ __forceinline__ double wave_max_lean(double v) {
+#if defined(FBX_WAVE_REDUCE_PARENT)
+    return wave_max(v);
+#else
+    v = fmax(v, dpp_permute_bc<0xB1>(v));
+    v = fmax(v, dpp_permute_bc<0x4E>(v));
+    v = fmax(v, dpp_permute_bc<0x141>(v));
+    v = fmax(v, dpp_permute_bc<0x140>(v));
+    return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
+#endif
+}
 // sum over all NT threads of the workgroup (every thread receives the same total, summed in one
 // fixed order); `red` is NT/64 doubles of LDS scratch, unused for single-wave workgroups
 template <int NT>

@@ -435,8 +435,14 @@ static __device__ int run(cplx* __restrict__ Ms, cplx* __restrict__ Vs, int lane
             double o2, dg = 0.0;
             if (diag) { o2 = x1.re * x1.re + x1.im * x1.im; dg = x0.re * x0.re + dP_ * dP_; }   // (0,1) entry; a, d
             else o2 = (x0.re * x0.re + x0.im * x0.im) + (y0.re * y0.re + y0.im * y0.im);
-            o2 = 2.0 * uniform(wave_sum(o2));
-            if (sweep == 0) n2 = o2 + uniform(wave_sum(dg));
+            // The lean reductions of fbx_common.hpp (same tree, same bits), the first sweep's pair level by level: this form of the
+            // solver is only instantiated for the one-wave PGDB body (ChoiLds<..., TWO_WORKERS>), a full wavefront, and the
+            // sweep loop runs on wave-uniform values -- all 64 lanes are here
+            if (sweep == 0) {
+                double r2[2] = {o2, dg};
+                wave_sum_n(r2);
+                o2 = 2.0 * uniform(r2[0]); n2 = o2 + uniform(r2[1]);
+            } else o2 = 2.0 * uniform(wave_sum_lean(o2));
             if (sweep == 0 && expect_n2 >= 0.0 && !(fabs(n2 - expect_n2) <= FBX_BASIS_NORM_TOL * expect_n2)) return -1;
             if (!(o2 > tol2 * n2)) break;
         }

@@ -251,6 +251,11 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
     // lane, the 16-state one a trip and a single state; the two-waves kernel has no registers for more than one
     constexpr int TABLE_U = LEAN ? 1 : 3;
     int lane = threadIdx.x & 63;
+    // Wave reductions.  The one-wave body is one full wavefront, and every reduction below stands under wave-uniform control flow
+    // with the `lane < ...` / `g < m` guards closed in front of it: all 64 lanes reach it, and it takes the lean forms of
+    // fbx_common.hpp (wave_sum_lean / wave_sum_n / wave_max_lean: the tree of wave_sum on the same operands -- same bits -- in 26
+    // instead of 44 issue slots).  The two-waves body keeps wave_sum / wave_max and its code.
+    // (wave_sum_as<true>() is wave_sum_lean(), wave_sum_as<false>() is wave_sum())
     const long long item = item_;
     const int m = des.m, S = des.S;
     const int nslots = STREAM ? (m + 63) / 64 : MAXJ;       // outcome slots per lane (a compile-time constant unless STREAM)
@@ -322,7 +327,7 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
                 tot += c;
             }
         }
-        tot = uniform(wave_sum(tot));
+        tot = uniform(wave_sum_as<!LEAN>(tot));
 #pragma unroll
         for (int j = 0; j < MAXJ; ++j) {
             if constexpr (LEAN) {
@@ -454,7 +459,7 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
                     acc = slot_valid(j) ? next : acc;
                 }
             }
-            return uniform(wave_sum(acc));
+            return uniform(wave_sum_lean(acc));
         }
 #pragma unroll SLOT_UNROLL
         for (int j = 0; j < (STREAM ? nslots : MAXJ); ++j) {
@@ -470,7 +475,7 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
                 acc -= np_ * fast_log_pos(pp) + nm_ * fast_log_pos(pm);
             }
         }
-        return uniform(wave_sum(acc));
+        return uniform(wave_sum_as<!LEAN>(acc));
     };
 
     // ---- initial estimate I_D / d (tomography.py:564) in block layout
@@ -664,7 +669,7 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
         }
         double ipr, ipi;
         blk_dotc(upd, grad, ipr, ipi);
-        ipr = uniform(wave_sum(ipr));
+        ipr = uniform(wave_sum_as<!LEAN>(ipr));
         PH_STOP(pc, 2);
 
         // ---- prediction tables for the line search
@@ -708,7 +713,7 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
             if (__ballot(exact(up_, ep_))) near_clip |= STREAM ? 1u : 1u << (2 * j);
             if (__ballot(exact(um_, em_))) near_clip |= STREAM ? 1u : 2u << (2 * j);
         }
-        rmax = uniform(wave_max(rmax));
+        if constexpr (LEAN) rmax = uniform(wave_max(rmax)); else rmax = uniform(wave_max_lean(rmax));
         const bool small_ok = rmax == rmax;
         // The near-clip outcomes are few and scattered over lanes and slots: they are compacted into
         // one entry per lane (through LDS -- the Jacobi work area is idle during the line search), so
@@ -809,13 +814,20 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
                         for (int k = 0; k < NS; ++k) { Sk[k] += t; t *= x; }
                     }
                 }
+                // the sixteen sums level by level (SLOT_BATCH; the sixteen-slot instantiation has no registers for sixteen partners)
+                if constexpr (LEAN) {
 #pragma unroll
-                for (int k = 0; k < NS; ++k) Sk[k] = uniform(wave_sum(Sk[k])) * ((k & 1) ? -1.0 : 1.0) / (double)(k + 1);
+                    for (int k = 0; k < NS; ++k) Sk[k] = uniform(wave_sum(Sk[k])) * ((k & 1) ? -1.0 : 1.0) / (double)(k + 1);
+                } else {
+                    if constexpr (SLOT_BATCH) wave_sum_n(Sk); else wave_sum_each(Sk);
+#pragma unroll
+                    for (int k = 0; k < NS; ++k) Sk[k] = uniform(Sk[k]) * ((k & 1) ? -1.0 : 1.0) / (double)(k + 1);
+                }
                 have_sums = true; ++ls_sums;
             }
             double acc = series(alpha);
             if (near_clip)                   // the listed outcomes: exact difference of clipped logs
-                acc += uniform(wave_sum(clip_n * clipped_log(fma(alpha, clip_pu, clip_pe)) - clip_base));
+                acc += uniform(wave_sum_as<!LEAN>(clip_n * clipped_log(fma(alpha, clip_pu, clip_pe)) - clip_base));
             ls_exact = true; ls_diff = -acc;
             return old_cost - acc;
         };
@@ -860,7 +872,7 @@ pgdb_body(char* smem, long long item_, const DesignDev& des, long long B, const 
         }
         PH_STOP(pc, 5);
         est = blk_axpy(est, alpha, upd);            // tomography.py:588
-        outer_step = alpha * sqrt(uniform(wave_sum(blk_norm2(upd))));
+        outer_step = alpha * sqrt(uniform(wave_sum_as<!LEAN>(blk_norm2(upd))));
         if (trace_out && iters < trace_iters && lane == 0) {     // Dykstra iterations and halvings of THIS outer iteration
             int* tr = trace_out + ((size_t)item * trace_iters + iters) * 2;
             tr[0] = dyk - dyk_before; tr[1] = backtracks - bt_before;

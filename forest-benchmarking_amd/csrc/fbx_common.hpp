@@ -10,6 +10,7 @@
 #include <map>
 #include <mutex>
 #include "../../include/fbx.h"
+#include "fbx_pgdb_call.hpp"
 
 namespace fbx {
 
@@ -51,27 +52,17 @@ int ordering_events(int n, hipEvent_t** out);            // >= n reusable events
 bool host_pointer_is_pinned(const void* p, size_t bytes);   // the whole range is page-locked (fbx_host_alloc / hipHostMalloc / hipHostRegister)
 long long option_pgdb_host_chunk();                      // fbx_set_option("pgdb_host_chunk")
 
-// per-call arguments of fbx_pgdb_process_ex[_dev] beyond those of fbx_pgdb_process
-struct PgdbExtras {
-    double eig_rel_tol = -1.0;     // < 0: the process default (fbx_set_option)
-    int32_t* trace = nullptr;      // DEVICE [B][trace_iters][2]: Dykstra iterations and halvings of every outer iteration
-    int trace_iters = 0;
-    // set by the pipelined host-pointer entry point only: the stream a stage's kernels go to, and the stage's share of
-    // the per-item workspace: `ws_items` slots in all, this stage's start at `ws_offset` (stages on different streams get disjoint ranges)
-    hipStream_t launch_stream = nullptr;
-    int64_t ws_items = 0, ws_offset = 0;
-    int64_t total_batch = 0;       // size of the caller's whole batch when this launch is one stage of it: kernels are chosen by IT,
-                                   // so that a result never depends on how a batch was cut into stages
-};
-
 // Named grow-only device workspaces of the calling thread (kept between calls; released by
 // fbx_release_workspace).  A workspace only ever serves kernels on the calling thread's stream, so
 // growing it (stream sync + hipFree + hipMalloc) cannot pull memory from under another thread's kernel.
-enum WorkspaceSlot { WS_PGDB_BASIS = 0, WS_PGDB3_BASIS = 1, WS_SWEEP_REF = 2, WS_COMM = 3, WS_CONVERT = 4, WS_PGDB1_COUNTER = 5, WS_PGDB1_BINS = 6, WS_PGDB_PIECES = 7, WS_DIAMOND = 8, WS_CHERNOFF = 9, WS_FIT = 10, WS_QV_WIDE = 11, WS_SAMPLE_WIDE = 12, WS_QV_NOISY = 13, WS_COUNT = 14 };
+enum WorkspaceSlot { WS_PGDB_BASIS = 0, WS_PGDB3_BASIS = 1, WS_SWEEP_REF = 2, WS_COMM = 3, WS_CONVERT = 4, WS_PGDB1_COUNTER = 5, WS_PGDB1_BINS = 6, WS_PGDB_PIECES = 7, WS_DIAMOND = 8, WS_CHERNOFF = 9, WS_FIT = 10, WS_QV_WIDE = 11, WS_SAMPLE_WIDE = 12, WS_QV_NOISY = 13, WS_PGDB3_ETA = 14, WS_COUNT = 15 };
 int workspace(WorkspaceSlot slot, size_t bytes, void** out);
 // staging blocks of the host-pointer entry points: taken from / returned to the calling thread's pool
 int pool_take(size_t bytes, void** out);
 void pool_give(void* p);
+// a small page-locked host scratch of the calling thread (grow-only, allocated on first use, released with the workspaces):
+// the destination of read-backs that must not hold the host until their stream has drained
+int pinned_scratch(size_t bytes, void** out);
 
 #define FBX_HIP(call)                                                          \
     do {                                                                       \
@@ -97,8 +88,9 @@ inline int launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_by
 
 // Device block from the calling thread's pool (no hipMalloc / hipFree per call once the pool is warm); it goes back when the
 // DevBuf goes out of scope, whatever is still queued on it.  Whoever holds one waits for that work first: HostIO below does
-// so on every path, fbx_pgdb_process_ex drains its streams by hand, and the asynchronous `_dev` launchers that keep one as
-// scratch rely on stream order instead (the pool serves one thread, whose next use of the block queues behind theirs).
+// so on every path (fbx_pgdb_process_ex, which also queues on its copy streams, keeps a guard for those next to its HostIO),
+// and the asynchronous `_dev` launchers that keep one as scratch rely on stream order instead (the pool serves one thread,
+// whose next use of the block queues behind theirs).
 struct DevBuf {
     void* p = nullptr;
     ~DevBuf() { if (p) pool_give(p); }

@@ -161,17 +161,27 @@ long long* g_phase_out = nullptr;          // diagnostics builds only: set by fb
 #define FBX_PHASE_OUT(b0) ((long long*)nullptr)
 #endif
 
+// what the kernels of fbx_pgdb.hip / fbx_pgdb_lean.hip get of a call (already cut to the items of one launch)
+static PgdbLaunch pgdb_launch_args(const PgdbCall& s, const DesignDev& dev, int mode) {
+    PgdbLaunch a;
+    a.dev = dev; a.nb = s.B; a.e = s.e; a.c = s.c; a.tp = s.tp; a.mode = mode; a.max_iters = s.max_iters;
+    a.choi = s.choi; a.it = s.it; a.dy = s.dy; a.bt = s.bt; a.cost = s.cost; a.sw = s.sw;
+    a.trace = s.trace; a.trace_iters = s.trace_iters;
+    return a;
+}
+
 template <int NQ, int MAXJ>
-static int launch_pgdb(const fbx_design* des, int64_t B, const double* e, const double* c, int tp,
-                       int mode, int max_iters, double* choi, int32_t* it, int32_t* dy, int32_t* bt,
-                       double* cost, int32_t* sw, const PgdbExtras& ex) {
-    const bool ls_reference = (mode & FBX_MODE_LS_REFERENCE) != 0;      // per call: the line search taken literally (include/fbx.h)
-    mode &= 0xff;
+static int launch_pgdb(const PgdbCall& call) {
+    const fbx_design* des = call.des;
+    const int64_t B = call.B;
+    const int max_iters = call.max_iters;
+    const bool ls_reference = (call.mode & FBX_MODE_LS_REFERENCE) != 0;      // per call: the line search taken literally (include/fbx.h)
+    const int mode = call.mode & 0xff;
     // batches that put several reconstructions on a SIMD take the lean two-waves-per-SIMD kernel (2 qubits)
     // MAXJ = 0: the STREAMED instantiation (fbx_pgdb_body.hpp) -- any number of settings, outcome slots read from HBM / L2
     constexpr bool STREAM = MAXJ == 0;
     const int slots = STREAM ? (des->dev.m + 63) / 64 : MAXJ;            // outcome slots per lane
-    bool lean = STREAM || (NQ == 2 && (ex.total_batch > B ? ex.total_batch : B) >= FBX_LEAN_MIN_BATCH);
+    bool lean = STREAM || (NQ == 2 && (call.total_batch > B ? call.total_batch : B) >= FBX_LEAN_MIN_BATCH);
     size_t lds = STREAM ? pgdb_stream_lds(NQ, des->dev.S) : PgdbLds<NQ, false>::bytes(des->dev.S, 64 * MAXJ);      // Ln has one row pair per outcome slot of the kernel
     if constexpr (NQ == 2 && !STREAM) {
         lean = lean && pgdb_lean_eligible(des->dev.S);
@@ -197,7 +207,7 @@ static int launch_pgdb(const fbx_design* des, int64_t B, const double* e, const 
     const size_t counts_item = lean ? sizeof(double) * 2 * (size_t)slots * 64 : 0;      // normalised counts of the lean kernel (fbx_pgdb_body.hpp)
     int64_t CHUNK = 65536;
     char* wsp = nullptr;
-    int64_t ws_items = ex.ws_items > 0 ? ex.ws_items : (B < CHUNK ? B : CHUNK);
+    int64_t ws_items = call.ws_items > 0 ? call.ws_items : (B < CHUNK ? B : CHUNK);
     if (basis_item + counts_item) {
         for (;;) {
             // the pipelined host entry point says how many slots its stages need between them; everybody else min(B, CHUNK)
@@ -206,27 +216,22 @@ static int launch_pgdb(const fbx_design* des, int64_t B, const double* e, const 
             const int rc = workspace(WS_PGDB_BASIS, total, &w);
             if (rc == FBX_OK) { wsp = (char*)w; break; }
             // (the streamed instantiations keep 16 B x m of normalised counts per slot: a huge merged design may need fewer slots than 1024)
-            if (rc != FBX_ERR_NOMEM || ex.ws_items > 0 || ws_items <= (STREAM ? 1 : 1024)) return rc;
+            if (rc != FBX_ERR_NOMEM || call.ws_items > 0 || ws_items <= (STREAM ? 1 : 1024)) return rc;
             (void)hipGetLastError();
             ws_items /= 2; CHUNK = ws_items;
         }
     }
     const int64_t n_slots = ws_items;
-    cplx* basis = basis_item ? (cplx*)wsp + (size_t)ex.ws_offset * D * D * BASIS_CAP : nullptr;
-    double* ncounts = counts_item ? (double*)(wsp + basis_item * (size_t)n_slots) + (size_t)ex.ws_offset * 2 * (size_t)slots * 64 : nullptr;
-    const size_t m = des->dev.m;
+    cplx* basis = basis_item ? (cplx*)wsp + (size_t)call.ws_offset * D * D * BASIS_CAP : nullptr;
+    double* ncounts = counts_item ? (double*)(wsp + basis_item * (size_t)n_slots) + (size_t)call.ws_offset * 2 * (size_t)slots * 64 : nullptr;
     DesignDev dev = des->dev;
-    dev.eig_rel_tol = ex.eig_rel_tol >= 0.0 ? ex.eig_rel_tol : option_pgdb_eig_rel_tol(NQ);     // per call, else the process default
+    dev.eig_rel_tol = call.eig_rel_tol >= 0.0 ? call.eig_rel_tol : option_pgdb_eig_rel_tol(NQ);     // per call, else the process default
     dev.ls_reference = ls_reference ? 1 : 0;
-    hipStream_t st = ex.launch_stream ? ex.launch_stream : stream();
+    hipStream_t st = call.launch_stream ? call.launch_stream : stream();
     for (int64_t b0 = 0; b0 < B; b0 += CHUNK) {
         const int64_t nb = B - b0 < CHUNK ? B - b0 : CHUNK;
-        PgdbLaunch a;
-        a.dev = dev; a.nb = nb; a.e = e + b0 * m; a.c = c + b0 * m; a.tp = tp; a.mode = mode; a.max_iters = max_iters;
-        a.choi = choi + b0 * D * D * 2; a.it = it ? it + b0 : nullptr; a.dy = dy ? dy + b0 : nullptr; a.bt = bt ? bt + b0 : nullptr;
-        a.cost = cost ? cost + b0 : nullptr; a.sw = sw ? sw + 4 * b0 : nullptr; a.phase = FBX_PHASE_OUT(b0); a.basis = basis;
-        a.basis_cap = BASIS_CAP; a.ncounts = ncounts; a.trace = ex.trace ? ex.trace + (size_t)b0 * ex.trace_iters * 2 : nullptr;
-        a.trace_iters = ex.trace_iters;
+        PgdbLaunch a = pgdb_launch_args(call.slice(b0, nb), dev, mode);
+        a.phase = FBX_PHASE_OUT(b0); a.basis = basis; a.basis_cap = BASIS_CAP; a.ncounts = ncounts;
         // more than one reconstruction per SIMD on the one-wave kernel: in pieces too -- except single-qubit batches to convergence,
         // whose outer iterations last microseconds (a piece's set-up and hand-over then cost what the tail saves: 8000 Pauli
         // experiments 8.6 -> 10.3 ms, while 100 fixed iterations of the SIC design gain 25-35 %; scripts/pieces_time_1q.py)
@@ -262,9 +267,9 @@ static int launch_pgdb(const fbx_design* des, int64_t B, const double* e, const 
                     void* w = nullptr;
                     const size_t fbytes = (sizeof(int) * (size_t)n_slots + 255) & ~(size_t)255;
                     if (workspace(WS_PGDB_PIECES, 512 + fbytes + sizeof(double) * PGDB_REC * (size_t)n_slots, &w) == FBX_OK) {
-                        a.pieces = pieces; a.queue = (int*)w + (ex.ws_offset ? 64 : 0);
-                        a.flags = (int*)((char*)w + 512) + ex.ws_offset;
-                        a.recs = (double*)((char*)w + 512 + fbytes) + (size_t)ex.ws_offset * PGDB_REC;
+                        a.pieces = pieces; a.queue = (int*)w + (call.ws_offset ? 64 : 0);
+                        a.flags = (int*)((char*)w + 512) + call.ws_offset;
+                        a.recs = (double*)((char*)w + 512 + fbytes) + (size_t)call.ws_offset * PGDB_REC;
                     } else (void)hipGetLastError();                  // no room: whole reconstructions
                 }
             }
@@ -293,17 +298,13 @@ static int launch_pgdb(const fbx_design* des, int64_t B, const double* e, const 
     return FBX_OK;
 }
 
-int pgdb3_dispatch(const fbx_design* des, int64_t B, const double* e, const double* c, int tp, int mode,
-                   int max_iters, double* choi, int32_t* it, int32_t* dy, int32_t* bt, double* cost,
-                   int32_t* sw, const PgdbExtras& ex);   // fbx_pgdb3.hip
+int pgdb3_dispatch(const PgdbCall& call);                 // fbx_pgdb3.hip
 bool pgdb1_eligible(const fbx_design* des);               // fbx_pgdb1.hip: the lane-per-item single-qubit kernel
-int pgdb1_dispatch(const fbx_design* des, int64_t B, const double* e, const double* c, int tp, int mode,
-                   int max_iters, double* choi, int32_t* it, int32_t* dy, int32_t* bt, double* cost,
-                   int32_t* sw, const PgdbExtras& ex);
+int pgdb1_dispatch(const PgdbCall& call);
 
-static int pgdb_dispatch(const fbx_design* des, int64_t B, const double* e, const double* c, int tp,
-                         int mode, int max_iters, double* choi, int32_t* it, int32_t* dy,
-                         int32_t* bt, double* cost, int32_t* sw, const PgdbExtras& ex) {
+static int pgdb_dispatch(const PgdbCall& call) {
+    const fbx_design* des = call.des;
+    const int64_t B = call.B;
     const int n = des->dev.n, m = des->dev.m;
     if (n == 1) {
         // Large batches: 64 reconstructions per wavefront, one per lane (fbx_pgdb1.hip; the eigensolver at its full tolerance --
@@ -314,42 +315,155 @@ static int pgdb_dispatch(const fbx_design* des, int64_t B, const double* e, cons
         // design.  fbx_set_option("pgdb_packed_1q", 0 | 2) forces one or the other.
         {
             const int packed = option_pgdb_packed_1q();
-            const int64_t total = ex.total_batch > B ? ex.total_batch : B;
+            const int64_t total = call.total_batch > B ? call.total_batch : B;
             const int64_t from = m <= 12 ? FBX_PACKED_1Q_MIN_BATCH : 2 * FBX_PACKED_1Q_MIN_BATCH;
             // the lane-per-item kernel always solves to full tolerance: a caller who passes an explicit eigensolver tolerance
             // (fbx_pgdb_process_ex, eig_rel_tol >= 0) gets the wavefront-per-item kernel, which honours it, whatever the batch size
             // -- so that an experiment's iterates do not depend on how many neighbours it is batched with (packed == 2 forces
             // the lane-per-item kernel all the same: a test / diagnostics setting, documented in include/fbx.h)
-            const bool explicit_tol = ex.eig_rel_tol >= 0.0 || (mode & FBX_MODE_LS_REFERENCE);      // (the flag too: the wave kernel honours it)
+            const bool explicit_tol = call.eig_rel_tol >= 0.0 || (call.mode & FBX_MODE_LS_REFERENCE);      // (the flag too: the wave kernel honours it)
             if (pgdb1_eligible(des) && (packed == 2 || (packed == 1 && total >= from && !explicit_tol)))
-                return pgdb1_dispatch(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
+                return pgdb1_dispatch(call);
         }
-        if (m <= 64) return launch_pgdb<1, 1>(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
-        if (m <= 256) return launch_pgdb<1, 4>(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
+        if (m <= 64) return launch_pgdb<1, 1>(call);
+        if (m <= 256) return launch_pgdb<1, 4>(call);
         // merged / repeated datasets (the reference takes any result list, tomography.py:494-539): outcome slots streamed from HBM
-        return launch_pgdb<1, 0>(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
+        return launch_pgdb<1, 0>(call);
     } else if (n == 2) {
-        if (m <= 256) return launch_pgdb<2, 4>(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
-        if (m <= 576) return launch_pgdb<2, 9>(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
-        if (m <= 1024) return launch_pgdb<2, 16>(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
-        return launch_pgdb<2, 0>(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
+        if (m <= 256) return launch_pgdb<2, 4>(call);
+        if (m <= 576) return launch_pgdb<2, 9>(call);
+        if (m <= 1024) return launch_pgdb<2, 16>(call);
+        return launch_pgdb<2, 0>(call);
     }
     else if (n == 3) {
-        return pgdb3_dispatch(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
+        return pgdb3_dispatch(call);
     }
     set_error("fbx_pgdb_process: process designs of 1 to 3 qubits");
     return FBX_ERR_UNSUPPORTED;
 }
 
-static int pgdb_check(const fbx_design* des, int64_t B, const void* e, const void* c, int mode,
-                      int max_iters, const void* choi) {
-    { const int rc = check_design(des, "fbx_pgdb_process"); if (rc) return rc; }
-    FBX_REQUIRE(des->dev.kind == FBX_KIND_PROCESS, "fbx_pgdb_process: needs a process design");
-    FBX_REQUIRE(B >= 0, "fbx_pgdb_process: negative batch");
-    FBX_REQUIRE(B == 0 || (e && c && choi), "fbx_pgdb_process: NULL buffer");
-    FBX_REQUIRE((mode & ~FBX_MODE_LS_REFERENCE) == FBX_MODE_CONVERGE || (mode & ~FBX_MODE_LS_REFERENCE) == FBX_MODE_FIXED, "fbx_pgdb_process: bad mode");
-    FBX_REQUIRE(max_iters >= 0, "fbx_pgdb_process: negative max_iters");
+// The checks of fbx_pgdb_process_ex[_dev] on the record its entry point has filled in (pointers all host or all device), and the
+// strides, which it takes from the design
+static int pgdb_prepare(PgdbCall& call) {
+    FBX_TRY(ensure_device());
+    FBX_TRY(check_design(call.des, "fbx_pgdb_process"));
+    FBX_REQUIRE(call.des->dev.kind == FBX_KIND_PROCESS, "fbx_pgdb_process: needs a process design");
+    FBX_REQUIRE(call.B >= 0, "fbx_pgdb_process: negative batch");
+    FBX_REQUIRE(call.B == 0 || (call.e && call.c && call.choi), "fbx_pgdb_process: NULL buffer");
+    const int mode = call.mode & ~FBX_MODE_LS_REFERENCE;
+    FBX_REQUIRE(mode == FBX_MODE_CONVERGE || mode == FBX_MODE_FIXED, "fbx_pgdb_process: bad mode");
+    FBX_REQUIRE(call.max_iters >= 0, "fbx_pgdb_process: negative max_iters");
+    FBX_REQUIRE(call.eig_rel_tol < 0.0 || call.eig_rel_tol <= 1e-3, "fbx_pgdb_process_ex: eig_rel_tol must be negative (default) or in [0, 1e-3]");
+    FBX_REQUIRE(call.eig_rel_tol == call.eig_rel_tol, "fbx_pgdb_process_ex: eig_rel_tol is NaN");
+    FBX_REQUIRE(call.trace_iters >= 0 && (call.trace == nullptr || call.trace_iters > 0), "fbx_pgdb_process_ex: trace_out needs trace_iters > 0");
+    if (!call.trace) call.trace_iters = 0;
+    call.m = (size_t)call.des->dev.m; call.DD = (size_t)call.des->dev.D * call.des->dev.D;
     return FBX_OK;
+}
+
+// The three extra streams of the pipelined path.  Left any other way than through finish(), it waits for them: copies and
+// kernels may be queued there on staging blocks that go back to the thread's pool next (declare it AFTER the HostIO that owns
+// them, which waits for the calling thread's own stream).
+struct PipelineStreams {
+    hipStream_t in = nullptr, out = nullptr, c2 = nullptr;
+    bool queued = false;
+    PipelineStreams() = default;
+    PipelineStreams(const PipelineStreams&) = delete;
+    PipelineStreams& operator=(const PipelineStreams&) = delete;
+    ~PipelineStreams() { drain(); }
+    int acquire() { FBX_TRY(copy_streams(&in, &out, &c2)); queued = true; return FBX_OK; }
+    void drain() {
+        if (queued) { (void)hipStreamSynchronize(in); (void)hipStreamSynchronize(c2); (void)hipStreamSynchronize(out); }
+        queued = false;
+    }
+    // success: the downloads have arrived (the calling thread's stream, already waited for, followed the second compute stream)
+    int finish() {
+        if (!queued) return FBX_OK;
+        FBX_HIP(hipStreamSynchronize(out));
+        FBX_HIP(hipStreamSynchronize(in));
+        queued = false;
+        return FBX_OK;
+    }
+};
+
+// Page-locked caller buffers and more than one stage of work (pgdb_stage_plan, fbx_pgdb_call.hpp, has the reasons): uploads on
+// one stream, the stages' kernels on the calling thread's and the high-priority second compute stream, the Choi matrices down
+// on a fourth.  The small outputs follow on the calling thread's stream (HostIO::finish).
+static int pgdb_host_pipelined(const PgdbCall& host, const PgdbCall& dev, int64_t host_chunk, const PipelineStreams& s) {
+    // (the 3-qubit launcher has one workspace: one compute stream)
+    const PgdbStagePlan plan = pgdb_stage_plan(host.B, host_chunk, host.des->dev.n <= 2);
+    const int nst = (int)plan.stages.size();
+    hipEvent_t* ev = nullptr;
+    FBX_TRY(ordering_events(2 * nst + 1, &ev));
+    // (the staging buffers may still be in use by earlier work of this thread's stream)
+    FBX_HIP(hipEventRecord(ev[2 * nst], stream()));
+    FBX_HIP(hipStreamWaitEvent(s.in, ev[2 * nst], 0));
+    FBX_HIP(hipStreamWaitEvent(s.out, ev[2 * nst], 0));
+    FBX_HIP(hipStreamWaitEvent(s.c2, ev[2 * nst], 0));
+    for (int k = 0; k < nst; ++k) {                        // uploads in stage order, back to back
+        const PgdbStage& stage = plan.stages[k];
+        const PgdbCall h = host.slice(stage.b0, stage.nb), d = dev.slice(stage.b0, stage.nb);
+        const size_t bytes = sizeof(double) * (size_t)h.B * h.m;
+        FBX_HIP(hipMemcpyAsync(const_cast<double*>(d.e), h.e, bytes, hipMemcpyHostToDevice, s.in));
+        FBX_HIP(hipMemcpyAsync(const_cast<double*>(d.c), h.c, bytes, hipMemcpyHostToDevice, s.in));
+        FBX_HIP(hipEventRecord(ev[2 * k], s.in));
+    }
+    for (int k = 0; k < nst; ++k) {
+        const PgdbStage& stage = plan.stages[k];
+        PgdbCall d = dev.slice(stage.b0, stage.nb);
+        d.launch_stream = stage.second ? s.c2 : stream(); d.ws_items = plan.ws_total; d.ws_offset = stage.ws_offset;
+        FBX_HIP(hipStreamWaitEvent(d.launch_stream, ev[2 * k], 0));
+        // (FBX_ERR_NOMEM: the pipeline wants workspace slots for the whole bulk at once; the caller then runs the batch staged)
+        FBX_TRY(pgdb_dispatch(d));
+        FBX_HIP(hipEventRecord(ev[2 * k + 1], d.launch_stream));
+        FBX_HIP(hipStreamWaitEvent(s.out, ev[2 * k + 1], 0));
+        FBX_HIP(hipMemcpyAsync(host.slice(stage.b0, stage.nb).choi, d.choi, sizeof(double) * 2 * (size_t)d.B * d.DD, hipMemcpyDeviceToHost, s.out));
+    }
+    FBX_HIP(hipEventRecord(ev[2 * nst], s.c2));            // the small outputs follow BOTH compute streams
+    FBX_HIP(hipStreamWaitEvent(stream(), ev[2 * nst], 0));
+    return FBX_OK;
+}
+
+// everything on the calling thread's stream, in launches that fit the device (launch_pgdb halves them until the store does)
+static int pgdb_host_staged(const PgdbCall& host, const PgdbCall& dev) {
+    const size_t bytes = sizeof(double) * (size_t)host.B * host.m;
+    FBX_HIP(hipMemcpyAsync(const_cast<double*>(dev.e), host.e, bytes, hipMemcpyHostToDevice, stream()));
+    FBX_HIP(hipMemcpyAsync(const_cast<double*>(dev.c), host.c, bytes, hipMemcpyHostToDevice, stream()));
+    FBX_TRY(pgdb_dispatch(dev));
+    FBX_HIP(hipMemcpyAsync(host.choi, dev.choi, sizeof(double) * 2 * (size_t)host.B * host.DD, hipMemcpyDeviceToHost, stream()));
+    return FBX_OK;
+}
+
+// The host-pointer call (`host`: every pointer a host pointer) on the calling thread's device; host.total_batch = size of the
+// caller's whole batch when this is one device's block of it (kernels are chosen by the whole, so that the split does not
+// change a single bit of any item)
+static int pgdb_process_host(const PgdbCall& host) {
+    const size_t B = (size_t)host.B, n_in = B * host.m, n_choi = 2 * B * host.DD;
+    // `dev`: the same call on device blocks.  Expectations, counts and Choi matrices are moved by whichever path runs (blocks
+    // only: no host pointer given); the small outputs come down in finish() on both.
+    HostIO io;
+    PipelineStreams streams;
+    PgdbCall dev = host;
+    double *de = nullptr, *dc = nullptr;
+    FBX_TRY(io.in<double>(nullptr, n_in, &de)); FBX_TRY(io.in<double>(nullptr, n_in, &dc));
+    dev.e = de; dev.c = dc;
+    FBX_TRY(io.out<double>(nullptr, n_choi, &dev.choi));
+    FBX_TRY(io.out(host.it, B, &dev.it)); FBX_TRY(io.out(host.dy, B, &dev.dy)); FBX_TRY(io.out(host.bt, B, &dev.bt));
+    FBX_TRY(io.out(host.cost, B, &dev.cost)); FBX_TRY(io.out(host.sw, 4 * B, &dev.sw));
+    FBX_TRY(io.out_opt(host.trace, 2 * B * host.trace_iters, &dev.trace));
+    if (dev.trace) FBX_HIP(hipMemsetAsync(dev.trace, 0, sizeof(int32_t) * 2 * B * host.trace_iters, stream()));
+    const int64_t host_chunk = option_pgdb_host_chunk();
+    bool staged = !(host.B > host_chunk && host_pointer_is_pinned(host.e, sizeof(double) * n_in) &&
+                    host_pointer_is_pinned(host.c, sizeof(double) * n_in) && host_pointer_is_pinned(host.choi, sizeof(double) * n_choi));
+    if (!staged) {
+        FBX_TRY(streams.acquire());
+        const int rc = pgdb_host_pipelined(host, dev, host_chunk, streams);
+        if (rc == FBX_ERR_NOMEM) { streams.drain(); (void)hipGetLastError(); staged = true; }
+        else if (rc) return rc;
+    }
+    if (staged) FBX_TRY(pgdb_host_staged(host, dev));
+    FBX_TRY(io.finish());
+    return streams.finish();
 }
 
 }  // namespace fbx
@@ -379,29 +493,19 @@ int fbx_debug_log(const double* x, double* out, int64_t n) {
 }
 #endif
 
-static int check_extras(double eig_rel_tol, const void* trace, int trace_iters) {
-    FBX_REQUIRE(eig_rel_tol < 0.0 || eig_rel_tol <= 1e-3, "fbx_pgdb_process_ex: eig_rel_tol must be negative (default) or in [0, 1e-3]");
-    FBX_REQUIRE(eig_rel_tol == eig_rel_tol, "fbx_pgdb_process_ex: eig_rel_tol is NaN");
-    FBX_REQUIRE(trace_iters >= 0 && (trace == nullptr || trace_iters > 0), "fbx_pgdb_process_ex: trace_out needs trace_iters > 0");
-    return FBX_OK;
-}
-
 int fbx_pgdb_process_ex_dev(const fbx_design* design, int64_t B, const double* d_expect,
                             const double* d_counts, int trace_preserving, int mode, int max_iters,
                             double eig_rel_tol, double* d_choi_out, int32_t* d_iters_out, int32_t* d_dykstra_out,
                             int32_t* d_backtracks_out, double* d_cost_out, int32_t* d_work_out,
                             int32_t* d_trace_out, int trace_iters) {
-    int rc = ensure_device();
-    if (rc) return rc;
-    rc = pgdb_check(design, B, d_expect, d_counts, mode, max_iters, d_choi_out);
-    if (rc) return rc;
-    rc = check_extras(eig_rel_tol, d_trace_out, trace_iters);
-    if (rc) return rc;
+    PgdbCall call;
+    call.des = design; call.B = B; call.e = d_expect; call.c = d_counts; call.tp = trace_preserving; call.mode = mode; call.max_iters = max_iters;
+    call.choi = d_choi_out; call.it = d_iters_out; call.dy = d_dykstra_out; call.bt = d_backtracks_out; call.cost = d_cost_out;
+    call.sw = d_work_out; call.eig_rel_tol = eig_rel_tol; call.trace = d_trace_out; call.trace_iters = trace_iters;
+    FBX_TRY(pgdb_prepare(call));
     if (B == 0) return FBX_OK;
-    PgdbExtras ex; ex.eig_rel_tol = eig_rel_tol; ex.trace = d_trace_out; ex.trace_iters = d_trace_out ? trace_iters : 0;
-    if (ex.trace) FBX_HIP(hipMemsetAsync(ex.trace, 0, sizeof(int32_t) * 2 * (size_t)B * trace_iters, stream()));
-    return pgdb_dispatch(design, B, d_expect, d_counts, trace_preserving, mode, max_iters,
-                         d_choi_out, d_iters_out, d_dykstra_out, d_backtracks_out, d_cost_out, d_work_out, ex);
+    if (call.trace) FBX_HIP(hipMemsetAsync(call.trace, 0, sizeof(int32_t) * 2 * (size_t)B * trace_iters, stream()));
+    return pgdb_dispatch(call);
 }
 
 int fbx_pgdb_process_dev(const fbx_design* design, int64_t B, const double* d_expect,
@@ -412,165 +516,33 @@ int fbx_pgdb_process_dev(const fbx_design* design, int64_t B, const double* d_ex
                                    d_iters_out, d_dykstra_out, d_backtracks_out, d_cost_out, d_work_out, nullptr, 0);
 }
 
-// the host-pointer call on the calling thread's device; `total_batch` = size of the caller's whole batch when this is one
-// device's block of it (kernels are chosen by the whole, so that the split does not change a single bit of any item)
-static int pgdb_process_host(const fbx_design* design, int64_t B, const double* expect,
-                             const double* counts, int trace_preserving, int mode, int max_iters, double eig_rel_tol,
-                             double* choi_out, int32_t* iters_out, int32_t* dykstra_out,
-                             int32_t* backtracks_out, double* cost_out, int32_t* work_out,
-                             int32_t* trace_out, int trace_iters, int64_t total_batch);
-
 int fbx_pgdb_process_ex(const fbx_design* design, int64_t B, const double* expect,
                         const double* counts, int trace_preserving, int mode, int max_iters, double eig_rel_tol,
                         double* choi_out, int32_t* iters_out, int32_t* dykstra_out,
                         int32_t* backtracks_out, double* cost_out, int32_t* work_out,
                         int32_t* trace_out, int trace_iters) {
-    int rc = ensure_device();
-    if (rc) return rc;
-    rc = pgdb_check(design, B, expect, counts, mode, max_iters, choi_out);
-    if (rc) return rc;
-    rc = check_extras(eig_rel_tol, trace_out, trace_iters);
-    if (rc) return rc;
+    PgdbCall host;
+    host.des = design; host.B = B; host.e = expect; host.c = counts; host.tp = trace_preserving; host.mode = mode; host.max_iters = max_iters;
+    host.choi = choi_out; host.it = iters_out; host.dy = dykstra_out; host.bt = backtracks_out; host.cost = cost_out;
+    host.sw = work_out; host.eig_rel_tol = eig_rel_tol; host.trace = trace_out; host.trace_iters = trace_iters; host.total_batch = B;
+    FBX_TRY(pgdb_prepare(host));
     if (B == 0) return FBX_OK;
     // fbx_set_devices: contiguous blocks of the batch, one per entry of the device list, each on that entry's
     // worker thread with its own context and a replica of the design; no exchange between devices
     if (device_list_size() > 1 && !in_device_worker() && B >= 2 * (int64_t)device_list_size()) {
-        const size_t m = design->dev.m, DD = (size_t)design->dev.D * design->dev.D;
         return run_on_devices([&](int g, int G) -> int {       // G: the list's length as run_on_devices read it, under its lock
             const int64_t per = (B + G - 1) / G;
             const int64_t lo = (int64_t)g * per < B ? (int64_t)g * per : B, nb = (B - lo < per ? B - lo : per);
             if (nb <= 0) return FBX_OK;
             int r = ensure_device();
             if (r) return r;
-            const fbx_design* dg = design_on_this_device(design, &r);
+            PgdbCall block = host.slice(lo, nb);
+            block.des = design_on_this_device(design, &r);
             if (r) return r;
-            return pgdb_process_host(dg, nb, expect + lo * m, counts + lo * m, trace_preserving, mode, max_iters, eig_rel_tol,
-                                     choi_out + lo * 2 * DD, iters_out ? iters_out + lo : nullptr, dykstra_out ? dykstra_out + lo : nullptr,
-                                     backtracks_out ? backtracks_out + lo : nullptr, cost_out ? cost_out + lo : nullptr,
-                                     work_out ? work_out + 4 * lo : nullptr, trace_out ? trace_out + (size_t)lo * trace_iters * 2 : nullptr,
-                                     trace_iters, B);
+            return pgdb_process_host(block);
         });
     }
-    return pgdb_process_host(design, B, expect, counts, trace_preserving, mode, max_iters, eig_rel_tol, choi_out, iters_out,
-                             dykstra_out, backtracks_out, cost_out, work_out, trace_out, trace_iters, B);
-}
-
-static int pgdb_process_host(const fbx_design* design, int64_t B, const double* expect,
-                             const double* counts, int trace_preserving, int mode, int max_iters, double eig_rel_tol,
-                             double* choi_out, int32_t* iters_out, int32_t* dykstra_out,
-                             int32_t* backtracks_out, double* cost_out, int32_t* work_out,
-                             int32_t* trace_out, int trace_iters, int64_t total_batch) {
-    int rc = FBX_OK;
-    const size_t m = design->dev.m, D = design->dev.D;
-    const size_t trace_bytes = trace_out ? sizeof(int32_t) * 2 * (size_t)B * trace_iters : 0;
-    DevBuf de, dc, dchoi, dit, ddy, dbt, dcost, dsw, dtr;
-    if ((rc = de.alloc(sizeof(double) * B * m)) || (rc = dc.alloc(sizeof(double) * B * m)) ||
-        (rc = dchoi.alloc(sizeof(double) * 2 * B * D * D)) || (rc = dit.alloc(sizeof(int32_t) * B)) ||
-        (rc = ddy.alloc(sizeof(int32_t) * B)) || (rc = dbt.alloc(sizeof(int32_t) * B)) ||
-        (rc = dcost.alloc(sizeof(double) * B)) || (rc = dsw.alloc(sizeof(int32_t) * 4 * B)) ||
-        (trace_bytes && (rc = dtr.alloc(trace_bytes))))
-        return rc;
-    PgdbExtras ex; ex.eig_rel_tol = eig_rel_tol; ex.trace = trace_bytes ? dtr.as<int32_t>() : nullptr; ex.trace_iters = trace_bytes ? trace_iters : 0;
-    ex.total_batch = total_batch;
-    if (ex.trace) FBX_HIP(hipMemsetAsync(ex.trace, 0, trace_bytes, stream()));
-    // Page-locked caller buffers and more than one stage of work: H2D, kernels and D2H overlap on separate streams (SURVEY.md
-    // 8d prices the path including both transfers).  What cannot be hidden is the H2D of the first stage and the D2H of the
-    // last, and every boundary between stages costs a launch tail (a stage's slowest items run while SIMDs idle): so the plan
-    // is a SMALL first stage (fbx_set_option("pgdb_host_chunk") items, default 4096 = two reconstructions per wave slot of the two-waves kernel, which runs them in pieces; at
-    // most half the batch), a small last one, and everything in between in as few launches as the per-item workspace allows
-    // (65 536 items each) on a second, HIGH-PRIORITY compute stream: the first stage's kernel covers the upload of the rest,
-    // the bulk takes the SIMDs over as soon as it has arrived, and the last stage -- queued behind the first on the normal-
-    // priority stream -- only fills what the bulk's tail leaves idle and is still computing while the bulk's results go
-    // down.  (Round 3 first used equal stages: 8 boundaries for 65 536 items, 94-96 % of the resident rate.)
-    const int64_t CH = option_pgdb_host_chunk();
-    if (B > CH && host_pointer_is_pinned(expect, sizeof(double) * B * m) && host_pointer_is_pinned(counts, sizeof(double) * B * m) &&
-        host_pointer_is_pinned(choi_out, sizeof(double) * 2 * B * D * D)) {
-        hipStream_t s_in, s_out, s_c2;
-        if ((rc = copy_streams(&s_in, &s_out, &s_c2))) return rc;
-        // every failure inside the pipeline leaves through ONE door that waits for all four streams: copies and kernels may
-        // already be queued on them, and the staging blocks go back to the thread's pool when this function returns
-        auto drain = [&]() { (void)hipStreamSynchronize(s_in); (void)hipStreamSynchronize(stream()); (void)hipStreamSynchronize(s_c2); (void)hipStreamSynchronize(s_out); };
-#define FBX_HIP_P(call) do { hipError_t _e = (call); if (_e != hipSuccess) { drain(); return hip_fail(_e, #call, __FILE__, __LINE__); } } while (0)
-        struct Stage { int64_t b0, nb; bool second; int64_t ws_offset; };
-        std::vector<Stage> plan;
-        const int64_t MID = 65536;
-        const bool two_streams = design->dev.n <= 2;          // (the 3-qubit launcher has one workspace: one compute stream)
-        const int64_t first = CH < B / 2 ? CH : B / 2;
-        const int64_t last = (B >= 4 * CH) ? CH : 0;           // queued BEHIND the first stage: only when the bulk outlasts both
-        plan.push_back({0, first, false, 0});
-        for (int64_t b0 = first; b0 < B - last; b0 += MID)
-            plan.push_back({b0, (B - last - b0 < MID ? B - last - b0 : MID), two_streams, two_streams ? first : 0});
-        if (last) plan.push_back({B - last, last, false, 0});
-        const int64_t mid_slots = (B - last - first) < MID ? (B - last - first) : MID;
-        const int64_t ws_total = two_streams ? first + mid_slots : (first > mid_slots ? first : mid_slots);
-        const int nst = (int)plan.size();
-        hipEvent_t* ev = nullptr;
-        if ((rc = ordering_events(2 * nst + 1, &ev))) return rc;      // (nothing queued yet)
-        // (the staging buffers may still be in use by earlier work of this thread's stream)
-        FBX_HIP_P(hipEventRecord(ev[2 * nst], stream()));
-        FBX_HIP_P(hipStreamWaitEvent(s_in, ev[2 * nst], 0));
-        FBX_HIP_P(hipStreamWaitEvent(s_out, ev[2 * nst], 0));
-        FBX_HIP_P(hipStreamWaitEvent(s_c2, ev[2 * nst], 0));
-        for (int k = 0; k < nst; ++k) {                        // uploads in stage order, back to back
-            const int64_t b0 = plan[k].b0, nb = plan[k].nb;
-            FBX_HIP_P(hipMemcpyAsync(de.as<double>() + b0 * m, expect + b0 * m, sizeof(double) * nb * m, hipMemcpyHostToDevice, s_in));
-            FBX_HIP_P(hipMemcpyAsync(dc.as<double>() + b0 * m, counts + b0 * m, sizeof(double) * nb * m, hipMemcpyHostToDevice, s_in));
-            FBX_HIP_P(hipEventRecord(ev[2 * k], s_in));
-        }
-        for (int k = 0; k < nst; ++k) {
-            const int64_t b0 = plan[k].b0, nb = plan[k].nb;
-            hipStream_t s_k = plan[k].second ? s_c2 : stream();
-            FBX_HIP_P(hipStreamWaitEvent(s_k, ev[2 * k], 0));
-            PgdbExtras exk = ex;
-            if (exk.trace) exk.trace += (size_t)b0 * exk.trace_iters * 2;
-            exk.launch_stream = s_k; exk.ws_items = ws_total; exk.ws_offset = plan[k].ws_offset; exk.total_batch = total_batch > B ? total_batch : B;
-            rc = pgdb_dispatch(design, nb, de.as<double>() + b0 * m, dc.as<double>() + b0 * m, trace_preserving, mode, max_iters,
-                               dchoi.as<double>() + b0 * 2 * D * D, dit.as<int32_t>() + b0, ddy.as<int32_t>() + b0,
-                               dbt.as<int32_t>() + b0, dcost.as<double>() + b0, dsw.as<int32_t>() + 4 * b0, exk);
-            if (rc) break;
-            FBX_HIP_P(hipEventRecord(ev[2 * k + 1], s_k));
-            FBX_HIP_P(hipStreamWaitEvent(s_out, ev[2 * k + 1], 0));
-            FBX_HIP_P(hipMemcpyAsync(choi_out + b0 * 2 * D * D, dchoi.as<double>() + b0 * 2 * D * D, sizeof(double) * 2 * nb * D * D,
-                                   hipMemcpyDeviceToHost, s_out));
-        }
-        if (rc) {
-            drain();
-            // the pipeline wants workspace slots for the whole bulk at once; when the device cannot give that much the staged path
-            // below runs the batch in launches that fit (it halves them until the store does)
-            if (rc != FBX_ERR_NOMEM) return rc;
-            (void)hipGetLastError();
-            goto staged;
-        }
-        FBX_HIP_P(hipEventRecord(ev[2 * nst], s_c2));            // the small outputs below follow BOTH compute streams
-        FBX_HIP_P(hipStreamWaitEvent(stream(), ev[2 * nst], 0));
-        if (iters_out) FBX_HIP_P(hipMemcpyAsync(iters_out, dit.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream()));
-        if (dykstra_out) FBX_HIP_P(hipMemcpyAsync(dykstra_out, ddy.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream()));
-        if (backtracks_out) FBX_HIP_P(hipMemcpyAsync(backtracks_out, dbt.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream()));
-        if (cost_out) FBX_HIP_P(hipMemcpyAsync(cost_out, dcost.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream()));
-        if (work_out) FBX_HIP_P(hipMemcpyAsync(work_out, dsw.p, sizeof(int32_t) * 4 * B, hipMemcpyDeviceToHost, stream()));
-        if (trace_bytes) FBX_HIP_P(hipMemcpyAsync(trace_out, dtr.p, trace_bytes, hipMemcpyDeviceToHost, stream()));
-        FBX_HIP_P(hipStreamSynchronize(stream()));
-        FBX_HIP_P(hipStreamSynchronize(s_out));
-        FBX_HIP_P(hipStreamSynchronize(s_in));
-        return FBX_OK;
-#undef FBX_HIP_P
-    }
-staged:
-    FBX_HIP(hipMemcpyAsync(de.p, expect, sizeof(double) * B * m, hipMemcpyHostToDevice, stream()));
-    FBX_HIP(hipMemcpyAsync(dc.p, counts, sizeof(double) * B * m, hipMemcpyHostToDevice, stream()));
-    rc = pgdb_dispatch(design, B, de.as<double>(), dc.as<double>(), trace_preserving, mode, max_iters,
-                       dchoi.as<double>(), dit.as<int32_t>(), ddy.as<int32_t>(), dbt.as<int32_t>(),
-                       dcost.as<double>(), dsw.as<int32_t>(), ex);
-    if (rc) { (void)hipStreamSynchronize(stream()); return rc; }
-    FBX_HIP(hipMemcpyAsync(choi_out, dchoi.p, sizeof(double) * 2 * B * D * D, hipMemcpyDeviceToHost, stream()));
-    if (iters_out) FBX_HIP(hipMemcpyAsync(iters_out, dit.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream()));
-    if (dykstra_out) FBX_HIP(hipMemcpyAsync(dykstra_out, ddy.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream()));
-    if (backtracks_out) FBX_HIP(hipMemcpyAsync(backtracks_out, dbt.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream()));
-    if (cost_out) FBX_HIP(hipMemcpyAsync(cost_out, dcost.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream()));
-    if (work_out) FBX_HIP(hipMemcpyAsync(work_out, dsw.p, sizeof(int32_t) * 4 * B, hipMemcpyDeviceToHost, stream()));
-    if (trace_bytes) FBX_HIP(hipMemcpyAsync(trace_out, dtr.p, trace_bytes, hipMemcpyDeviceToHost, stream()));
-    FBX_HIP(hipStreamSynchronize(stream()));
-    return FBX_OK;
+    return pgdb_process_host(host);
 }
 
 // _cost / _grad_cost (tomography.py:597-633); include/fbx.h

@@ -301,9 +301,8 @@ static long long env_ll(const char* name, long long dflt) { const char* v = gete
 // Binned relaunch of one chunk of the batch (items [first, first + n) of the caller's arrays), advanced ONE LAUNCH AT A TIME so that
 // the chunks of a call can be interleaved on two streams (round 6, pgdb1_binned_run below).
 struct P1Run {
-    const fbx_design* des = nullptr; long long first = 0, n = 0; const double* e = nullptr; const double* c = nullptr;
-    int tp = 0, mode = 0, max_iters = 0; double* choi = nullptr; int32_t *it = nullptr, *dy = nullptr, *bt = nullptr; double* cost = nullptr;
-    int32_t* sw = nullptr; PgdbExtras ex; long long tail_items = 0; int check_every = 8;
+    const PgdbCall* call = nullptr;       // the WHOLE call (mode without its flags): the kernel takes `first` and `n` beside the arrays
+    long long first = 0, n = 0; long long tail_items = 0; int check_every = 8;
     hipStream_t st = nullptr; size_t lds = 0;
     P1Bins bins; int* cnt = nullptr; double* region[2] = {nullptr, nullptr};
     long long active_bound = 0; int step = 0; bool done = false, reading = false;
@@ -315,7 +314,7 @@ struct P1Run {
         return (256 + ((size_t)n * 2 * m + 2 * region_doubles) * sizeof(double) + 255) & ~(size_t)255;
     }
     int start(void* w) {
-        const int m = des->dev.m;
+        const int m = call->des->dev.m;
         lds = sizeof(double) * 2 * (size_t)m * 64;
         bins.cap_slots = (n + 63) / 64 * 64;
         const size_t region_doubles = (size_t)(P1_NB / 2) * bins.cap_slots * P1_NF, tab_doubles = (size_t)n * 2 * m;
@@ -333,12 +332,13 @@ struct P1Run {
         bins.cur_count = cnt + 16 * (step % 3); bins.next_count = cnt + 16 * ((step + 1) % 3); bins.clear_count = cnt + 16 * ((step + 2) % 3);
         const bool tail = step > 0 && active_bound <= tail_items;
         const long long grid = (active_bound + 63) / 64 + (step == 0 ? 0 : P1_NB);
-        hipLaunchKernelGGL(pgdb1_step_kernel, dim3((unsigned)grid), dim3(64), lds, st, des->dev, first, n, e, c, tp, mode, max_iters,
-                           choi, it, dy, bt, cost, sw, ex.trace, ex.trace_iters, bins, step == 0 ? 1 : 0, tail ? 1 : 0, step);
+        hipLaunchKernelGGL(pgdb1_step_kernel, dim3((unsigned)grid), dim3(64), lds, st, call->des->dev, first, n, call->e, call->c, call->tp,
+                           call->mode, call->max_iters, call->choi, call->it, call->dy, call->bt, call->cost, call->sw, call->trace,
+                           call->trace_iters, bins, step == 0 ? 1 : 0, tail ? 1 : 0, step);
         FBX_HIP(hipGetLastError());
         ++step;
         if (tail) { done = true; return FBX_OK; }
-        if (mode == FBX_MODE_FIXED && step >= max_iters) { done = true; return FBX_OK; }        // every reconstruction runs exactly max_iters iterations
+        if (call->mode == FBX_MODE_FIXED && step >= call->max_iters) { done = true; return FBX_OK; }        // every reconstruction runs exactly max_iters iterations
         // how many are left: read back every few launches (the grid shrinks with it), at every launch near the end
         if (step % check_every == 0 || active_bound <= 4 * tail_items) {
             FBX_HIP(hipMemcpyAsync(host_cnt, bins.next_count, sizeof(int) * P1_NB, hipMemcpyDeviceToHost, st));
@@ -363,9 +363,9 @@ struct P1Run {
 // floor of one lane): the batch is therefore cut into chunks that run as INDEPENDENT binned pipelines, two at a time on two
 // streams (the calling thread's and its second compute stream), so that one pipeline's launches fill the other's tails.  Bins are
 // per chunk; an item's arithmetic does not know which chunk or stream it ran in (bit-identical outputs, tests/test_pgdb1_gpu.py).
-static int pgdb1_binned_run(const fbx_design* des, long long B, const double* e, const double* c, int tp, int mode, int max_iters,
-                            double* choi, int32_t* it, int32_t* dy, int32_t* bt, double* cost, int32_t* sw, const PgdbExtras& ex,
-                            long long chunk, long long tail_items, int check_every, int n_streams) {
+static int pgdb1_binned_run(const PgdbCall& call, long long chunk, long long tail_items, int check_every, int n_streams) {
+    const fbx_design* des = call.des;
+    const long long B = call.B;
     FBX_HIP(hipFuncSetAttribute((const void*)pgdb1_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(sizeof(double) * 2 * (size_t)des->dev.m * 64)));
     const int m = des->dev.m;
@@ -382,9 +382,9 @@ static int pgdb1_binned_run(const fbx_design* des, long long B, const double* e,
     // (no room for the bins: the caller falls back to the persistent kernel, which needs none)
     if (workspace(WS_PGDB1_BINS, per * lanes, &w) != FBX_OK) { (void)hipGetLastError(); return FBX_ERR_NOMEM; }
     // (page-locked: a read-back into pageable memory would hold the host until its stream has drained -- and with it the other pipeline's launches)
-    static thread_local int* host_cnt_mem = nullptr;
-    if (!host_cnt_mem) FBX_HIP(hipHostMalloc((void**)&host_cnt_mem, sizeof(int) * 2 * P1_NB, hipHostMallocDefault));
-    int* host_cnt[2] = {host_cnt_mem, host_cnt_mem + P1_NB};
+    void* host_cnt_mem = nullptr;
+    { const int rc = pinned_scratch(sizeof(int) * 2 * P1_NB, &host_cnt_mem); if (rc) return rc; }
+    int* host_cnt[2] = {(int*)host_cnt_mem, (int*)host_cnt_mem + P1_NB};
     if (lanes == 2) {                                              // the second stream starts behind whatever the caller queued on the first
         FBX_HIP(hipEventRecord(ev[0], sts[0]));
         FBX_HIP(hipStreamWaitEvent(sts[1], ev[0], 0));
@@ -395,8 +395,7 @@ static int pgdb1_binned_run(const fbx_design* des, long long B, const double* e,
     auto feed = [&](int k) -> int {                                // the next chunk of the batch into pipeline k
         P1Run& r = run[k];
         r = P1Run();
-        r.des = des; r.first = next; r.n = B - next < chunk ? B - next : chunk; r.e = e; r.c = c; r.tp = tp; r.mode = mode; r.max_iters = max_iters;
-        r.choi = choi; r.it = it; r.dy = dy; r.bt = bt; r.cost = cost; r.sw = sw; r.ex = ex; r.tail_items = tail_items; r.check_every = check_every;
+        r.call = &call; r.first = next; r.n = B - next < chunk ? B - next : chunk; r.tail_items = tail_items; r.check_every = check_every;
         r.st = sts[k]; r.host_cnt = host_cnt[k];
         next += r.n;
         return r.start((char*)w + per * k);
@@ -419,15 +418,18 @@ static int pgdb1_binned_run(const fbx_design* des, long long B, const double* e,
     return rc;
 }
 
+static int pgdb1_run(const PgdbCall& call);
+
+int pgdb1_dispatch(const PgdbCall& in) {
+    PgdbCall call = in;
+    call.mode &= 0xff;     // (a call with FBX_MODE_LS_REFERENCE only gets here with pgdb_packed_1q = 2, a diagnostics setting: the flag is dropped)
 #ifdef FBX_PHASE_TIMERS
-static int pgdb1_dispatch_(const fbx_design* des, int64_t B, const double* e, const double* c, int tp, int mode, int max_iters,
-                   double* choi, int32_t* it, int32_t* dy, int32_t* bt, double* cost, int32_t* sw, const PgdbExtras& ex);
-int pgdb1_dispatch(const fbx_design* des, int64_t B, const double* e, const double* c, int tp, int mode, int max_iters,
-                   double* choi, int32_t* it, int32_t* dy, int32_t* bt, double* cost, int32_t* sw, const PgdbExtras& ex) {
     static unsigned long long z[P1_PROF_STEPS][24];
     memset(z, 0, sizeof(z));
     FBX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_p1_prof), z, sizeof(z)));
-    const int rc = pgdb1_dispatch_(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
+#endif
+    const int rc = pgdb1_run(call);
+#ifdef FBX_PHASE_TIMERS
     FBX_HIP(hipStreamSynchronize(stream()));
     FBX_HIP(hipMemcpyFromSymbol(z, HIP_SYMBOL(g_p1_prof), sizeof(z)));
     for (int sidx = 0; sidx < P1_PROF_STEPS; ++sidx) {
@@ -436,13 +438,15 @@ int pgdb1_dispatch(const fbx_design* des, int64_t B, const double* e, const doub
         for (int k = 0; k < 24; ++k) fprintf(stderr, " %llu", z[sidx][k]);
         fprintf(stderr, "\n");
     }
+#endif
     return rc;
 }
-#define pgdb1_dispatch static pgdb1_dispatch_
-#endif
-int pgdb1_dispatch(const fbx_design* des, int64_t B, const double* e, const double* c, int tp, int mode, int max_iters,
-                   double* choi, int32_t* it, int32_t* dy, int32_t* bt, double* cost, int32_t* sw, const PgdbExtras& ex) {
-    mode &= 0xff;          // (a call with FBX_MODE_LS_REFERENCE only gets here with pgdb_packed_1q = 2, a diagnostics setting: the flag is dropped)
+
+// binned relaunch or the persistent kernel
+static int pgdb1_run(const PgdbCall& call) {
+    const fbx_design* des = call.des;
+    const int64_t B = call.B;
+    const int mode = call.mode, max_iters = call.max_iters;
     {
         // Binned relaunch from the batch sizes at which it wins (scripts/pgdb1_binned_time.py; below them a launch per outer
         // iteration costs more than the grouping returns): to convergence 2^20 experiments (2^19 for designs of <= 12
@@ -454,7 +458,7 @@ int pgdb1_dispatch(const fbx_design* des, int64_t B, const double* e, const doub
         const long long from = mode == FBX_MODE_FIXED ? (1 << 17) : (des->dev.m <= 12 ? (1 << 19) : (1 << 20));
         // (a stage of the pipelined host entry point shares the calling thread's workspaces with the stage on the other stream:
         // those stay with the persistent kernel)
-        if (!ex.launch_stream && !(mode == FBX_MODE_FIXED && max_iters == 0) && (binned == 2 || (binned == 1 && B >= from))) {
+        if (!call.launch_stream && !(mode == FBX_MODE_FIXED && max_iters == 0) && (binned == 2 || (binned == 1 && B >= from))) {
             // chunks: FBX_P1_CHUNK, else HALF the batch (at least 2^18 items, at most 2^20): one pipeline per stream.  Measured at 2^20
             // experiments (scripts/pgdb1_streams_time.py, same box, every output bit-identical): a pipeline costs ~22 ms whatever its
             // size -- the launches of the long tail of iteration counts, the serial floor of the slowest lanes -- plus ~7.7 ms per 2^18
@@ -464,7 +468,7 @@ int pgdb1_dispatch(const fbx_design* des, int64_t B, const double* e, const doub
             long long chunk_ = chunk > 0 ? chunk : (B + 1) / 2;
             if (chunk <= 0) chunk_ = chunk_ < (1 << 18) ? (1 << 18) : (chunk_ > (1 << 20) ? (1 << 20) : chunk_);
             chunk_ = chunk_ < 4096 ? 4096 : (chunk_ > (1 << 22) ? (1 << 22) : chunk_);
-            const int rc = pgdb1_binned_run(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex, chunk_, tail, every < 1 ? 1 : (int)every,
+            const int rc = pgdb1_binned_run(call, chunk_, tail, every < 1 ? 1 : (int)every,
                                             (int)env_ll("FBX_P1_STREAMS", 2));
             // out of device memory for the bins (before anything of the chunk was launched: results are per item, the chunks
             // already done stay valid and are simply recomputed): the persistent kernel below takes the whole batch
@@ -493,12 +497,12 @@ int pgdb1_dispatch(const fbx_design* des, int64_t B, const double* e, const doub
     void* w = nullptr;
     { const int rc = workspace(WS_PGDB1_COUNTER, 256, &w); if (rc) return rc; }
     // (the pipelined host entry point runs two stages at once on two streams: each has its own counter)
-    unsigned long long* counter = (unsigned long long*)w + (ex.ws_offset ? 8 : 0);
-    hipStream_t st = ex.launch_stream ? ex.launch_stream : stream();
+    unsigned long long* counter = (unsigned long long*)w + (call.ws_offset ? 8 : 0);
+    hipStream_t st = call.launch_stream ? call.launch_stream : stream();
     hipLaunchKernelGGL(pgdb1_set_counter, dim3(1), dim3(1), 0, st, counter, (unsigned long long)(grid * 64));
     DesignDev d = des->dev;
-    hipLaunchKernelGGL(pgdb1_packed_kernel, dim3((unsigned)grid), dim3(64), lds, st, d, (long long)B, e, c, tp, mode, max_iters,
-                       choi, it, dy, bt, cost, sw, ex.trace, ex.trace_iters, counter);
+    hipLaunchKernelGGL(pgdb1_packed_kernel, dim3((unsigned)grid), dim3(64), lds, st, d, (long long)B, call.e, call.c, call.tp, mode, max_iters,
+                       call.choi, call.it, call.dy, call.bt, call.cost, call.sw, call.trace, call.trace_iters, counter);
     FBX_HIP(hipGetLastError());
     return FBX_OK;
 }

@@ -377,8 +377,8 @@ __device__ Blk proj_tni(const Blk& x, Lds& L, int t, int& sweeps) {   // project
     return subtract_kron_pt(x, L, t);
 }
 
-// -DFBX3_DYK_DETAIL (diagnostics, with FBX_PHASE_TIMERS): the phases of a Dykstra iteration take over the timer slots of
-// the outer phases -- 3 basis load, 7 basis write-back, 4 TP / TNI projection, 5 stopping functional (2 then = Hermitise only)
+// marks of the phases of a Dykstra iteration -- 3 basis load, 7 basis write-back, 4 TP / TNI projection, 5 stopping functional
+// (no build fills them in any more: the per-phase timers of -DFBX_PHASE_TIMERS cover the outer phases only)
 #define PH3(ph)
 // one stored basis (64 KiB, the layout of Vs) from HBM / L2 into LDS without passing through registers: every lane moves
 // four 16-byte entries; the LDS address of a global_load_lds is wave-uniform base + lane * 16
@@ -938,9 +938,9 @@ pgdb3_kernel(DesignDev des, long long B, const double* __restrict__ expect, cons
 }
 
 template <int MAXJ>
-static int launch3(const fbx_design* des, int64_t B, const double* e, const double* c, int tp, int mode,
-                   int max_iters, double* choi, int32_t* it, int32_t* dy, int32_t* bt, double* cost, int32_t* sw,
-                   const PgdbExtras& ex) {
+static int launch3(const PgdbCall& call) {
+    const fbx_design* des = call.des;
+    const int64_t B = call.B;
     const size_t lds = p3::Lds::bytes();
     if ((size_t)des->dev.S * p3::D * sizeof(double) > 2 * sizeof(cplx) * p3::D * p3::D) {
         set_error("fbx_pgdb_process: too many distinct input states for the 3-qubit kernel");
@@ -961,16 +961,13 @@ static int launch3(const fbx_design* des, int64_t B, const double* e, const doub
     cplx* scratch = (cplx*)w;
     cplx* basis = scratch;                   // (`scratch` itself only tells the kernel that warm starts are on)
     double* park = (double*)((char*)w + basis_bytes);
-    const size_t m = des->dev.m, DD = (size_t)p3::D * p3::D;
     DesignDev dev = des->dev;
-    dev.eig_rel_tol = ex.eig_rel_tol >= 0.0 ? ex.eig_rel_tol : option_pgdb_eig_rel_tol(3);
+    dev.eig_rel_tol = call.eig_rel_tol >= 0.0 ? call.eig_rel_tol : option_pgdb_eig_rel_tol(3);
     for (int64_t b0 = 0; b0 < B; b0 += CHUNK) {
-        const int64_t nb = B - b0 < CHUNK ? B - b0 : CHUNK;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(1024), lds, ex.launch_stream ? ex.launch_stream : stream(), dev, (long long)nb,
-                           e + b0 * m, c + b0 * m, tp, mode, max_iters, choi + b0 * DD * 2, it ? it + b0 : nullptr,
-                           dy ? dy + b0 : nullptr, bt ? bt + b0 : nullptr, cost ? cost + b0 : nullptr, scratch,
-                           FBX_PHASE_OUT3(b0), sw ? sw + 4 * b0 : nullptr, basis, BASIS_CAP,
-                           ex.trace ? ex.trace + (size_t)b0 * ex.trace_iters * 2 : nullptr, ex.trace_iters, park);
+        const PgdbCall s = call.slice(b0, B - b0 < CHUNK ? B - b0 : CHUNK);
+        hipLaunchKernelGGL(kern, dim3((unsigned)s.B), dim3(1024), lds, s.launch_stream ? s.launch_stream : stream(), dev, (long long)s.B,
+                           s.e, s.c, s.tp, s.mode, s.max_iters, s.choi, s.it, s.dy, s.bt, s.cost, scratch,
+                           FBX_PHASE_OUT3(b0), s.sw, basis, BASIS_CAP, s.trace, s.trace_iters, park);
     }
     FBX_HIP(hipGetLastError());
     return FBX_OK;
@@ -1087,11 +1084,12 @@ int pgdb3_cost_grad_launch(const fbx_design* des, int64_t B, const double* nvec,
         set_error("fbx_pgdb_cost_grad: too many distinct input states for the 3-qubit kernel");
         return FBX_ERR_UNSUPPORTED;
     }
-    DevBuf eta;
-    { const int rc = eta.alloc(sizeof(double) * 2 * (size_t)B * des->dev.m); if (rc) return rc; }
+    // (a grow-only workspace of the calling thread: it outlives the kernel, and growing it waits for the stream)
+    void* eta = nullptr;
+    { const int rc = workspace(WS_PGDB3_ETA, sizeof(double) * 2 * (size_t)B * des->dev.m, &eta); if (rc) return rc; }
     FBX_HIP(hipFuncSetAttribute((const void*)pgdb3_cost_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(pgdb3_cost_grad_kernel, dim3((unsigned)B), dim3(1024), lds, stream(), des->dev, (long long)B, nvec, choi, eps, cost,
-                       grad, eta.as<double>());
+                       grad, (double*)eta);
     FBX_HIP(hipGetLastError());
     return FBX_OK;
 }
@@ -1185,18 +1183,17 @@ int linv_process3_launch(const fbx_design* des, int64_t B, const double* d_expec
 }
 
 // called from fbx_pgdb.hip's dispatcher
-int pgdb3_dispatch(const fbx_design* des, int64_t B, const double* e, const double* c, int tp, int mode,
-                   int max_iters, double* choi, int32_t* it, int32_t* dy, int32_t* bt, double* cost, int32_t* sw,
-                   const PgdbExtras& ex) {
-    const int m = des->dev.m;
-    mode &= 0xff;          // FBX_MODE_LS_REFERENCE: this kernel's line search always evaluates the full cost with the rounded test
-    if (m <= 4096) return launch3<4>(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
-    if (m <= 14336) return launch3<14>(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
+int pgdb3_dispatch(const PgdbCall& in) {
+    const int m = in.des->dev.m;
+    PgdbCall call = in;
+    call.mode &= 0xff;     // FBX_MODE_LS_REFERENCE: this kernel's line search always evaluates the full cost with the rounded test
+    if (m <= 4096) return launch3<4>(call);
+    if (m <= 14336) return launch3<14>(call);
     // Merged / repeated datasets (the reference takes any result list, tomography.py:494-539): the same kernel with 32 / 64 outcome
     // slots per thread.  Their per-slot arrays no longer fit 128 registers and live in scratch: slow (a few times the resident
     // instantiations per outer iteration outside the projection) and complete up to 65 536 settings.
-    if (m <= 32768) return launch3<32>(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
-    if (m <= 65536) return launch3<64>(des, B, e, c, tp, mode, max_iters, choi, it, dy, bt, cost, sw, ex);
+    if (m <= 32768) return launch3<32>(call);
+    if (m <= 65536) return launch3<64>(call);
     set_error("fbx_pgdb_process: 3-qubit designs are limited to 65536 settings");
     return FBX_ERR_UNSUPPORTED;
 }

@@ -29,8 +29,11 @@ struct ThreadCtx {
     std::vector<Block> pool;
     void* ws[WS_COUNT] = {};
     size_t ws_bytes[WS_COUNT] = {};
+    void* pinned = nullptr;                                // page-locked host scratch (pinned_scratch)
+    size_t pinned_bytes = 0;
 
     void drop_memory() {
+        if (pinned) { (void)hipHostFree(pinned); pinned = nullptr; pinned_bytes = 0; }
         for (auto& b : pool) if (b.p) (void)hipFree(b.p);
         pool.clear();
         for (int i = 0; i < WS_COUNT; ++i) { if (ws[i]) (void)hipFree(ws[i]); ws[i] = nullptr; ws_bytes[i] = 0; }
@@ -253,6 +256,23 @@ int pool_take(size_t bytes, void** out) {
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(staging)", __FILE__, __LINE__);
     c->pool.push_back({p, bytes, true});
     *out = p;
+    return FBX_OK;
+}
+
+int pinned_scratch(size_t bytes, void** out) {
+    ThreadCtx* c = ctx();
+    if (!c) { set_error("libfbx: no device context"); return FBX_ERR_HIP; }
+    if (bytes > c->pinned_bytes) {
+        if (c->pinned) {
+            FBX_HIP(hipStreamSynchronize(c->stream));       // a read-back of this thread may still be on its way into the old one
+            if (c->compute2) FBX_HIP(hipStreamSynchronize(c->compute2));
+            (void)hipHostFree(c->pinned);
+            c->pinned = nullptr; c->pinned_bytes = 0;
+        }
+        FBX_HIP(hipHostMalloc(&c->pinned, bytes, hipHostMallocDefault));
+        c->pinned_bytes = bytes;
+    }
+    *out = c->pinned;
     return FBX_OK;
 }
 

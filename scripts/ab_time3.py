@@ -1,6 +1,6 @@
 """A/B of two builds of the library on ONE box, 3-qubit PGDB (256 items, SIC in-basis, 100 fixed iterations): python scripts/ab_time3.py libA.so libB.so"""
 import os, subprocess, sys
-ROOT="/root/repo"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = r'''
 import sys, os, ctypes
 sys.path.insert(0, os.path.join(sys.argv[1], "forest-benchmarking_amd"))

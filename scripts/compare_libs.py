@@ -1,4 +1,5 @@
-"""Bit-for-bit comparison of two builds of the library on the same inputs: PGDB (2 qubits on both kernels, 1 and 3 qubits), the
+"""Bit-for-bit comparison of two builds of the library on the same inputs: PGDB (2 qubits on both kernels, 1 and 3 qubits -- both
+in-bases -- and the 3-qubit _cost / _grad_cost), the
 state estimators and measures for 1-4 qubits incl. designs of more than 64 settings, Choi projections, every conversion route and
 Kraus sweep kernel (both forms of the 3-qubit ones, batches past the persistent grid, Kraus counts on either side of each kernel
 switch), the Kraus-pair / twirl / partial-trace / apply / fidelity / linear-inversion entry points, and fbx_eigh / fbx_matmul /
@@ -15,7 +16,7 @@ from fbx import synthetic, tomography, _lib
 _lib.set_device(0)
 out = []
 for n, basis, B, kw in ((2, "pauli", 256, dict(mode="fixed", max_iters=100)), (2, "pauli", 2304, {}), (2, "sic", 64, {}), (1, "pauli", 32, {}),
-                        (3, "sic", 4, dict(mode="fixed", max_iters=12))):
+                        (3, "sic", 4, dict(mode="fixed", max_iters=12)), (3, "pauli", 2, dict(mode="fixed", max_iters=6))):
     design, _, e, c = synthetic.process_batch(n, basis, min(B, 256))
     if B > 256:
         e = np.tile(e, (B // 256, 1)); c = np.tile(c, (B // 256, 1))
@@ -24,6 +25,11 @@ for n, basis, B, kw in ((2, "pauli", 256, dict(mode="fixed", max_iters=100)), (2
     for k in ("iterations", "dykstra", "backtracks"):
         h.update(np.ascontiguousarray(st[k]).tobytes())
     out.append(h.hexdigest()[:16])
+# 3-qubit _cost / _grad_cost (pgdb3_cost_grad_kernel) at estimates three iterations in
+design, _, e, c = synthetic.process_batch(3, "sic", 2)
+est = tomography.pgdb_process_estimate_batch(design, e, c, mode="fixed", max_iters=3)
+cost, grad = tomography.cost_and_gradient_batch(design, tomography.normalised_counts(e, c), est)
+out.append(hashlib.sha256(np.ascontiguousarray(cost).tobytes() + np.ascontiguousarray(grad).tobytes()).hexdigest()[:16])
 # everything else that shares the touched headers: state MLE, Choi projections, conversions (incl. the eigh routes), the sweeps
 import warnings
 warnings.simplefilter("ignore")

@@ -1,6 +1,6 @@
 """Bit-for-bit comparison of two builds of the library on the same inputs: PGDB (2 qubits on both kernels, 1 and 3 qubits -- both
 in-bases -- and the 3-qubit _cost / _grad_cost), the
-state estimators and measures for 1-4 qubits incl. designs of more than 64 settings, Choi projections, every conversion route and
+state estimators and measures for 1-5 qubits incl. designs of more than 64 settings, Choi projections, every conversion route and
 Kraus sweep kernel (both forms of the 3-qubit ones, batches past the persistent grid, Kraus counts on either side of each kernel
 switch), the Kraus-pair / twirl / partial-trace / apply / fidelity / linear-inversion entry points, and fbx_eigh / fbx_matmul /
 fbx_choi2kraus at every size class, and the simulated acquisitions (tomography plain / grouped / symmetrized / calibration, DFE,
@@ -66,7 +66,7 @@ for n, B in ((2, 1001), (3, 33)):
     _lib.check(lib.fbx_kraus_sweep(n, B, K, _lib.dptr(k.view(np.float64)), _lib.dptr(ref.view(np.float64)), _lib.dptr(choi.view(np.float64)),
                                    _lib.dptr(ptm.view(np.float64)), _lib.dptr(chi.view(np.float64)), _lib.dptr(fid)))
     out.append(H(choi, ptm, chi, fid))
-# the state path entry point by entry point (1-4 qubits; designs of 66-126 settings: the staged R operator, 4200: the streamed one)
+# the state path entry point by entry point (1-5 qubits; designs of 66-126 settings: the staged R operator, 4200: the streamed one)
 # and the general linear algebra of csrc/fbx_linalg.hip
 from fbx import design as fd, distance_measures as dm
 def rand_states(B, d, seed):
@@ -91,6 +91,11 @@ design, _, e, c = synthetic.state_batch(4, 2, mixed=0.05)
 state_calls(design, e, c, rand_states(2, 16, 15), (dict(maxiter=8), dict(maxiter=8, beta=0.5), dict(maxiter=8, entropy_penalty=0.005)))
 out.append(H(psm.project_state_matrix_to_physical_batch(rs.randn(2, 16, 16) + 1j * rs.randn(2, 16, 16) + np.eye(16))))
 measures(rand_states(2, 16, 25), rand_states(2, 16, 35))
+design, _, e, c = synthetic.state_batch(5, 1, mixed=0.05)                  # 5 qubits: one item through the workgroup kernels
+out.append(H(tomography.iterative_mle_state_estimate_batch(design, e, c, maxiter=3)))
+r5 = np.random.RandomState(5)
+out.append(H(psm.project_state_matrix_to_physical_batch(r5.randn(1, 32, 32) + 1j * r5.randn(1, 32, 32) + np.eye(32))))
+measures(rand_states(1, 32, 26), rand_states(1, 32, 36))
 variants = (dict(maxiter=40), dict(beta=0.5, epsilon=1e-4, maxiter=12), dict(entropy_penalty=0.005, maxiter=12))
 for n, reps in ((1, 22), (2, 5), (3, 2)):
     p = np.tile(fd.traceless_pauli_codes(n), (reps, 1))

@@ -4,7 +4,7 @@ tests/golden/repeated.npz (make_goldens.py --repeated, produced by the reference
 sizes of the kernels: 2-qubit process designs of 1620 (Pauli x 3) and 1200 (SIC x 5) settings (register-resident kernels:
 1024), a 1-qubit one of 270 (256), state designs of 4200 settings (64 KiB of per-setting LDS staging = 3970).  Until round 5
 those calls returned FBX_ERR_UNSUPPORTED (3 qubits: beyond 14 336 settings, tests at the end); now they take the streamed forms (csrc/fbx_pgdb_body.hpp STREAM: outcome slots read
-from HBM / L2; csrc/fbx_state.hip r_operator_elem: no per-setting staging) and must give the reference's answer for that list.
+from HBM / L2; csrc/fbx_state.hip r_operator_strided: no per-setting staging) and must give the reference's answer for that list.
 
 CPU: the oracle against the fixture.  GPU: the kernels against the fixture, and the streamed kernels against the resident ones
 on a design both can run."""
@@ -119,7 +119,7 @@ def test_state_tomography_of_a_repeated_dataset(gpu, tag, n):
 @pytest.mark.parametrize("n,reps", [(1, 22), (2, 5), (3, 2)])
 def test_state_tomography_of_a_staged_design(gpu, n, reps):
     """More than 64 settings (no setting per lane, no packed or plain kernel) but within the 64 KiB of per-setting LDS staging:
-    mle_state_kernel with the STAGED form of r_operator_elem, which the fixtures above (4200 settings: streamed) and
+    mle_state_kernel with the STAGED form of r_operator_strided, which the fixtures above (4200 settings: streamed) and
     tests/test_state_gpu.py (at most 63) do not reach.  The non-identity Pauli design measured `reps` times, against the oracle
     on the same list, item by item, with the tolerances of the 4200-setting fixtures."""
     import warnings

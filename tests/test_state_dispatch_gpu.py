@@ -8,17 +8,17 @@ With D = 4^n, m settings, and "plain" for no entropy penalty and no hedging, the
     n >= 4                                   mle_state_big_kernel<n>
     packed = plain && n <= 2 && m <= D       mle_state_packed_kernel<n>      16 / 4 items per wavefront
     n == 3 && plain && m <= 64               mle_state_plain3_kernel
-    otherwise                                mle_state_kernel<n>             m <= 64: r_operator_tab (a setting per lane),
-                                                                             m > 64: r_operator_elem (staged in LDS)
+    otherwise                                mle_state_kernel<n>             m <= 64: r_operator_resident (a setting per lane),
+                                                                             m > 64: r_operator_strided (staged in LDS)
 
 and the tests reach
 
     test                                        n, design (m)                                        kernel
     test_packed_at_m_equal_D                    1, 2 with_identity (4, 16 = D)                       mle_state_packed_kernel<1, 2>
     test_packed_partial_and_full_waves          1, 2 standard (3, 15), B around 16 / 4 per wave      mle_state_packed_kernel<1, 2>
-    test_one_setting_per_lane                   1, 2 d_plus_1 (D + 1), twice (6, 30), sixty_four     mle_state_kernel<1, 2>, r_operator_tab
-    test_first_staged_design                    1, 2 sixty_five (65)                                 mle_state_kernel<1, 2>, r_operator_elem
-    test_three_qubit_variants                   3 standard (63), with_identity (64), hedged/maxent   mle_state_kernel<3>, r_operator_tab
+    test_one_setting_per_lane                   1, 2 d_plus_1 (D + 1), twice (6, 30), sixty_four     mle_state_kernel<1, 2>, r_operator_resident
+    test_first_staged_design                    1, 2 sixty_five (65)                                 mle_state_kernel<1, 2>, r_operator_strided
+    test_three_qubit_variants                   3 standard (63), with_identity (64), hedged/maxent   mle_state_kernel<3>, r_operator_resident
     test_three_qubit_plain                      3 standard (63), with_identity (64)                  mle_state_plain3_kernel
     test_four_qubit_coefficients                4 standard (255), signed                             mle_state_big_kernel<4>
     test_linear_inversion_r_and_likelihood      every design above, and 3 twice (126)                linv_state_kernel, r_operator_kernel,
@@ -120,7 +120,7 @@ def test_packed_partial_and_full_waves(gpu, n, sizes, signed):
 @pytest.mark.parametrize("n", [1, 2])
 @SIGNED
 def test_one_setting_per_lane(gpu, n, kind, signed, mode):
-    """D < m <= 64 without variants: mle_state_kernel<1, 2> with the settings in registers (r_operator_tab); several lanes add
+    """D < m <= 64 without variants: mle_state_kernel<1, 2> with the settings in registers (r_operator_resident); several lanes add
     to the weight of the same Pauli operator"""
     against_the_oracle(n, kind, signed, ROW_B[n, kind], mode)
 
@@ -128,7 +128,7 @@ def test_one_setting_per_lane(gpu, n, kind, signed, mode):
 @pytest.mark.parametrize("n", [1, 2])
 @SIGNED
 def test_first_staged_design(gpu, n, signed):
-    """m = 65: the first design whose settings no longer fit the lanes (r_operator_elem, staged in LDS)"""
+    """m = 65: the first design whose settings no longer fit the lanes (r_operator_strided, staged in LDS)"""
     against_the_oracle(n, "sixty_five", signed, ROW_B[n, "sixty_five"], "plain")
 
 
@@ -136,7 +136,7 @@ def test_first_staged_design(gpu, n, signed):
 @pytest.mark.parametrize("kind", ["standard", "with_identity"])
 @SIGNED
 def test_three_qubit_variants(gpu, kind, signed, mode):
-    """hedging and the entropy penalty at 3 qubits with at most 64 settings: mle_state_kernel<3> on r_operator_tab with
+    """hedging and the entropy penalty at 3 qubits with at most 64 settings: mle_state_kernel<3> on r_operator_resident with
     PauliTables<3>, which nothing else launches; with_identity fills all 64 lanes"""
     against_the_oracle(3, kind, signed, ROW_B[3, kind], mode)
 
@@ -151,7 +151,7 @@ def test_three_qubit_plain(gpu, kind, signed, mode):
 
 @pytest.mark.parametrize("mode,maxiter", [("plain", 10), ("hedged", 6)])
 def test_four_qubit_coefficients(gpu, mode, maxiter):
-    """the coefficient branch of r_operator_big"""
+    """the coefficient branch of r_operator_strided over a workgroup"""
     against_the_oracle(4, "standard", True, ROW_B[4, "standard"], mode, maxiter)
 
 

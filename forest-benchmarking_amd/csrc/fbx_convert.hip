@@ -10,6 +10,25 @@
 
 namespace fbx {
 
+// Is an entry that a route into chi reads not finite?  From a Choi matrix (`lower`) the route reads what the reference's eigh
+// reads, the real part of the diagonal and the strict lower triangle; from a superoperator or a Pauli-Liouville matrix every
+// entry (the walk to the Choi matrix may carry it anywhere).  This thread's share of a D x D matrix, NT threads.
+template <int D, int LD, int NT>
+__device__ __forceinline__ int nonfinite_share(const cplx* a, bool lower, int t) {
+    int bad = 0;
+    for (int idx = t; idx < D * D; idx += NT) {
+        const int r = idx / D, c = idx % D;
+        const cplx v = a[r * LD + c];
+        if (!lower || r > c) bad |= !(isfinite(v.re) && isfinite(v.im));
+        else if (r == c) bad |= !isfinite(v.re);
+    }
+    return bad;
+}
+__device__ __forceinline__ void fill_nan(double* __restrict__ o, int n, int t, int nt) {
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (int idx = t; idx < n; idx += nt) o[idx] = nan;
+}
+
 // ---------------------------------------------------------------------------------------------
 // The walk: chi -> choi <-> superop <-> pauli-liouville, choi -> chi, entered from Kraus operators (straight to the Choi matrix
 // or the superoperator, whichever is nearer the target) or from a matrix.  `cur` / `nxt` are the ping-pong matrices of the
@@ -35,6 +54,15 @@ __device__ __forceinline__ void convert_walk(Ops op, int from, int to, const dou
     } else {
         load_matrix<NQ, NT, LD>(in + item * (long long)D * D * 2, cur, t);
         __syncthreads();
+        if constexpr (Ops::ABS) {
+            // A non-finite item on its way into chi gives NaN in every entry (include/fbx.h): the eigensolver's stopping test is
+            // false on a NaN or an infinite norm, so it would hand back the diagonal with the identity, and the cut below turns
+            // a NaN eigenvalue into 0 -- a finite chi matrix of something else.  Nothing is converted.
+            if (to == FBX_REP_CHI && op.nonfinite(cur, from == FBX_REP_CHOI, t)) {
+                fill_nan(out + item * (long long)D * D * 2, 2 * D * D, t, NT);
+                return;
+            }
+        }
     }
     const bool kraus_chi = (from == FBX_REP_KRAUS && to == FBX_REP_CHI);    // the Choi matrix of a Kraus set is PSD: |C| = C
     while (rep != to) {
@@ -78,6 +106,10 @@ struct WalkSmall : WalkLds<NQ, 64, (1 << (2 * NQ)) + 1> {
     static constexpr bool ABS = EIGH;
     ChoiLds<NQ> L;
     __device__ __forceinline__ void abs_choi(const cplx* a, cplx* b, int t) { abs_via_eigh<NQ>(a, b, L, 1e-9, t); }
+    __device__ __forceinline__ bool nonfinite(const cplx* a, bool lower, int t) const {        // one wavefront per item
+        constexpr int D = 1 << (2 * NQ);
+        return __ballot(nonfinite_share<D, D + 1, 64>(a, lower, t)) != 0;
+    }
 };
 template <int NQ, bool EIGH = true>
 __global__ void __launch_bounds__(64)
@@ -131,6 +163,18 @@ convert3_kernel(int from, int to, long long B, const double* __restrict__ in, in
     } else {
         load_matrix<NQ, NT, LD>(in + item * (long long)D * D * 2, cur, t);
         __syncthreads();
+        if (to == FBX_REP_CHI) {        // a non-finite item on its way into chi: NaN in every entry (convert_walk)
+            const bool wave_bad = __ballot(nonfinite_share<D, LD, NT>(cur, from == FBX_REP_CHOI, t)) != 0;
+            if ((t & 63) == 0) red[t >> 6] = wave_bad ? 1.0 : 0.0;
+            __syncthreads();
+            double any = 0.0;
+            for (int w = 0; w < NT / 64; ++w) any += red[w];
+            __syncthreads();            // red is the Jacobi's scratch next
+            if (any != 0.0) {
+                fill_nan(out + item * (long long)D * D * 2, 2 * D * D, t, NT);
+                return;
+            }
+        }
     }
     const bool kraus_chi = (from == FBX_REP_KRAUS && to == FBX_REP_CHI);
     while (rep != to) {
@@ -230,7 +274,21 @@ static int launch_convert_big(int from, int to, int64_t B, const double* in, int
 // the reference's cut, fbx_matmul_dev for V diag(|lambda|) V^H, and the kernel's linear basis change on that PSD matrix.
 __global__ void __launch_bounds__(256) abs_cut_kernel(double* __restrict__ w, long long n, double tol) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) { const double a = fabs(w[i]); w[i] = a > tol ? a : 0.0; }
+    if (i < n) { const double a = fabs(w[i]); w[i] = a <= tol ? 0.0 : a; }        // (a NaN eigenvalue stays one)
+}
+// A superoperator or a Pauli-Liouville matrix with a non-finite entry gives NaN in every entry of its chi matrix (include/fbx.h),
+// wherever the walk to the Choi matrix carried that entry -- above the diagonal fbx_eigh would not read it.  One workgroup per
+// item: a NaN into the first diagonal entry of the item's Choi matrix, and fbx_eigh's own contract does the rest.
+__global__ void __launch_bounds__(256) poison_nonfinite_kernel(const double* __restrict__ src, long long n_per_item, double* __restrict__ choi) {
+    __shared__ int any;
+    if (threadIdx.x == 0) any = 0;
+    __syncthreads();
+    const double* s = src + (long long)blockIdx.x * n_per_item;
+    int bad = 0;
+    for (long long i = threadIdx.x; i < n_per_item; i += 256) bad |= !isfinite(s[i]);
+    if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(&any, 1);
+    __syncthreads();
+    if (any && threadIdx.x == 0) choi[(long long)blockIdx.x * n_per_item] = __longlong_as_double(0x7ff8000000000000LL);
 }
 template <int NQ>
 static int convert_into_chi_big(int from, int64_t B, const double* in, double* out) {
@@ -241,7 +299,11 @@ static int convert_into_chi_big(int from, int64_t B, const double* in, double* o
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t nb = B - b0 < chunk ? B - b0 : chunk;
         const double* choi = in + (size_t)b0 * D * D * 2;
-        if (from != FBX_REP_CHOI) { const int rc = launch_convert_big<NQ>(from, FBX_REP_CHOI, nb, choi, 0, c.as<double>()); if (rc) return rc; choi = c.as<double>(); }
+        if (from != FBX_REP_CHOI) {
+            const int rc = launch_convert_big<NQ>(from, FBX_REP_CHOI, nb, choi, 0, c.as<double>()); if (rc) return rc;
+            FBX_TRY(launch_lds(poison_nonfinite_kernel, dim3((unsigned)nb), dim3(256), 0, choi, (long long)(D * D * 2), c.as<double>()));
+            choi = c.as<double>();
+        }
         { const int rc = fbx_eigh_dev((int)D, nb, choi, w.as<double>(), v.as<double>()); if (rc) return rc; }
         FBX_TRY(launch_lds(abs_cut_kernel, dim3((unsigned)((nb * D + 255) / 256)), dim3(256), 0, w.as<double>(), nb * D, 1e-9));
         { const int rc = fbx_matmul_dev((int)D, nb, v.as<double>(), 0, w.as<double>(), v.as<double>(), 1, c.as<double>()); if (rc) return rc; }

@@ -309,7 +309,16 @@ int fbx_state_log_likelihood_dev(const fbx_design* design, int64_t B, const doub
  * (choi2kraus: chi of |C|, eigenvalues within 1e-9 dropped) -- are composed from fbx_eigh_dev, fbx_matmul_dev and the
  * linear basis change (25 ms per 256 x 256 item, ~1 s per 1024 x 1024 item: complete, not fast).  Kraus sets with more
  * operators than the fused kernels stage in LDS (K x D x 16 B against 160 KiB) go through the basis-free kernel
- * (fbx_convert_general: any K) to the Choi matrix and on from there. */
+ * (fbx_convert_general: any K) to the Choi matrix and on from there.
+ * Non-finite input: on a route INTO chi from a Choi / superoperator / Pauli-Liouville matrix, an item with a NaN or an Inf in an
+ * entry the route reads is not converted.  Every entry of its output is NaN, the call returns FBX_OK, and every other item is
+ * bit-identical to the same call with a finite matrix in that place.  From a Choi matrix the route reads what the reference's
+ * eigh reads: the real parts of the diagonal and the strict lower triangle (the strict upper triangle and the diagonal's
+ * imaginary parts are never read: NaN or Inf there changes nothing).  From a superoperator or a Pauli-Liouville matrix it reads
+ * every entry.  (Left to the arithmetic, the eigensolver's stopping test is false on a NaN or an infinite norm and the cut at
+ * 1e-9 turns a NaN eigenvalue into 0: the result would be a finite chi matrix of some other input.)  The other routes are linear
+ * maps, entry by entry: a non-finite entry reaches the output entries that depend on it -- through superop <-> choi, a
+ * permutation, exactly one -- and no other item. */
 int fbx_convert(int from_rep, int to_rep, int n_qubits, int64_t B, const double* in, int K,
                 double* out);
 /* same with device pointers (buffers from fbx_malloc): the batch stays resident in HBM */

@@ -14,6 +14,11 @@
 
 namespace fbx {
 
+// Records of measured shots ([n_shots][columns] bytes: fbx_shots.hip, fbx_histogram.hip, fbx_qvolume.hip) below this many bytes
+// get a wavefront each, four records per 256-thread workgroup and no workgroup barrier; from here on a workgroup each.
+// _lib.HIST_WAVE_BYTES and tests/shots_cases.py:WAVE_BYTES restate it.
+constexpr long long FBX_RECORD_WAVE_BYTES = 16384;
+
 // ------------------------------------------------------------------ host: errors / per-thread context
 // The library is re-entrant across host threads (ctypes drops the GIL during a call): every host
 // thread that enters the library owns a context -- its HIP stream, its timer events, its cached

@@ -24,7 +24,6 @@ namespace fbx {
 
 constexpr int FBX_HIST_MAX_JOINT_K = 10;
 constexpr long long FBX_HIST_MAX_SHOTS = 2147483647ll;       // 32-bit counters in LDS
-constexpr long long FBX_HIST_WAVE_BYTES = 16384;             // records below this many bytes: a wavefront per record
 
 struct HistWave {
     unsigned hist[1 << FBX_HIST_MAX_JOINT_K];
@@ -233,7 +232,7 @@ int fbx_bit_histogram_dev(int n_cols, int64_t B, int64_t n_shots, const uint8_t*
     FBX_TRY(hist_check(n_cols, B, n_shots, d_bits, k, d_cols, kind, d_counts_out));
     if (B == 0) return FBX_OK;
     FBX_TRY(ensure_device());
-    const bool per_wave = n_shots * n_cols < FBX_HIST_WAVE_BYTES && B >= 4;
+    const bool per_wave = n_shots * n_cols < FBX_RECORD_WAVE_BYTES && B >= 4;
     const int64_t units = per_wave ? (B + 3) / 4 : B;
     const unsigned grid = (unsigned)(units < 256 * 16 ? units : 256 * 16);
 #define FBX_HIST_LAUNCH(NC) do { \

@@ -275,7 +275,7 @@ qv_count_kernel(long long B, long long n_shots, const uint8_t* __restrict__ bits
 
 template <int NQ>
 static int launch_qv_count(int64_t B, int64_t n_shots, const uint8_t* bits, const uint64_t* mask, int64_t* counts) {
-    const bool per_wave = n_shots * NQ < 16384 && B >= 4;               // short records: a wavefront per circuit (as fbx_shots.hip)
+    const bool per_wave = n_shots * NQ < FBX_RECORD_WAVE_BYTES && B >= 4;               // short records: a wavefront per circuit (as fbx_shots.hip)
     const int64_t units = per_wave ? (B + 3) / 4 : B;
     const unsigned grid = (unsigned)(units < 256 * 16 ? units : 256 * 16);
     if (per_wave)

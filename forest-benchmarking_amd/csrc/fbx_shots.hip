@@ -9,6 +9,22 @@
 
 namespace fbx {
 
+// (mean, var) of one setting from its count of -1 outcomes, times the term's coefficient
+__device__ __forceinline__ void shots_moments(long long n_minus, long long n_shots, double coef, bool identity, int beta_prior,
+                                              double& mean, double& var) {
+    const long long n_plus = n_shots - n_minus;
+    if (identity) { mean = coef; var = 0.0; }                    // identity term (:826-827)
+    else if (beta_prior) {                                       // :837-846
+        const double a = (double)n_plus + 1.0, bb = (double)n_minus + 1.0;
+        const double bm = a / (a + bb), bv = a * bb / ((a + bb) * (a + bb) * (a + bb + 1.0));
+        mean = coef * (2.0 * bm - 1.0); var = coef * coef * 4.0 * bv;
+    } else {                                                     // :848-850
+        const double m = ((double)n_plus - (double)n_minus) / (double)n_shots;
+        mean = coef * m;
+        var = coef * coef * (1.0 - m * m) / (double)n_shots;
+    }
+}
+
 // number of shots with odd parity in one 64-bit word holding 8 / NQB shots of NQB masked bytes
 template <int NQB>
 __device__ __forceinline__ int odd_shots(unsigned long long x) {
@@ -129,19 +145,8 @@ __device__ __forceinline__ void shots_wave_pipeline(long long first, long long s
         for (int k = 0; k < VPL; ++k) cnt += odd_shots<NQB>(cur[k].x & pat) + odd_shots<NQB>(cur[k].y & pat);
         const long long n_minus = (long long)wave_sum((double)cnt);
         if (lane == 0) {
-            const long long n_plus = n_shots - n_minus;
-            const double coef = coefs ? coefs[s] : 1.0;
             double mean, var;
-            if (pat == 0) { mean = coef; var = 0.0; }
-            else if (beta_prior) {
-                const double a = (double)n_plus + 1.0, bb = (double)n_minus + 1.0;
-                const double bm = a / (a + bb), bv = a * bb / ((a + bb) * (a + bb) * (a + bb + 1.0));
-                mean = coef * (2.0 * bm - 1.0); var = coef * coef * 4.0 * bv;
-            } else {
-                const double m = ((double)n_plus - (double)n_minus) / (double)n_shots;
-                mean = coef * m;
-                var = coef * coef * (1.0 - m * m) / (double)n_shots;
-            }
+            shots_moments(n_minus, n_shots, coefs ? coefs[s] : 1.0, pat == 0, beta_prior, mean, var);
             mean_out[s] = mean; var_out[s] = var;
         }
 #pragma unroll
@@ -220,19 +225,8 @@ shots_pipe_packed_kernel(long long n_settings, long long n_shots, const uint8_t*
         }
         const long long n_minus = (long long)wave_sum((double)cnt);
         if (lane == 0) {
-            const long long n_plus = n_shots - n_minus;
-            const double coef = coefs ? coefs[s] : 1.0;
             double mean, var;
-            if (mbits == 0) { mean = coef; var = 0.0; }
-            else if (beta_prior) {
-                const double a = (double)n_plus + 1.0, bb = (double)n_minus + 1.0;
-                const double bm = a / (a + bb), bv = a * bb / ((a + bb) * (a + bb) * (a + bb + 1.0));
-                mean = coef * (2.0 * bm - 1.0); var = coef * coef * 4.0 * bv;
-            } else {
-                const double m = ((double)n_plus - (double)n_minus) / (double)n_shots;
-                mean = coef * m;
-                var = coef * coef * (1.0 - m * m) / (double)n_shots;
-            }
+            shots_moments(n_minus, n_shots, coefs ? coefs[s] : 1.0, mbits == 0, beta_prior, mean, var);
             mean_out[s] = mean; var_out[s] = var;
         }
 #pragma unroll
@@ -287,19 +281,8 @@ shots_kernel(int n, long long n_settings, long long n_shots, const uint8_t* __re
             n_minus = part[0] + part[1] + part[2] + part[3];
         }
         if (tid == 0) {
-            const long long n_plus = n_shots - n_minus;
-            const double coef = coefs ? coefs[s] : 1.0;
             double mean, var;
-            if (!any) { mean = coef; var = 0.0; }                       // identity term (:826-827)
-            else if (beta_prior) {                                       // :837-846
-                const double a = (double)n_plus + 1.0, bb = (double)n_minus + 1.0;
-                const double bm = a / (a + bb), bv = a * bb / ((a + bb) * (a + bb) * (a + bb + 1.0));
-                mean = coef * (2.0 * bm - 1.0); var = coef * coef * 4.0 * bv;
-            } else {                                                     // :848-850
-                const double m = ((double)n_plus - (double)n_minus) / (double)n_shots;
-                mean = coef * m;
-                var = coef * coef * (1.0 - m * m) / (double)n_shots;
-            }
+            shots_moments(n_minus, n_shots, coefs ? coefs[s] : 1.0, !any, beta_prior, mean, var);
             mean_out[s] = mean; var_out[s] = var;
         }
     }
@@ -461,7 +444,7 @@ int fbx_shots_to_moments_dev(int n_qubits, int64_t n_settings, int64_t n_shots, 
     FBX_TRY(ensure_device());
     if (n_settings == 0) return FBX_OK;
     // short records (below 16 KB per setting): a wavefront per setting, four settings per workgroup
-    const bool per_wave = n_shots * n_qubits < 16384 && n_settings >= 4;
+    const bool per_wave = n_shots * n_qubits < FBX_RECORD_WAVE_BYTES && n_settings >= 4;
     const int64_t units = per_wave ? (n_settings + 3) / 4 : n_settings;
     const unsigned grid = (unsigned)(units < 256 * 16 ? units : 256 * 16);
     // records that are whole 16-byte vectors, at most eight per lane, from a 16-byte aligned base: the pipelined form

@@ -25,7 +25,7 @@ FIT_PREPARE_RB, FIT_PREPARE_UNITARITY = 0, 1
 HIST_JOINT, HIST_WEIGHT = 0, 1
 HIST_MAX_JOINT_K = 10
 HIST_MAX_SHOTS = 2 ** 31 - 1
-HIST_WAVE_BYTES = 16384         # records below this many bytes get a wavefront each (csrc/fbx_histogram.hip)
+HIST_WAVE_BYTES = 16384         # records below this many bytes get a wavefront each (FBX_RECORD_WAVE_BYTES, csrc/fbx_common.hpp)
 CLIFFORD_NONE = 0xFFFFFFFF      # no element: "no interleaved gate" / "no such index" (include/fbx.h)
 RB_MAX_NOISE_PTMS = 16
 RB_STANDARD, RB_UNITARITY = 0, 1        # modes of fbx_rb_acquire

@@ -4,7 +4,8 @@ state estimators and measures for 1-5 qubits incl. designs of more than 64 setti
 Kraus sweep kernel (both forms of the 3-qubit ones, batches past the persistent grid, Kraus counts on either side of each kernel
 switch), the Kraus-pair / twirl / partial-trace / apply / fidelity / linear-inversion entry points, and fbx_eigh / fbx_matmul /
 fbx_choi2kraus at every size class, and the simulated acquisitions (tomography plain / grouped / symmetrized / calibration, DFE,
-RPE) on both of their work splits.
+RPE) on both of their work splits, and the four readers of shot records (shots to moments, bit histograms, RPE from shots, QV heavy
+counts) on both of their teams, host form and _dev form at a 1-byte offset.
 usage: python scripts/compare_libs.py libA.so libB.so      (names inside forest-benchmarking_amd/; FBX_LIBRARY selects each build)"""
 import os, subprocess, sys, hashlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -219,6 +220,71 @@ for B in (3, LANE // 2):
         sim_hash(lambda g, **kw: rpe.simulate_rpe_batch(g, num_depths=1, num_shots=37, return_probabilities=True, return_histograms=True,
                                                         return_records=records, **kw),
                  gate, "flips", lambda: np.random.RandomState(70).uniform(0, 0.2, (B, 1, 2)))
+# the four readers of shot records (fbx_shots, fbx_histogram, fbx_rpe, fbx_qvolume), one hash per entry point: records of 33 shots (a run
+# and a tail, and for odd widths an odd number of bytes, so that later records start off the 16-byte grid and have a head), B = 3 (a
+# workgroup per record) and B = 5 (a wavefront per record), the host form and the _dev form with the records 1 byte into their buffer
+import ctypes as C
+from fbx import quantum_volume as qv
+U8, U64, I64 = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
+rr = np.random.default_rng(16)
+def u8(a): return a.ctypes.data_as(U8)
+def shifted(a):                       # a device copy of a that starts 1 byte into its allocation
+    buf = _lib.DeviceBuffer(a.nbytes + 16)
+    _lib.check(lib.fbx_memcpy_h2d(buf.ptr.value + 1, a.ctypes.data, a.nbytes))
+    return buf, buf.ptr.value + 1
+def fetch(bufs_shapes, *inputs):       # the outputs as arrays; they and the inputs named are freed
+    _lib.synchronize()
+    arrays = [b.to_array(dt, shape) for b, dt, shape in bufs_shapes]
+    for b in [b for b, _, _ in bufs_shapes] + list(inputs):
+        b.free()
+    return arrays
+parts = {"shots": [], "hist": [], "rpe": [], "qv": []}
+for B in (3, 5):
+    for n in (2, 3, 9):
+        bits = rr.integers(0, 256, size=(B, 33, n), dtype=np.uint8)
+        mask = rr.integers(0, 2, size=(B, n), dtype=np.uint8); mask[0] = 0
+        coefs = rr.uniform(-2, 2, B)
+        d_bits, at = shifted(bits)
+        d_mask, d_coefs = _lib.DeviceBuffer.from_array(mask), _lib.DeviceBuffer.from_array(coefs)
+        for prior in (0, 1):
+            mean, var = np.empty(B), np.empty(B)
+            _lib.check(lib.fbx_shots_to_moments(n, B, 33, u8(bits), u8(mask), _lib.dptr(coefs), prior, _lib.dptr(mean), _lib.dptr(var)))
+            d_mean, d_var = _lib.DeviceBuffer(B * 8), _lib.DeviceBuffer(B * 8)
+            _lib.check(lib.fbx_shots_to_moments_dev(n, B, 33, at, d_mask.ptr, d_coefs.ptr, prior, d_mean.ptr, d_var.ptr))
+            parts["shots"] += [mean, var] + fetch([(d_mean, np.float64, (B,)), (d_var, np.float64, (B,))])
+        for b in (d_bits, d_mask, d_coefs):
+            b.free()
+    for n in (1, 3, 11):
+        bits = rr.integers(0, 256, size=(B, 33, n), dtype=np.uint8)
+        k = min(n, 10)
+        for kind in (0, 1):
+            bins = (1 << k) if kind == 0 else k + 1
+            counts = np.empty((B, bins), dtype=np.int64)
+            _lib.check(lib.fbx_bit_histogram(n, B, 33, u8(bits), k, None, 1, None, kind, counts.ctypes.data_as(I64)))
+            d_bits, at = shifted(bits)
+            d_counts = _lib.DeviceBuffer(B * bins * 8)
+            _lib.check(lib.fbx_bit_histogram_dev(n, B, 33, at, k, None, 1, None, kind, d_counts.ptr))
+            parts["hist"] += [counts] + fetch([(d_counts, np.int64, (B, bins))], d_bits)
+    for n, col, zcol in ((1, 0, -1), (3, 2, 0), (8, 0, 7)):
+        xb, yb = rr.integers(0, 256, size=(B, 2, 33, n), dtype=np.uint8), rr.integers(0, 256, size=(B, 2, 33, n), dtype=np.uint8)
+        phase, depth, bloch, mom = np.empty(B), np.empty(B, dtype=np.int32), np.empty((B, 2, 2)), np.empty((B, 2, 4))
+        _lib.check(lib.fbx_rpe_from_shots(n, B, 2, 33, u8(xb), u8(yb), col, zcol, 1, _lib.dptr(phase), _lib.iptr(depth), _lib.dptr(bloch),
+                                          _lib.dptr(mom)))
+        (d_x, at_x), (d_y, at_y) = shifted(xb), shifted(yb)
+        d_p, d_d, d_m = _lib.DeviceBuffer(B * 8), _lib.DeviceBuffer(B * 4), _lib.DeviceBuffer(B * 2 * 4 * 8)
+        _lib.check(lib.fbx_rpe_from_shots_dev(n, B, 2, 33, at_x, at_y, col, zcol, 1, d_p.ptr, d_d.ptr, None, d_m.ptr))
+        parts["rpe"] += [phase, depth, bloch, mom] + fetch([(d_p, np.float64, (B,)), (d_d, np.int32, (B,)), (d_m, np.float64, (B, 2, 4))],
+                                                           d_x, d_y)
+    for n in (2, 9):
+        bits = rr.integers(0, 256, size=(B, 33, n), dtype=np.uint8)
+        mask = qv.pack_heavy_mask(rr.integers(0, 2, size=(B, 1 << n)).astype(bool))
+        counts = np.empty(B, dtype=np.int64)
+        _lib.check(lib.fbx_qv_count_heavy(n, B, 33, u8(bits), mask.ctypes.data_as(U64), counts.ctypes.data_as(I64)))
+        d_bits, at = shifted(bits)
+        d_mask, d_counts = _lib.DeviceBuffer.from_array(mask), _lib.DeviceBuffer(B * 8)
+        _lib.check(lib.fbx_qv_count_heavy_dev(n, B, 33, at, d_mask.ptr, d_counts.ptr))
+        parts["qv"] += [counts] + fetch([(d_counts, np.int64, (B,))], d_bits, d_mask)
+out += [H(*parts[k]) for k in ("shots", "hist", "rpe", "qv")]
 print(" ".join(out))
 '''
 res = []

@@ -47,6 +47,7 @@ def main():
     _lib.set_device(0)
     lib = _lib.lib()
     sink = open(args.out, "w") if args.out else None
+    # (scripts/ab_shot_records.py times these sizes too: keep its copy in step)
     for kind, k in ((0, 1), (0, 2), (0, 3), (0, 10), (1, 5), (1, 17)):
         for shots, B in ((1000, 4096), (10 ** 6, 64)):
             rng = np.random.default_rng([kind, k, shots])

@@ -68,6 +68,7 @@ def baseline(n, perms, gates, count):
 
 def main():
     ap = argparse.ArgumentParser()
+    # (scripts/ab_shot_records.py times these sizes too: keep its copy in step)
     ap.add_argument("--widths", type=int, nargs="+", default=list(range(2, 14)))
     ap.add_argument("--batches", type=int, nargs="+", default=[100, 4096])
     ap.add_argument("--reps", type=int, default=7)

@@ -40,6 +40,7 @@ def timed_dev(launch, reps):
 
 def main():
     ap = argparse.ArgumentParser()
+    # (scripts/ab_shot_records.py times these sizes too: keep its copy in step)
     ap.add_argument("--batch", type=int, default=100000)
     ap.add_argument("--depths", type=int, default=10)
     ap.add_argument("--shots", type=int, default=500)

@@ -7,6 +7,7 @@ import numpy as np
 from fbx import _lib
 _lib.set_device(0)
 lib = _lib.lib()
+# (scripts/ab_shot_records.py times these sizes too: keep its copy in step)
 for n, S, shots in ([(int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]))] if len(sys.argv) > 3 else
                     [(2, 540 * 256, 1000), (2, 540 * 64, 10000), (3, 4032 * 16, 1000), (3, 4032 * 16, 1003), (8, 65536, 1000), (5, 65536, 1000), (6, 65536, 1000), (7, 32768, 1001), (9, 32768, 1000)]):
     rs = np.random.RandomState(1)

@@ -14,20 +14,20 @@ import numpy as np
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the launcher, fbx_shots_to_moments_dev (csrc/fbx_shots.hip); every constant once, beside the line it restates
 # ---------------------------------------------------------------------------------------------------------------------------------
-WAVE_BYTES = 16384          # :464  per_wave = n_shots * n_qubits < 16384 && n_settings >= 4
-WAVE_MIN_SETTINGS = 4       # :464
-WAVES_PER_GROUP = 4         # :465  units = per_wave ? (n_settings + 3) / 4 : n_settings   (and :158, :171, :253: blockIdx.x * 4 + wave)
-GRID_CAP = 256 * 16         # :466  grid = min(units, 256 * 16) = 4096 workgroups
-PIPE_BYTES = 8192           # :470  bytes <= 8192: at most eight 16-byte vectors per lane
-VEC_BYTES = 16              # :469  (bytes & 15) == 0 && (d_bits & 15) == 0
-LANES = 64                  # :472  vpl = (bytes / 16 + 63) / 64
-PACKED_ALIGN = 8            # :481-482  (bytes & 7) == 0 && (d_bits & 7) == 0
-PACKED_RUN = 16             # :482  n_shots / 16: runs of 16 shots
-PACKED_RUNS_ONE = 64        # :483  one = n_shots / 16 <= 64    -> RPL = 1
-PACKED_RUNS_MAX = 128       # :482  n_shots / 16 <= 128         -> RPL = 2
-VEC_N = (1, 2, 4, 8)        # :469, :264
-PACKED_PIPE_N = (3, 5)      # :481
-PACKED_N = (3, 5, 6, 7)     # :270
+WAVE_BYTES = 16384          # :447  per_wave = n_shots * n_qubits < FBX_RECORD_WAVE_BYTES (csrc/fbx_common.hpp) && n_settings >= 4
+WAVE_MIN_SETTINGS = 4       # :447
+WAVES_PER_GROUP = 4         # :448  units = per_wave ? (n_settings + 3) / 4 : n_settings   (and :163, :176, :247: blockIdx.x * 4 + wave)
+GRID_CAP = 256 * 16         # :449  grid = min(units, 256 * 16) = 4096 workgroups
+PIPE_BYTES = 8192           # :453  bytes <= 8192: at most eight 16-byte vectors per lane
+VEC_BYTES = 16              # :452  (bytes & 15) == 0 && (d_bits & 15) == 0
+LANES = 64                  # :455  vpl = (bytes / 16 + 63) / 64
+PACKED_ALIGN = 8            # :464-465  (bytes & 7) == 0 && (d_bits & 7) == 0
+PACKED_RUN = 16             # :465  n_shots / 16: runs of 16 shots
+PACKED_RUNS_ONE = 64        # :466  one = n_shots / 16 <= 64    -> RPL = 1
+PACKED_RUNS_MAX = 128       # :465  n_shots / 16 <= 128         -> RPL = 2
+VEC_N = (1, 2, 4, 8)        # :452, :258
+PACKED_PIPE_N = (3, 5)      # :464
+PACKED_N = (3, 5, 6, 7)     # :264
 SECOND_TRIP_WAVE = WAVES_PER_GROUP * GRID_CAP + 5           # 16389 settings: five wavefronts make a second trip
 SECOND_TRIP_GROUP = GRID_CAP + 5                            # 4101 settings: five workgroups make a second trip
 
@@ -43,33 +43,33 @@ class Route(NamedTuple):
 
 
 def record_paths(n, S, shots, base_offset=0):
-    """the count path of every record in shots_kernel (:262-277), by the record's own alignment"""
+    """the count path of every record in shots_kernel (:256-271), by the record's own alignment"""
     out = []
     for s in range(S):
         addr = base_offset + s * shots * n
-        if n in VEC_N and addr % VEC_BYTES == 0:                                       # :262, :264
+        if n in VEC_N and addr % VEC_BYTES == 0:                                       # :256, :258
             out.append("vec")
-        elif n in PACKED_N and addr % PACKED_ALIGN == 0:                               # :270
+        elif n in PACKED_N and addr % PACKED_ALIGN == 0:                               # :264
             out.append("packed")
-        else:                                                                          # :275
+        else:                                                                          # :269
             out.append("generic")
     return out
 
 
 def route(n, S, shots, base_offset=0):
-    nbytes = shots * n                                                                 # :468
-    per_wave = nbytes < WAVE_BYTES and S >= WAVE_MIN_SETTINGS                          # :464
-    units = -(-S // WAVES_PER_GROUP) if per_wave else S                                # :465
-    second = units > GRID_CAP                                                          # :466 with the loops at :124, :193, :255
-    if per_wave and n in VEC_N and nbytes % VEC_BYTES == 0 and nbytes <= PIPE_BYTES and base_offset % VEC_BYTES == 0:   # :469-470
-        vpl = -(-(nbytes // VEC_BYTES) // LANES)                                       # :472
-        cls = 1 if vpl <= 1 else 2 if vpl == 2 else 4 if vpl <= 4 else 8               # :475-476
+    nbytes = shots * n                                                                 # :451
+    per_wave = nbytes < WAVE_BYTES and S >= WAVE_MIN_SETTINGS                          # :447
+    units = -(-S // WAVES_PER_GROUP) if per_wave else S                                # :448
+    second = units > GRID_CAP                                                          # :449 with the loops at :140, :198, :249
+    if per_wave and n in VEC_N and nbytes % VEC_BYTES == 0 and nbytes <= PIPE_BYTES and base_offset % VEC_BYTES == 0:   # :452-453
+        vpl = -(-(nbytes // VEC_BYTES) // LANES)                                       # :455
+        cls = 1 if vpl <= 1 else 2 if vpl == 2 else 4 if vpl <= 4 else 8               # :458-459
         return Route(f"pipe<{n},{cls}>", frozenset(), second)
     runs = shots // PACKED_RUN
     if (per_wave and n in PACKED_PIPE_N and nbytes % PACKED_ALIGN == 0 and base_offset % PACKED_ALIGN == 0
-            and 1 <= runs <= PACKED_RUNS_MAX):                                         # :481-482
-        return Route(f"packed<{n},{1 if runs <= PACKED_RUNS_ONE else 2}>", frozenset(), second)                         # :483
-    return Route("wave" if per_wave else "workgroup", frozenset(record_paths(n, S, shots, base_offset)), second)       # :490-495
+            and 1 <= runs <= PACKED_RUNS_MAX):                                         # :464-465
+        return Route(f"packed<{n},{1 if runs <= PACKED_RUNS_ONE else 2}>", frozenset(), second)                         # :466
+    return Route("wave" if per_wave else "workgroup", frozenset(record_paths(n, S, shots, base_offset)), second)       # :473-478
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -33,6 +33,8 @@ RB_ACQUIRE_MAX_DEPTHS = 256
 DFE_MAX_CLASSES = 16
 DFE_NOISELESS = 255             # noise class of a gate without noise (include/fbx.h)
 RPE_SIM_LANE_MIN_UNITS = 131072 # from this many (item, depth, basis) units on a lane takes a unit (csrc/fbx_rpe_sim.hip)
+SPEC_LANE_MIN_UNITS = 131072    # ... and of fbx_spec_acquire: FBX_TOMO_LANE_MIN_UNITS (item, point) units (csrc/fbx_sim_shared.hpp)
+SPEC_MAX_POINTS = 65536         # points per item of fbx_spec_acquire
 
 
 class FbxError(RuntimeError):
@@ -223,6 +225,8 @@ PROTOTYPES = {
                            _vp, _vp, _vp, _vp, _vp, _vp],
     "fbx_rb_depth_means": [_i64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp],
     "fbx_rb_depth_means_dev": [_i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
+    "fbx_spec_acquire": [_i64, C.c_int, _dp, _i64, _dp, _dp, _i64, C.c_uint64, _i64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip],
+    "fbx_spec_acquire_dev": [_i64, C.c_int, _vp, _i64, _vp, _vp, _i64, C.c_uint64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fbx_clifford_conjugate": [C.c_int, _i64, _u32p, C.c_int, _i64, _u64p, _u64p, _u8p, _u64p, _u64p, _u8p],
     "fbx_clifford_conjugate_dev": [C.c_int, _i64, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     "fbx_dfe_settings": [C.c_int, C.c_int, _i64, C.c_uint64, _i64, _u32p, _i64, _u64p, _u64p, _u64p, _u64p, _u64p, _u8p],

@@ -832,3 +832,46 @@ def restate_rb_counts(probs, shots, mode, seed, first_item=0):
         expect[:, :, col] = mean
         std_err[:, :, col] = np.sqrt((1.0 - mean * mean) / float(N))
     return hist, expect, std_err
+
+
+# --------------------------------------------------------------------------------------------------
+# fbx_spec_acquire (include/fbx.h) on the host: the curve mirrored in numpy, the shots restated in integers.
+# --------------------------------------------------------------------------------------------------
+SPECTROSCOPY_KEY_TAG = 0x51535043        # "QSPC": the shots of fbx_spec_acquire
+
+
+def spectroscopy_probabilities(x, params, flips=None):
+    """Steps 1-3 of the contract of ``fbx_spec_acquire`` in numpy, operation for operation: ``x`` [K] (shared) or [B, K],
+    ``params`` [B, 6] = (amplitude, decay_time, gauss_time, omega, offset, baseline), ``flips`` None, [2] or [B, 2] -> the
+    probabilities of reading 1, [B, K], unclamped: env = exp(-(x / decay_time) - (x / gauss_time) (x / gauss_time)), p_true =
+    baseline + (amplitude env) cos(omega x + offset), p_read = f0 (1 - p_true) + (1 - f1) p_true.  The exact expectation of the
+    measured Pauli is ``1 - 2 * p_read``.  numpy rounds every operation on its own, as the device does; the two differ through
+    their exp and cos only."""
+    x = np.asarray(x, dtype=np.float64)
+    params = np.atleast_2d(np.asarray(params, dtype=np.float64))
+    if params.ndim != 2 or params.shape[1] != 6 or x.ndim not in (1, 2) or (x.ndim == 2 and x.shape[0] != params.shape[0]):
+        raise ValueError("need params [B, 6] and x [K] or [B, K]")
+    xs = x if x.ndim == 2 else x[None, :]
+    amplitude, decay_time, gauss_time, omega, offset, baseline = (params[:, j:j + 1] for j in range(6))
+    with np.errstate(all="ignore"):
+        env = np.exp(-(xs / decay_time) - (xs / gauss_time) * (xs / gauss_time))
+        arg = omega * xs + offset
+        p = baseline + (amplitude * env) * np.cos(arg)
+        if flips is not None:
+            f = np.broadcast_to(np.asarray(flips, dtype=np.float64), (params.shape[0], 2))
+            f0, f1 = f[:, 0:1], f[:, 1:2]
+            p = f0 * (1 - p) + (1 - f1) * p
+    return p
+
+
+def restate_spectroscopy_counts(probabilities, shots, seed, first_item=0):
+    """Steps 4-5 of the contract of ``fbx_spec_acquire`` restated on the host, in integers, from the probabilities it reports
+    (``prob_out`` [B, K]): mu = 1 - 2 p, t = floor(clamp(0.5 mu + 0.5, 0, 1) 2^32), and shot s of point k counts +1 iff word
+    ``s & 3`` of the Philox4x32-10 block with counter (gid low, gid high, k, s >> 2) and key (seed low ^ 0x51535043, seed high) is
+    below t, gid = first_item + item -- ``restate_dfe_counts`` under this simulator's key tag.  Returns ``(expectations, std_errs,
+    counts, k_plus)``, all [B, K]; ``shots`` None or 0: (mu, 0, 0, 0), nothing drawn."""
+    mu = 1 - 2 * np.atleast_2d(np.asarray(probabilities, dtype=np.float64))
+    if shots is None or int(shots) == 0:
+        return mu, np.zeros_like(mu), np.zeros_like(mu), np.zeros(mu.shape, dtype=np.int64)
+    e, counts, s, k_plus = restate_dfe_counts(mu, 1.0, shots, seed, first_item, key_tag=SPECTROSCOPY_KEY_TAG)
+    return e, s, counts, k_plus

@@ -1212,6 +1212,53 @@ int fbx_rb_depth_means(int64_t E, int S, int K, int C, const double* values, con
 int fbx_rb_depth_means_dev(int64_t E, int S, int K, int C, const double* d_values, const double* d_seq_std_errs, double* d_mean_out,
                            double* d_std_err_out);
 
+/* ---------------------------------------------------------------- qubit spectroscopy, acquisition (qubit_spectroscopy.py)
+ * fbx_spec_acquire: what do_t1_or_t2, acquire_rabi_data and acquire_cz_phase_ramsey_data (qubit_spectroscopy.py:81-112, 325-356,
+ * 421-447) get from a QuantumComputer, for B experiments (a qubit each) of K points in one launch: the probability of reading 1
+ * from a physical curve and the readout flips, the shots of every point, and the bit statistics the fit front ends read.
+ *
+ * Inputs.  x: the K points (delay times, rotation angles), [K] shared by the batch (x_stride = 0) or [B][K] (x_stride = K), as in
+ * fbx_curve_fit.  params [B][6] = (amplitude, decay_time, gauss_time, omega, offset, baseline).  flips [B][2] or NULL: [0] =
+ * P(read 1 | 0), [1] = P(read 0 | 1).  n_shots: the shots of every point; 0 = the exact expectations, no shots.  seed,
+ * first_item: as in fbx_tomo_simulate; gid = first_item + b.
+ *
+ * Outputs, each may be NULL, not all; every one is [B][K] double but status_out [B] int32.
+ *
+ * Per item b and point k, all in fp64, every operation but exp and cos rounded once on its own (no fused multiply-adds), so
+ * that numpy doing the same operations in the same order differs through the two functions only:
+ *  1. ENVELOPE.  env = exp(-(x / decay_time) - (x / gauss_time) * (x / gauss_time)).  +inf is allowed for either time; its term
+ *     is then 0.
+ *  2. CURVE.  arg = omega * x + offset;  p_true = baseline + (amplitude * env) * cos(arg).
+ *  3. READOUT.  Without flips p_read = p_true; with flips p_read = f0 * (1 - p_true) + (1 - f1) * p_true.  prob_out = p_read,
+ *     unclamped.
+ *  4. MEAN.  mu = 1 - 2 * p_read, the expectation of the measured Pauli (bit 1 = eigenvalue -1).  exact_out = mu.
+ *  5. SHOTS.  The unit of fbx_tomo_simulate with coefficient 1: t = floor(clamp(0.5 mu + 0.5, 0, 1) 2^32); shot s of n_shots
+ *     counts +1 iff word s & 3 of the Philox4x32-10 block with counter (gid low, gid high, k, s >> 2) and key (seed low ^
+ *     0x51535043, seed high) is below t; the tag "QSPC" keeps the stream apart from every other simulator's under one seed.
+ *     t = 0 and t = 2^32 (p_read >= 1, p_read <= 0) give all -1 / all +1 without draws.  expect_out = (k_plus - k_minus) / N,
+ *     std_err_out = sqrt(4 k_plus k_minus / N) / N, counts_out = N.
+ *     n_shots = 0: expect_out = mu, std_err_out = 0, counts_out = 0, and nothing is drawn.
+ *  6. BIT FORM, what the fit front ends of fbx/qubit_spectroscopy.py build from (expectation, standard error), bit for bit:
+ *     bit_out = ((-1 * expect) + 1) / 2, the estimated probability of reading 1;  bit_err_out = sqrt((std_err * std_err) / 4).
+ * A value depends on (seed, gid, k), the item's inputs and n_shots only: not on B, the item's position in the batch or the
+ * launch shape; a batch is cut with first_item.  From B K >= 131072 units on a lane takes a unit, below that a wavefront; both
+ * give the same bits.
+ *
+ * A poisoned item -- a non-finite amplitude, omega, offset or baseline; a decay_time or gauss_time that is not > 0 (NaN included;
+ * +inf is fine); a non-finite x among its K points; a flip outside [0, 1] or NaN -- gets status 1, NaN in every double output
+ * and counts_out = n_shots; its neighbours are bit-identical to a clean call.  A p_read outside [0, 1] is not poison: it is
+ * clamped for the threshold only.
+ * FBX_ERR_BAD_ARG before any buffer is touched: B < 0, n_shots outside 0 .. 2^32 - 1, first_item < 0, K outside 1 .. 65536,
+ * x_stride neither 0 nor K, NULL x or params with B > 0, every output NULL.  B == 0: nothing is done.
+ * The _dev form enqueues on the calling thread's stream and does not synchronise. */
+int fbx_spec_acquire(int64_t B, int K, const double* x, int64_t x_stride, const double* params, const double* flips, int64_t n_shots,
+                     uint64_t seed, int64_t first_item, double* prob_out, double* exact_out, double* expect_out, double* std_err_out,
+                     double* counts_out, double* bit_out, double* bit_err_out, int32_t* status_out);
+int fbx_spec_acquire_dev(int64_t B, int K, const double* d_x, int64_t x_stride, const double* d_params, const double* d_flips,
+                         int64_t n_shots, uint64_t seed, int64_t first_item, double* d_prob_out, double* d_exact_out,
+                         double* d_expect_out, double* d_std_err_out, double* d_counts_out, double* d_bit_out, double* d_bit_err_out,
+                         int32_t* d_status_out);
+
 /* ---------------------------------------------------------------- Clifford circuits and direct fidelity estimation, 1..64 qubits
  * The experiment generators of direct_fidelity_estimation.py:15-182 and the noisy expectations of their settings for a Clifford
  * circuit with Pauli noise, exact in the Heisenberg picture: the observable walks backwards through the circuit as a signed Pauli

@@ -246,6 +246,10 @@ PROTOTYPES = {
     "fbx_clifford_sample_shots": [C.c_int, _i64, _u32p, _u8p, C.c_int, _u64p, _i64, _i64, _dp, _dp, C.c_uint64, _i64, _u8p, _u64p,
                                   _ip],
     "fbx_clifford_sample_shots_dev": [C.c_int, _i64, _vp, _vp, C.c_int, _vp, _i64, _i64, _vp, _vp, C.c_uint64, _i64, _vp, _vp, _vp],
+    "fbx_reversible_sample_shots": [C.c_int, _i64, _u32p, _u8p, C.c_int, _i64, _u64p, C.c_int, _u8p, _u64p, _i64, _i64, _dp, _dp,
+                                    C.c_uint64, _i64, _i64, _u8p, _u64p, _i64p, _ip],
+    "fbx_reversible_sample_shots_dev": [C.c_int, _i64, _vp, _vp, C.c_int, _i64, _vp, C.c_int, _vp, _vp, _i64, _i64, _vp, _vp,
+                                        C.c_uint64, _i64, _i64, _vp, _vp, _vp, _vp],
 }
 
 

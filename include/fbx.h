@@ -1466,6 +1466,82 @@ int fbx_clifford_sample_shots_dev(int n_qubits, int64_t G, const uint32_t* d_gat
                                   const double* d_readout_flip, uint64_t seed, int64_t first_item, uint8_t* d_bits_out,
                                   uint64_t* d_words_out, int32_t* d_status_out);
 
+/* ---------------------------------------------------------------- shots of a noisy reversible circuit: classical bits, 1..64 qubits
+ * Measured bitstrings of a circuit that only ever holds a product of Z or X eigenstates and whose gates act classically on them
+ * (csrc/fbx_reversible.hip): the experiment half of classical_logic/ripple_carry_adder.py (adder,
+ * get_n_bit_adder_results).  CCNOT is not Clifford, so the Pauli frames above do not apply; a shot is instead ONE 64-bit word
+ * of classical bits, bit q = the bit qubit q holds, and which basis a qubit holds its bit in (Z: |0>, |1>; X: |+>, |->) is a
+ * static property of the circuit that fbx.classical_logic.reversible.encode_reversible resolves into the micro-op words below.
+ *
+ * THE WORD (uint32):
+ *   bits  0..2   micro-op, FBX_REV_*
+ *   bits  3..4   k = the number of qubits of the gate, 1..3: its operands are q0 .. q(k-1), all different
+ *   bits  5..10  q0, bits 11..16 q1, bits 17..22 q2 (0 when the gate has no such operand)
+ *   bits 23..25  for operand 0, 1, 2: 1 when the qubit holds its bit in X AFTER the gate -- a Pauli error flips it through its Z
+ *                part; 0: it holds it in Z and a Pauli error flips it through its X part (0 when there is no such operand)
+ *   bits 26..31  XIN only: the bit of the unit's input word that decides whether the gate exists (0 otherwise)
+ * FBX_REV_SITE    no change of a bit (H; X on a bit held in X; CZ on two bits held in Z): an error site only
+ * FBX_REV_NOT     bit q0 ^= 1                    (X on a bit held in Z), k = 1
+ * FBX_REV_XOR     bit q0 ^= bit q1               (CNOT(c, t) in Z: q0 = t, q1 = c; in X: q0 = c, q1 = t; CZ on a Z-held and an
+ *                                                 X-held bit: q0 = the X-held one, q1 = the Z-held one), k = 2
+ * FBX_REV_ANDXOR  bit q0 ^= bit q1 & bit q2      (CCNOT(c1, c2, t), all in Z: q0 = t, q1 = c1, q2 = c2), k = 3
+ * FBX_REV_XIN     bit q0 ^= 1 iff the input bit is set, and the gate -- its error site included -- exists only then
+ *                 (bitstring_prep's RX(pi * bit)), k = 1, the bit held in Z */
+#define FBX_REV_SITE 0
+#define FBX_REV_NOT 1
+#define FBX_REV_XOR 2
+#define FBX_REV_ANDXOR 3
+#define FBX_REV_XIN 4
+
+/* fbx_reversible_sample_shots: the circuit words[G] on |0..0>, run for B items (noise) x P units (input words) x n_shots shots,
+ * followed by a Z measurement of the m qubits out_qubits[m] (uint8, m in 1..64; column j of a record is qubit out_qubits[j]).
+ * noise_class [G] uint8: a class < K, 1 <= K <= 16, or FBX_DFE_NOISELESS; NULL = every gate is class 0.  inputs [P] uint64: the
+ * input word of unit r, read by XIN.  class_error [B][K] or NULL (= 0).  readout_flip [B][m][2] or NULL, per record column:
+ * [j][0] = P(read 1 | drawn 0), [j][1] = P(read 0 | drawn 1).  expected [P] uint64 or NULL: the expected record of unit r, packed
+ * in record-column order (bit j = column j).  Unit r is the global input index first_input + r, item b the global item
+ * first_item + b.  Outputs, each may be NULL, not all of the first three:
+ *   bits_out      [B][P][n_shots][m] uint8 0 / 1 -- for one item the layout of get_n_bit_adder_results;
+ *   words_out     [B][P][n_shots] uint64, the same record packed, bit j = column j;
+ *   weight_counts [B][P][m + 1] int64: entry w = the number of shots whose record differs from expected[r] in w columns (the
+ *                 weight-kind histogram of fbx_bit_histogram over bits_out, exactly); needs expected; zeroed by the call;
+ *   status_out    [B]: 0 good, 1 poisoned.
+ *
+ * THE MODEL.  A Pauli error flips the bit of a qubit iff it has an X part (X, Y) on a qubit that holds its bit in Z or a Z part
+ * (Y, Z) on a qubit that holds it in X; every other part is a phase that the final Z measurement never sees.  After a gate of
+ * class c, item b applies the depolarizing channel of fbx_clifford_sample_shots to the gate's k qubits: with probability
+ * class_error[b][c] a Pauli drawn uniformly from ALL 4^k Paulis, the identity included.  Under this noise the shots are exact
+ * samples of the circuit's outcome distribution.
+ *
+ * THE STREAM (part of the contract: it is what a host check restates).  Shot s of unit R = first_input + r of item
+ * g = first_item + b owns the Philox4x32-10 blocks with counter (g, R, s, j) and key (seed low ^ 0x52565253, seed high), words
+ * x0 .. x3 each; g and R are below 2^32.
+ *   Block l >> 1:  gate l, words (x0, x1) for even l and (x2, x3) for odd l.  A gate that exists and whose class is not
+ *                  FBX_DFE_NOISELESS errs iff (double) x_first * 2^-32 < class_error[b][c]; the Pauli index is then
+ *                  x_second >> (32 - 2 k): operand i has the Pauli (index >> 2 (k - 1 - i)) & 3; 0 I, 1 X, 2 Y, 3 Z.
+ *   Readout:       with J = (G + 1) >> 1, column j reads word j & 3 of block J + (j >> 2) and flips iff
+ *                  (double) x * 2^-32 < readout_flip[b][j][d], d the drawn bit of the column.
+ * Only the blocks that are needed are computed.  A record depends on (seed, g, R, s), the circuit and its item's noise only: not
+ * on B, P, n_shots or the launch shape.
+ *
+ * n_qubits or m outside 1..64, K outside 1..16, G >= 2^31, n_shots >= 2^32, a negative size or first index, first_item + B or
+ * first_input + P above 2^32, 2^31 or more workgroups (of four units of 64 shots: B * P * ceil(n_shots / 64) / 4), a NULL words (G > 0), inputs (P > 0) or
+ * out_qubits, weight_counts without expected, bits_out, words_out and weight_counts all NULL: FBX_ERR_BAD_ARG before any buffer is
+ * touched.  B, P or n_shots of 0: nothing is done.  A poisoned item -- a class error or a flip outside [0, 1], or NaN -- gets
+ * status 1, records of zeros and counts of zero; its neighbours are untouched.  The host form also refuses an invalid word (an
+ * unknown micro-op, k not that of the micro-op, an operand that is not below n_qubits or repeats, a set bit in an unused field),
+ * an invalid class and an out_qubits entry that is not below n_qubits; the _dev form takes them as validated (qubit indices are
+ * six bits: no access depends on a word's content), enqueues on the calling thread's stream and does not synchronise. */
+int fbx_reversible_sample_shots(int n_qubits, int64_t G, const uint32_t* words, const uint8_t* noise_class, int K, int64_t P,
+                                const uint64_t* inputs, int m, const uint8_t* out_qubits, const uint64_t* expected, int64_t B,
+                                int64_t n_shots, const double* class_error, const double* readout_flip, uint64_t seed,
+                                int64_t first_item, int64_t first_input, uint8_t* bits_out, uint64_t* words_out,
+                                int64_t* weight_counts, int32_t* status_out);
+int fbx_reversible_sample_shots_dev(int n_qubits, int64_t G, const uint32_t* d_words, const uint8_t* d_noise_class, int K, int64_t P,
+                                    const uint64_t* d_inputs, int m, const uint8_t* d_out_qubits, const uint64_t* d_expected,
+                                    int64_t B, int64_t n_shots, const double* d_class_error, const double* d_readout_flip,
+                                    uint64_t seed, int64_t first_item, int64_t first_input, uint8_t* d_bits_out,
+                                    uint64_t* d_words_out, int64_t* d_weight_counts, int32_t* d_status_out);
+
 /* out[b] = op(a[b]) diag(scale[b]) op(b[b]) for stacks of N x N complex matrices, N in 1..1024: op = the matrix itself
  * (conj_t = 0) or its conjugate transpose (conj_t = 1); scale is [B][N] real or NULL.  The products around fbx_eigh:
  * V f(lambda) V^H (sqrtm_psd, calculational.py:77-91), sqrt(rho) sigma sqrt(rho) (fidelity, distance_measures.py:64-84). */

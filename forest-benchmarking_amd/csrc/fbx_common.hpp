@@ -44,6 +44,7 @@ int option_pgdb1_binned();                       // fbx_set_option("pgdb1_binned
 double option_qv_wide_workspace_mib();          // fbx_set_option("qv_wide_workspace_mib"): cap of the state workspace of fbx_qv_heavy_outputs_wide
 double option_sample_wide_workspace_mib();      // fbx_set_option("sample_wide_workspace_mib"): cap of the table workspace of fbx_sample_bitstrings_wide
 double option_qv_noisy_workspace_mib();         // fbx_set_option("qv_noisy_workspace_mib"): cap of the partial-sum workspace of fbx_qv_noisy_trajectories
+double option_native_workspace_mib();           // fbx_set_option("native_workspace_mib"): cap of the partial-sum workspace of fbx_native_trajectories
 int option_pgdb_packed_1q();                  // fbx_set_option("pgdb_packed_1q"): single-qubit PGDB on the lane-per-item kernel: 0 never, 1 large batches (default), 2 always
 // Defaults of those options: the eigensolver of PGDB's CP projections stops at an off-diagonal norm of
 // <this> x the previous outer step (relative to ||H||_F), never tighter than 1e-13; 0 = always 1e-13.
@@ -60,7 +61,7 @@ long long option_pgdb_host_chunk();                      // fbx_set_option("pgdb
 // Named grow-only device workspaces of the calling thread (kept between calls; released by
 // fbx_release_workspace).  A workspace only ever serves kernels on the calling thread's stream, so
 // growing it (stream sync + hipFree + hipMalloc) cannot pull memory from under another thread's kernel.
-enum WorkspaceSlot { WS_PGDB_BASIS = 0, WS_PGDB3_BASIS = 1, WS_SWEEP_REF = 2, WS_COMM = 3, WS_CONVERT = 4, WS_PGDB1_COUNTER = 5, WS_PGDB1_BINS = 6, WS_PGDB_PIECES = 7, WS_DIAMOND = 8, WS_CHERNOFF = 9, WS_FIT = 10, WS_QV_WIDE = 11, WS_SAMPLE_WIDE = 12, WS_QV_NOISY = 13, WS_PGDB3_ETA = 14, WS_COUNT = 15 };
+enum WorkspaceSlot { WS_PGDB_BASIS = 0, WS_PGDB3_BASIS = 1, WS_SWEEP_REF = 2, WS_COMM = 3, WS_CONVERT = 4, WS_PGDB1_COUNTER = 5, WS_PGDB1_BINS = 6, WS_PGDB_PIECES = 7, WS_DIAMOND = 8, WS_CHERNOFF = 9, WS_FIT = 10, WS_QV_WIDE = 11, WS_SAMPLE_WIDE = 12, WS_QV_NOISY = 13, WS_PGDB3_ETA = 14, WS_NATIVE = 15, WS_COUNT = 16 };
 int workspace(WorkspaceSlot slot, size_t bytes, void** out);
 // staging blocks of the host-pointer entry points: taken from / returned to the calling thread's pool
 int pool_take(size_t bytes, void** out);

@@ -318,6 +318,8 @@ std::atomic<double> g_sample_wide_ws_mib{128.0};       // fbx_sample_bitstrings_
 double option_sample_wide_workspace_mib() { return g_sample_wide_ws_mib.load(); }
 std::atomic<double> g_qv_noisy_ws_mib{128.0};          // fbx_qv_noisy_trajectories: cap of the chunk's partial sums
 double option_qv_noisy_workspace_mib() { return g_qv_noisy_ws_mib.load(); }
+std::atomic<double> g_native_ws_mib{128.0};            // fbx_native_trajectories: cap of the chunk's partial sums
+double option_native_workspace_mib() { return g_native_ws_mib.load(); }
 int option_pgdb_pieces() { return g_pieces.load(); }
 int option_pgdb1_binned() { return g_binned_1q.load(); }
 }  // namespace fbx
@@ -452,6 +454,10 @@ int fbx_set_option(const char* name, double value) {
         FBX_REQUIRE(value >= 1.0 && value <= 65536.0, "fbx_set_option: qv_noisy_workspace_mib must be in [1, 65536]");
         fbx::g_qv_noisy_ws_mib.store(value); return FBX_OK;
     }
+    if (n == "native_workspace_mib") {
+        FBX_REQUIRE(value >= 0.015625 && value <= 65536.0, "fbx_set_option: native_workspace_mib must be in [1/64, 65536]");
+        fbx::g_native_ws_mib.store(value); return FBX_OK;
+    }
     set_error("fbx_set_option: unknown option '" + n + "'");
     return FBX_ERR_BAD_ARG;
 }
@@ -469,6 +475,7 @@ int fbx_get_option(const char* name, double* value) {
     if (n == "qv_wide_workspace_mib") { *value = fbx::g_qv_wide_ws_mib.load(); return FBX_OK; }
     if (n == "sample_wide_workspace_mib") { *value = fbx::g_sample_wide_ws_mib.load(); return FBX_OK; }
     if (n == "qv_noisy_workspace_mib") { *value = fbx::g_qv_noisy_ws_mib.load(); return FBX_OK; }
+    if (n == "native_workspace_mib") { *value = fbx::g_native_ws_mib.load(); return FBX_OK; }
     set_error("fbx_get_option: unknown option '" + n + "'");
     return FBX_ERR_BAD_ARG;
 }

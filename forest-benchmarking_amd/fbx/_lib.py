@@ -35,6 +35,9 @@ DFE_NOISELESS = 255             # noise class of a gate without noise (include/f
 RPE_SIM_LANE_MIN_UNITS = 131072 # from this many (item, depth, basis) units on a lane takes a unit (csrc/fbx_rpe_sim.hip)
 SPEC_LANE_MIN_UNITS = 131072    # ... and of fbx_spec_acquire: FBX_TOMO_LANE_MIN_UNITS (item, point) units (csrc/fbx_sim_shared.hpp)
 SPEC_MAX_POINTS = 65536         # points per item of fbx_spec_acquire
+NAT_I, NAT_RX, NAT_RZ, NAT_CZ, NAT_XY = range(5)        # opcodes of a native-gate word (include/fbx.h)
+NAT_WAVE_MAX_QUBITS = 8         # FBX_NAT_WAVE_MAX_QUBITS: the largest width one wavefront runs in fbx_native_trajectories
+NAT_SEG = 8                     # trajectories per partial sum of its probs_mean_out (csrc/fbx_native.hip)
 
 
 class FbxError(RuntimeError):
@@ -250,6 +253,12 @@ PROTOTYPES = {
                                     C.c_uint64, _i64, _i64, _u8p, _u64p, _i64p, _ip],
     "fbx_reversible_sample_shots_dev": [C.c_int, _i64, _vp, _vp, C.c_int, _i64, _vp, C.c_int, _vp, _vp, _i64, _i64, _vp, _vp,
                                         C.c_uint64, _i64, _i64, _vp, _vp, _vp, _vp],
+    "fbx_native_trajectories": [C.c_int, _i64, _u32p, _dp, _u8p, C.c_int, _i64, _u64p, C.c_int, _u8p, _i64, _i64, _dp, C.c_uint64,
+                                _i64, _i64, _dp, _ip, _ip],
+    "fbx_native_trajectories_dev": [C.c_int, _i64, _vp, _vp, _vp, C.c_int, _i64, _vp, C.c_int, _vp, _i64, _i64, _vp, C.c_uint64,
+                                    _i64, _i64, _vp, _vp, _vp],
+    "fbx_native_unitary": [C.c_int, _i64, _u32p, _dp, _dp],
+    "fbx_native_unitary_dev": [C.c_int, _i64, _vp, _vp, _vp],
 }
 
 

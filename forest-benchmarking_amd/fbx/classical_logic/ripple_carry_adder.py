@@ -10,7 +10,11 @@ input bits, the register assignment works on a networkx graph where the referenc
 ``simulate_n_bit_adder_results`` stands where ``get_n_bit_adder_results`` runs the programs -- the shots of the circuit under
 depolarizing noise after every gate and readout flips, drawn on the GPU by ``fbx_reversible_sample_shots``.
 ``simulate_adder_statistics_batch`` keeps the records on the device and returns the statistics of a whole batch of noise
-settings; ``predicted_adder_statistics`` computes the same two arrays exactly, without sampling."""
+settings; ``predicted_adder_statistics`` computes the same two arrays exactly, without sampling.
+
+``simulate_compiled_adder_results`` and ``compiled_adder_statistics_batch`` run the adder as the hardware would: compiled to native
+gates by ``fbx.compilation.basic_compile`` -- the Toffoli as its 123-gate decomposition -- with an error after every native gate, on
+a state vector (``fbx_native_trajectories``)."""
 from typing import Sequence
 
 import numpy as np
@@ -22,7 +26,8 @@ from .primitives import CNOT_X_basis, majority_gate, unmajority_add_gate
 __all__ = ["adder_expected_bits", "get_success_probabilities_from_results", "get_error_hamming_distributions_from_results",
            "get_success_probabilities_from_results_batch", "get_error_hamming_distributions_from_results_batch",
            "assign_registers_to_line_or_cycle", "get_qubit_registers_for_adder", "adder", "default_adder_registers",
-           "simulate_n_bit_adder_results", "simulate_adder_statistics_batch", "predicted_adder_statistics"]
+           "simulate_n_bit_adder_results", "simulate_adder_statistics_batch", "predicted_adder_statistics",
+           "compiled_adder_circuit", "simulate_compiled_adder_results", "compiled_adder_statistics_batch"]
 
 
 def adder_expected_bits(n_bits: int) -> np.ndarray:
@@ -255,4 +260,114 @@ def predicted_adder_statistics(n_bits, class_error, registers=None, in_x_basis=F
         for b in range(ce.shape[0]):
             dist = reversible.exact_distribution(words, n_qubits, word, ce[b], cls, None if flips is None else flips[b], out_qubits)
             hamming[b, r] = np.bincount(weight, weights=dist, minlength=m + 1)
+    return np.ascontiguousarray(hamming[:, :, 0]), hamming
+
+
+# --------------------------------------------------------------------------------------------------
+# The adder on native gates: compiled, with an error after every native gate, on a state vector
+# --------------------------------------------------------------------------------------------------
+def compiled_adder_circuit(n_bits, registers=None, in_x_basis=False):
+    """``adder`` compiled by ``basic_compile`` and encoded: ``(words, angles, n_qubits, out_qubits, noise_class)`` with the
+    default classes of ``native_circuit.native_noise_classes`` (0: RX, 1: RZ, 2: CZ).  ``n_bits <= 5`` on the default registers
+    (12 qubits); other registers must stay below qubit 13."""
+    from .. import native_circuit
+    from ..compilation import basic_compile
+    n_bits = int(n_bits)
+    if not 1 <= n_bits <= 5:
+        raise ValueError("n_bits must be 1..5: the state vector of 2 n_bits + 2 qubits has to fit the LDS of one CU")
+    registers = default_adder_registers(n_bits) if registers is None else registers
+    if len(registers[0]) != n_bits:
+        raise ValueError("the registers do not hold n_bits qubits each")
+    gates, out_qubits = adder(*registers, in_x_basis=in_x_basis)
+    n_qubits = max(max(registers[0]), max(registers[1]), registers[2], registers[3]) + 1
+    words, angles = native_circuit.encode_native(basic_compile(gates), n_qubits)
+    return words, angles, n_qubits, np.asarray(out_qubits, dtype=np.uint8), native_circuit.native_noise_classes(words)
+
+
+def _compiled_class_error(class_error):
+    ce = np.asarray(class_error, dtype=np.float64)
+    ce = ce.reshape(1, -1) if ce.ndim == 1 else ce
+    if ce.ndim != 2 or ce.shape[1] != 3:
+        raise ValueError("class_error must be (p_rx, p_rz, p_cz) or [B, 3]")
+    return np.ascontiguousarray(ce)
+
+
+def _compiled_inputs(n_bits, inputs):
+    if inputs is None:
+        return np.arange(1 << (2 * n_bits), dtype=np.uint64)
+    inputs = np.ascontiguousarray(np.asarray(inputs, dtype=np.uint64).ravel())
+    if inputs.size and int(inputs.max()) >> (2 * n_bits):
+        raise ValueError("an input word spells a in bits n .. 2n - 1 and b in bits 0 .. n - 1: nothing above")
+    return inputs
+
+
+def _compiled_marginals(dev, circuit, ce, inputs, trajectories, seed, first_item, first_input):
+    """The resident front of both calls: upload, ``fbx_native_trajectories_dev``; the dict of device buffers it returns."""
+    from .. import native_circuit
+    words, angles, n_qubits, out_qubits, cls = circuit
+    T = int(trajectories)
+    if not 1 <= T < 2 ** 32:
+        raise ValueError("need 1 <= trajectories < 2^32")
+    return native_circuit.native_trajectories_dev(
+        dev, n_qubits, words.size, dev.upload(words), dev.upload(angles), dev.upload(cls), 3, inputs.size, dev.upload(inputs),
+        out_qubits.size, dev.upload(out_qubits), ce.shape[0], T, dev.upload(ce), seed, first_item, first_input)
+
+
+def simulate_compiled_adder_results(n_bits, registers=None, in_x_basis=False, num_shots=100, class_error=(0.0, 0.0, 0.0),
+                                    trajectories=256, readout_flip=None, seed=0) -> np.ndarray:
+    """``get_n_bit_adder_results`` (ripple_carry_adder.py:248-314) on a simulated device that runs NATIVE gates: ``[4^n,
+    num_shots, n + 1]`` uint8, for each pair of summands ``num_shots`` measured answers.  Resident on the device: ``adder`` ->
+    ``basic_compile`` -> ``fbx_native_trajectories_dev`` (the mean outcome distribution of the answer qubits over
+    ``trajectories`` Pauli-error trajectories per pair) -> ``fbx_sample_bitstrings_dev`` (the shots, and ``readout_flip`` [n + 1,
+    2] per answer column).  ``class_error = (p_rx, p_rz, p_cz)``: the probability of a uniformly random Pauli after every RX
+    pulse, every (virtual) RZ and every CZ.  The shots of a pair are drawn from the MEAN of its trajectories: exact without gate
+    noise, and otherwise up to the sampling error of that mean (``1 / sqrt(trajectories)`` per probability)."""
+    from .. import _lib
+    from ..sampling import _noise, _raise_poisoned
+    circuit = compiled_adder_circuit(n_bits, registers, in_x_basis)
+    ce = _compiled_class_error(class_error)
+    if ce.shape[0] != 1:
+        raise ValueError("one noise setting per call; compiled_adder_statistics_batch takes a batch")
+    inputs = _compiled_inputs(int(n_bits), None)
+    P, m, key = int(inputs.size), int(n_bits) + 1, int(seed) & (2 ** 64 - 1)
+    shots, _, flips, _ = _noise(P, m, num_shots, None, readout_flip)
+    with _lib.DeviceScope() as dev:
+        res = _compiled_marginals(dev, circuit, ce, inputs, trajectories, key, 0, 0)
+        d_bits, d_status = dev.alloc(P * shots * m), dev.alloc(4 * P)
+        _lib.check(_lib.lib().fbx_sample_bitstrings_dev(m, P, shots, res["probs_mean"].ptr, None, _lib.devptr(dev.upload(flips)), key, 0,
+                                                        d_bits.ptr, d_status.ptr))
+        if res["status"].to_array(np.int32, (1,))[0]:
+            raise ValueError("a probability is outside [0, 1]")
+        if shots:
+            _raise_poisoned(d_status.to_array(np.int32, (P,)), 0, "simulate_compiled_adder_results")
+        return d_bits.to_array(np.uint8, (P, shots, m))
+
+
+def compiled_adder_statistics_batch(n_bits, class_error, registers=None, in_x_basis=False, trajectories=256, seed=0, inputs=None,
+                                    first_item=0, first_input=0):
+    """B noise settings ``class_error [B, 3]`` = (p_rx, p_rz, p_cz) of the compiled adder at once.  Returns ``(success [B, P],
+    hamming [B, P, n + 2])`` in the layout of ``simulate_adder_statistics_batch``, from the mean marginals of
+    ``fbx_native_trajectories_dev`` alone: the expectation over shots given the trajectories, without sampling -- entry w of
+    ``hamming`` is the weight the mean distribution puts on the answers that differ from a + b in w bits.  ``inputs``: the input
+    words r (default all 4^n pairs).  A poisoned setting is a row of NaN."""
+    from .. import _lib
+    n_bits = int(n_bits)
+    circuit = compiled_adder_circuit(n_bits, registers, in_x_basis)
+    ce = np.asarray(class_error, dtype=np.float64)
+    if ce.ndim != 2:
+        raise ValueError("class_error must be [B, 3]")
+    ce = _compiled_class_error(ce)
+    inputs = _compiled_inputs(n_bits, inputs)
+    B, P, m = ce.shape[0], int(inputs.size), n_bits + 1
+    with _lib.DeviceScope() as dev:
+        res = _compiled_marginals(dev, circuit, ce, inputs, trajectories, seed, first_item, first_input)
+        probs = res["probs_mean"].to_array(np.float64, (B, P, 1 << m))
+    words = inputs.astype(np.int64)
+    answer = (words >> n_bits) + (words & ((1 << n_bits) - 1))
+    diff = answer[:, None] ^ np.arange(1 << m)[None, :]
+    weight = np.zeros(diff.shape, dtype=np.int64)
+    for j in range(m):
+        weight += (diff >> j) & 1
+    hamming = np.stack([np.where(weight[None] == w, probs, 0.0).sum(axis=2) for w in range(m + 1)], axis=2)
+    hamming[np.isnan(probs).any(axis=2)] = np.nan
     return np.ascontiguousarray(hamming[:, :, 0]), hamming

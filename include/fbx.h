@@ -139,7 +139,10 @@ int         fbx_release_workspace(void);
  *   "sample_wide_workspace_mib" (default 128, range [1, 65536]): fbx_sample_bitstrings_wide[_dev] runs its batch in chunks of as
  *   many items as fit this many MiB of device workspace (always at least one item).  Results do not depend on it.
  *   "qv_noisy_workspace_mib" (default 128, range [1, 65536]): fbx_qv_noisy_trajectories[_dev] with probs_mean_out runs its batch
- *   in chunks of as many circuits as fit this many MiB of partial sums (always at least one circuit).  Results do not depend on it. */
+ *   in chunks of as many circuits as fit this many MiB of partial sums (always at least one circuit).  Results do not depend on it.
+ *   "native_workspace_mib" (default 128, range [1/64, 65536]): fbx_native_trajectories[_dev] with probs_mean_out runs its batch in
+ *   chunks of as many (item, input) pairs as fit this many MiB of partial sums (always at least one pair).  Results do not depend
+ *   on it. */
 int         fbx_set_option(const char* name, double value);
 int         fbx_get_option(const char* name, double* value);
 
@@ -1541,6 +1544,90 @@ int fbx_reversible_sample_shots_dev(int n_qubits, int64_t G, const uint32_t* d_w
                                     int64_t B, int64_t n_shots, const double* d_class_error, const double* d_readout_flip,
                                     uint64_t seed, int64_t first_item, int64_t first_input, uint8_t* d_bits_out,
                                     uint64_t* d_words_out, int64_t* d_weight_counts, int32_t* d_status_out);
+
+/* ---------------------------------------------------------------- circuits of native gates on a state vector, 1..13 qubits
+ * A circuit as the hardware runs it -- compiled to I, RX, RZ, CZ and XY (fbx.compilation.basic_compile, the reference's
+ * compilation.py) -- on a state vector, with a Pauli error after every native gate (csrc/fbx_native.hip).  This
+ * is the simulator under the Toffoli's decomposition, which is neither Clifford nor classical.  Amplitude index i has qubit 0 as
+ * its MOST significant bit, as fbx_qv_heavy_outputs.
+ *
+ * THE WORD (uint32):
+ *   bits  0..2   opcode, FBX_NAT_*
+ *   bits  3..6   q0
+ *   bits  7..10  q1 of CZ and XY, different from q0 (0 for the one-qubit gates)
+ *   bit   11     1: the gate is conditional
+ *   bits 12..17  a conditional gate: the bit of the unit's input word that decides whether the gate -- its error site included --
+ *                exists (0 otherwise)
+ *   bits 18..31  0
+ * angles [G] float64 holds the angle of RX, RZ and XY, and 0 for I and CZ (it is not read for them, but must be finite):
+ *   FBX_NAT_I    nothing: an error site only
+ *   FBX_NAT_RX   [[cos a/2, -i sin a/2], [-i sin a/2, cos a/2]], any finite angle
+ *   FBX_NAT_RZ   diag(exp(-i a/2), exp(i a/2))
+ *   FBX_NAT_CZ   diag(1, 1, 1, -1)
+ *   FBX_NAT_XY   1 (+) [[cos a/2, i sin a/2], [i sin a/2, cos a/2]] (+) 1 on |00>, (|01>, |10>), |11> */
+#define FBX_NAT_I 0
+#define FBX_NAT_RX 1
+#define FBX_NAT_RZ 2
+#define FBX_NAT_CZ 3
+#define FBX_NAT_XY 4
+/* the largest width at which one wavefront runs a trajectory; above it a workgroup does (tests straddle it) */
+#define FBX_NAT_WAVE_MAX_QUBITS 8
+
+/* fbx_native_trajectories: the circuit words[G], angles[G] on |0..0>, run for B items (noise) x P units (input words) x T
+ * stochastic Pauli-error trajectories.  noise_class [G] uint8: a class < K, 1 <= K <= 16, or FBX_DFE_NOISELESS; NULL = every gate
+ * is class 0.  inputs [P] uint64: the input word of unit r, read by the conditional gates.  class_error [B][K] or NULL (= 0).
+ * out_qubits [m] uint8, 1 <= m <= n_qubits, all different.  Unit r is the global input index first_input + r, item b the global
+ * item first_item + b.  Outputs, not both of the first two NULL:
+ *   probs_mean_out [B][P][2^m]  the mean over the T trajectories of the outcome distribution of the m qubits out_qubits: column c of
+ *                               out_qubits is bit m - 1 - c of the index (column 0 the most significant), so a row feeds
+ *                               fbx_sample_bitstrings_dev directly; m = n_qubits with out_qubits = 0 .. n - 1 is the full distribution;
+ *   n_errors_out   [B][P][T]    int32: the gates of the trajectory that erred (a draw of the identity Pauli counts);
+ *   status_out     [B]          0 good, 1 poisoned; may be NULL.
+ *
+ * THE MODEL is that of fbx_clifford_sample_shots and fbx_reversible_sample_shots.  After a gate that exists and whose class c is not
+ * FBX_DFE_NOISELESS, with probability class_error[b][c], a Pauli drawn uniformly from ALL 4^k Paulis of the gate's k qubits, the
+ * identity included, is applied.  Only probabilities leave the kernel, so Y is applied as X Z (a global phase).
+ *
+ * THE STREAM (part of the contract: it is what a host check restates).  Trajectory t of unit R = first_input + r of item
+ * g = first_item + b owns the Philox4x32-10 blocks with counter (g, R, t, j) and key (seed low ^ 0x4E415456, seed high) ("NATV"),
+ * words x0 .. x3 each; g and R are below 2^32.  Block l >> 1 serves gate l: words (x0, x1) for even l and (x2, x3) for odd l.  A
+ * gate errs iff (double) x_first * 2^-32 < class_error[b][c]; the Pauli index is then x_second >> (32 - 2 k): operand i (q0, q1)
+ * has the Pauli (index >> 2 (k - 1 - i)) & 3; 0 I, 1 X, 2 Y, 3 Z.  Only the blocks that are needed are computed.  A trajectory
+ * depends on (seed, g, R, t), the circuit and its item's noise only.
+ *
+ * THE MEAN is summed in an order that depends on T and n_qubits alone, without floating-point atomics: a trajectory's
+ * probabilities |amplitude|^2 are added up over 8 consecutive trajectories in the order of t; an output of the marginal is the sum,
+ * over its amplitudes in ascending index order, of each amplitude's partial sums in order, divided once by T.  An item repeats bit
+ * for bit under another B, another P, another first_item / first_input offset and another "native_workspace_mib" (fbx_set_option).
+ *
+ * n_qubits outside 1..13: FBX_ERR_UNSUPPORTED, before any buffer is touched.  m outside 1..n_qubits, K outside 1..16, T >= 2^32,
+ * G >= 2^31, a negative size or first index, first_item + B or first_input + P above 2^32, a NULL words or angles (G > 0), inputs
+ * (P > 0) or out_qubits, both outputs NULL: FBX_ERR_BAD_ARG, before any buffer is touched.  B, P or T of 0: nothing is done.
+ * G = 0 gives the distribution of |0..0>.  A poisoned item -- a class error outside [0, 1], or NaN -- gets status 1, NaN
+ * probabilities and zero error counts; its neighbours are untouched.  The host form also refuses an invalid word (an unknown
+ * opcode, a qubit that is not below n_qubits, q1 == q0 or a q1 of a one-qubit gate, a set bit in an unused field), a non-finite
+ * angle, an invalid class and an out_qubits entry that repeats or is not below n_qubits.  The _dev form takes them as validated,
+ * enqueues on the calling thread's stream and does not synchronise (growing the workspace does); it never indexes outside the
+ * state or its workspace whatever the words hold: a gate whose qubits do not fit the width is skipped and, like a non-finite
+ * angle, makes EVERY item poisoned, and with a bad out_qubits entry the probabilities are NaN. */
+int fbx_native_trajectories(int n_qubits, int64_t G, const uint32_t* words, const double* angles, const uint8_t* noise_class, int K,
+                            int64_t P, const uint64_t* inputs, int m, const uint8_t* out_qubits, int64_t B, int64_t T,
+                            const double* class_error, uint64_t seed, int64_t first_item, int64_t first_input,
+                            double* probs_mean_out, int32_t* n_errors_out, int32_t* status_out);
+int fbx_native_trajectories_dev(int n_qubits, int64_t G, const uint32_t* d_words, const double* d_angles,
+                                const uint8_t* d_noise_class, int K, int64_t P, const uint64_t* d_inputs, int m,
+                                const uint8_t* d_out_qubits, int64_t B, int64_t T, const double* d_class_error, uint64_t seed,
+                                int64_t first_item, int64_t first_input, double* d_probs_mean_out, int32_t* d_n_errors_out,
+                                int32_t* d_status_out);
+
+/* The unitary of a circuit of native gates, U_out [2^n][2^n] complex128 row-major: column j is the circuit applied to basis state j,
+ * through the gate loop of fbx_native_trajectories without noise.  Rows and columns are indexed as pyquil's program_unitary (and
+ * fbx.compilation.program_unitary) does: qubit 0 is the LEAST significant bit.  n_qubits 1..13 (others FBX_ERR_UNSUPPORTED); the
+ * buffer is the caller's (16 * 4^n bytes).  The host form refuses invalid words, non-finite angles and conditional gates
+ * (FBX_ERR_BAD_ARG); in the _dev form a conditional gate does not exist, and a column is NaN where a gate does not fit the width
+ * or an angle is not finite. */
+int fbx_native_unitary(int n_qubits, int64_t G, const uint32_t* words, const double* angles, double* U_out);
+int fbx_native_unitary_dev(int n_qubits, int64_t G, const uint32_t* d_words, const double* d_angles, double* d_U_out);
 
 /* out[b] = op(a[b]) diag(scale[b]) op(b[b]) for stacks of N x N complex matrices, N in 1..1024: op = the matrix itself
  * (conj_t = 0) or its conjugate transpose (conj_t = 1); scale is [B][N] real or NULL.  The products around fbx_eigh:
